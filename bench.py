@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — ray-samples/s of the TensoRF render path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -19,9 +19,15 @@ A "step" = one pass of the hot path over one batch of synthetic rays resident in
 value = nominal ray-samples/s = (rays x 512) / time, whole job (every ray counted with all 512 samples, masked or
 terminated or not — SURVEY.md §8d).  Timed region: barrier + synchronize, K steps, synchronize + barrier; MAX over ranks.
 
-roofline.traffic is measured by THIS run: after the timed region, rank 0 (N = 1) re-runs a 2-step bench under
-`rocprofv3 --pmc` in child processes, one pass per counter set (FETCH_SIZE; WRITE_SIZE; SQ/GRBM sets), as
-MI355X_MICROARCH.md's HBM section prescribes (FETCH_SIZE doubled on gfx950).  If the profiler is unavailable the field is
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the timed launches' kernel_ms).
+--full adds everything that costs work behind the timed region: the rooflines (kernel durations of launches that have the chip,
+rocprofv3 --pmc passes), the CPU baselines, the opt-in arithmetics, two frames in flight, the other BASELINE configs and the training
+steps (child runs), and for N > 1 the frame rendered by one rank alone.
+--dump-outputs DIR writes what the last timed step returned (rgb, depth; NGPNetworks: rgb) as DIR/<name>.npy, float32.
+
+roofline.traffic (--full) is measured by THIS run: after the timed region, rank 0 (N = 1) re-runs a 2-step bench under
+`rocprofv3 --pmc` in child processes, one pass per counter set (FETCH_SIZE; WRITE_SIZE; SQ/GRBM sets); gfx950 counts a 128-B
+read as 64 B of FETCH_SIZE, so traffic = 2 x FETCH_SIZE + WRITE_SIZE.  If the profiler is unavailable the field is
 null and `traffic_source` says why — never a constant read from a committed file.
 """
 import argparse
@@ -136,6 +142,23 @@ def emit(result):
         os.write(_JSON_FD, line)
 
 
+DUMP_BYTES = 63_000_000        # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: device tensor of the last timed step} -> path/<name>.npy, float32.  Beyond DUMP_BYTES in all (a batch of
+    several frames), every array keeps the same fixed, seeded sample of rows (rays, in order), so two builds' files compare row for row."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        n = min(a.shape[0] for a in host.values())
+        keep = np.sort(np.random.default_rng(0).choice(n, n * DUMP_BYTES // total, replace=False))
+        host = {k: a[keep] for k, a in host.items()}
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def bench_ngp(args, world, rank, device):
     """BASELINE configs[4]: JNeRF Instant-NGP inference, one 800x800 frame per step through the fused frame path (tvr_ngp_render).  The
     path has no exchange step: for N > 1 every rank renders its own frames (replicas only)."""
@@ -168,13 +191,17 @@ def bench_ngp(args, world, rank, device):
     t0 = time.perf_counter()
     for i in range(args.steps):
         st, pr = {}, {}
-        sampler.render_frame(*frames[(args.warmup + i) % len(frames)], stats=st, profile=pr)
+        rgb = sampler.render_frame(*frames[(args.warmup + i) % len(frames)], stats=st, profile=pr)
+        if i < args.steps - 1:
+            rgb = None                                  # released at once, as before; the last frame is kept for --dump-outputs
         marched += st["samples"]
         evaluated += st["evaluated"]
         k_ms[0] += pr["march_ms"]
         k_ms[1] += pr["render_ms"]
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rgb": rgb})
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -185,7 +212,7 @@ def bench_ngp(args, world, rank, device):
     ach = BYTES * ev_per / (k_ms[1] * 1e-3) / 1e9
     # roofline.traffic, live, as on the main path: rocprofv3 --pmc child passes of this same command after the timed region (rank 0, N = 1)
     pmc, pmc_source = {}, "not collected (--pmc off or N > 1)"
-    if args.pmc == "auto" and world == 1 and rank == 0:
+    if args.full and args.pmc == "auto" and world == 1 and rank == 0:
         pmc, pmc_source = collect_pmc(["--model", "NGPNetworks"], passes=PMC_PASSES[:3])
     pr_ = _pmc_kernel(pmc, "ngp_render_kernel")
     traffic = (2.0 * pr_["FETCH_SIZE"] + pr_["WRITE_SIZE"]) * 1024.0 if ("FETCH_SIZE" in pr_ and "WRITE_SIZE" in pr_) else None
@@ -199,15 +226,16 @@ def bench_ngp(args, world, rank, device):
                    "samples": "value counts the occupied steps the march produces (what the reference feeds its networks); the frame kernel "
                               "evaluates only those in front of the compositor's T < 1e-4 break"},
         "rays_per_sec": W * W * world * args.steps / dt,
-        "effective": {"marched_samples_per_frame": marched / args.steps, "evaluated_samples_per_frame": ev_per},
         "kernel_ms": {"march": k_ms[0], "render": k_ms[1]},
-        "roofline": {"kernel": "ngp_render_kernel<true>", "bound": "hbm", "achieved": ach, "peak": 8000.0, "unit": "GB/s", "frac": ach / 8000.0,
-                     "traffic": traffic, "traffic_source": pmc_source, "algorithmic_bytes_per_launch": BYTES * ev_per, "ms": k_ms[1],
-                     "clock_GHz_pmc_pass": (pr_["GRBM_GUI_ACTIVE"] / 8.0 / pr_["_dur_s"] / 1e9) if (pr_.get("GRBM_GUI_ACTIVE") and pr_.get("_dur_s")) else None,
-                     "mfma_busy_frac": (pr_["SQ_VALU_MFMA_BUSY_CYCLES"] / 1024.0 / (pr_["GRBM_GUI_ACTIVE"] / 8.0)) if pr_.get("GRBM_GUI_ACTIVE") and "SQ_VALU_MFMA_BUSY_CYCLES" in pr_ else None,
-                     "note": f"{BYTES} B per evaluated sample; the 52 MB of tables sit in L2 / MALL, so the measured traffic is fabric traffic of random 128-B lines"},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result["effective"] = {"marched_samples_per_frame": marched / args.steps, "evaluated_samples_per_frame": ev_per}
+        result["roofline"] = {"kernel": "ngp_render_kernel<true>", "bound": "hbm", "achieved": ach, "peak": 8000.0, "unit": "GB/s", "frac": ach / 8000.0,
+                              "traffic": traffic, "traffic_source": pmc_source, "algorithmic_bytes_per_launch": BYTES * ev_per, "ms": k_ms[1],
+                              "clock_GHz_pmc_pass": (pr_["GRBM_GUI_ACTIVE"] / 8.0 / pr_["_dur_s"] / 1e9) if (pr_.get("GRBM_GUI_ACTIVE") and pr_.get("_dur_s")) else None,
+                              "mfma_busy_frac": (pr_["SQ_VALU_MFMA_BUSY_CYCLES"] / 1024.0 / (pr_["GRBM_GUI_ACTIVE"] / 8.0)) if pr_.get("GRBM_GUI_ACTIVE") and "SQ_VALU_MFMA_BUSY_CYCLES" in pr_ else None,
+                              "note": f"{BYTES} B per evaluated sample; the 52 MB of tables sit in L2 / MALL, so the measured traffic is fabric traffic of random 128-B lines"}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import ngp_oracle as N
         o, d = frames[0]
         sel = torch.arange(0, W * W, 311, device=device)[:2048]                                 # a strided sample of pose 0
@@ -256,7 +284,7 @@ def collect_pmc(extra_args, budget_s=420.0, passes=None):
             break
         d = tempfile.mkdtemp(prefix="tvr_pmc_", dir="/tmp")
         cmd = [exe, "--pmc", *counters, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--pmc", "off", *extra_args]
+               "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--pmc", "off", *extra_args]
         try:
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=240)
             files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
@@ -292,7 +320,7 @@ def other_configs(budget_s=240.0):
         if time.time() - t0 > budget_s:
             out[key] = "skipped: time budget"
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--pmc", "off", *extra]
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--pmc", "off", *extra]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=200, env=dict(os.environ))
             d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -459,8 +487,12 @@ def main():
                                                               "default = the library's (30 720); 0 = one launch set per call, as before round 6")
     ap.add_argument("--chunk-stream", action="store_true", help="with --chunk: the chunk calls go through render.FrameStream (two calls in flight on two streams) "
                                                                 "instead of one after the other")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1 default workload: do not append the BASELINE configs[3] / configs[4] lines (child runs of this script)")
-    ap.add_argument("--pmc", choices=["auto", "off"], default="auto", help="auto: rank 0 at N = 1 measures roofline.traffic with rocprofv3 --pmc child passes")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N = 1 default workload: do not append the BASELINE configs[3] / configs[4] lines (child runs of this script)")
+    ap.add_argument("--pmc", choices=["auto", "off"], default="auto", help="auto: with --full, rank 0 at N = 1 measures roofline.traffic with rocprofv3 --pmc child passes")
+    ap.add_argument("--full", action="store_true", help="also measure what costs work behind the timed region: rooflines, CPU baselines, arith modes, two frames "
+                                                        "in flight, the other configs and training steps, N > 1: the frame on one rank alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy, float32 (beyond "
+                                                                         "63 MB in all: a fixed, seeded sample of its rays)")
     ap.add_argument("--img", type=int, default=int(os.environ.get("TVR_BENCH_IMG", "800")), help="frame edge in pixels (800 = the BASELINE workload; "
                                                                                               "smaller only for rehearsals / tests)")
     args = ap.parse_args()
@@ -587,7 +619,7 @@ def main():
             return pipe.submit(s % n_patterns, step_rays[s % n_patterns])
 
     # (20.64 ms per step against 20.62 ms of kernels).  When a rank's share is a fraction of a frame (strong split / --emulate-world: 2.7 ms
-    # of kernels at N = 8) the timed region runs without them and the kernel durations are taken in K more steps afterwards.
+    # of kernels at N = 8) the timed region runs without them and the kernel durations are taken in K more steps afterwards (--full; a plain line says calls 0).
     prof_in_region = split == 1
     prof_w = C.c_void_p()
     L.check(L.lib().tvr_profile_create(max(args.warmup, 1), C.byref(prof_w)), "tvr_profile_create")
@@ -626,11 +658,13 @@ def main():
         else:
             # per-kernel events on every FOURTH timed step: a frame in 21 pieces records 84 events, +0.05 ... 0.15 ms per frame (scripts/debug/instr_cost.py); kernel_ms is
             # the average over the recorded steps (kernel_ms.calls of them), the in-kernel statistics cover every step
-            step(args.warmup + s, profile=prof if (prof_in_region and s % 4 == 0) else None, stats=stats)
+            last = step(args.warmup + s, profile=prof if (prof_in_region and s % 4 == 0) else None, stats=stats)
+            if s < args.steps - 1:
+                last = None                                         # released at once, as before; the last step's outputs are kept for --dump-outputs
         if trace is not None:
             trace.append(time.perf_counter() - t0)
     if pipe is not None:
-        pipe.flush()
+        last = pipe.flush()
     torch.cuda.synchronize()
     if trace is not None:
         print("host time after each step call (ms):", [round(t * 1e3, 2) for t in trace], "after sync: %.2f" % ((time.perf_counter() - t0) * 1e3), file=sys.stderr)
@@ -639,7 +673,9 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     gc.enable()
-    if not prof_in_region:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rgb": last[0], "depth": last[1]})
+    if args.full and not prof_in_region:
         keep_pieces = model.render_piece_rays
         model.render_piece_rays = 0                                 # kernel durations of launches that have the chip (a 320 000-ray share would go out in pieces: see below)
         for s in range(args.steps):
@@ -670,7 +706,7 @@ def main():
     k_ms_timed, stats_timed = list(k_ms), stats
     if not prof_in_region:
         n_pieces = 1                                                # (the kernel durations above were taken with pieces off)
-    if n_pieces > 1 and args.chunk == 0 and split == 1:
+    if args.full and n_pieces > 1 and args.chunk == 0 and split == 1:
         keep = model.render_piece_rays
         model.render_piece_rays = 0
         prof_s = C.c_void_p()
@@ -718,7 +754,7 @@ def main():
     # BASELINE configs[2]'s own yardstick: the SAME frame rendered by one rank alone (outside the timed region; every rank does it on its own
     # GPU so that nobody idles at the next barrier, rank 0's time is reported).  SURVEY 8e: efficiency = t_1 / (N t_N).
     strong_split = None
-    if strong:
+    if args.full and strong:
         torch.cuda.synchronize()
         dist.barrier()
         t1s = []
@@ -744,7 +780,7 @@ def main():
     # roofline.traffic: rocprofv3 --pmc passes over a 2-step run of this same bench, in CHILD processes (spawned, never exec'd from this
     # process), after the timed region — run before it, the profiler sessions left every later launch of this process ~0.5 ms slower
     # (24.0 vs 22.5 ms per step at identical kernel times), which would have distorted `value`.
-    if args.pmc == "auto" and world == 1 and rank == 0 and default_workload:
+    if args.full and args.pmc == "auto" and world == 1 and rank == 0 and default_workload:
         extra = (["--alpha-mask", str(args.alpha_mask)] if args.alpha_mask else []) + (["--eps-T", str(args.eps_T)] if args.eps_T is not None else [])
         pmc, pmc_source = collect_pmc(extra + ["--pieces", "0"])     # per-dispatch counters of the one-launch-set kernels (the roofline's kernels)
 
@@ -863,20 +899,21 @@ def main():
                    "eps_T": float(model.rayMarch_weight_thres) if args.eps_T is None else args.eps_T, "tile": TILE,
                    "chunk": args.chunk if args.chunk > 0 else n_mine, "alpha_mask": args.alpha_mask, "emulate_world": args.emulate_world, "arith": args.arith},
         "rays_per_sec": rays_job * args.steps / dt,
-        "effective": {"density_samples_evaluated_per_sec": m_eval * world * args.steps / dt,
-                      "appearance_samples_per_sec": m_app * world * args.steps / dt,
-                      "frac_samples_evaluated": m_eval / (n_mine * S),
-                      # (round 6: this was called frac_samples_in_box; the counter only runs over the chunks a ray visits before it terminates, so it is NOT the in-box
-                      #  fraction of all nominal samples — without an alpha mask it equals frac_samples_evaluated by construction)
-                      "frac_samples_in_box_of_visited_chunks": m_bbox / (n_mine * S),
-                      "app_samples_per_ray": m_app / n_mine},
         "kernel_ms": {"march": k_ms_timed[0], "shade": k_ms_timed[1], "composite": k_ms_timed[2], "calls": n_calls, "pieces_per_call": n_pieces,
                       "note": ("sums over the pieces of a call of the HIP-event durations of the TIMED launches; two pieces are in flight at a time on two streams, so these are "
                                "durations under co-scheduling (march + shade + composite > ms_per_step)" if n_pieces > 1 else "HIP events around each kernel of the timed launches")
                               + ("; recorded on every fourth timed step (`calls` of them)" if prof_in_region else "")},
-        "roofline": dominant,
-        "roofline_all": {"march": roof_march, "shade": roof_shade},
     }
+    if args.full:
+        result["effective"] = {"density_samples_evaluated_per_sec": m_eval * world * args.steps / dt,
+                               "appearance_samples_per_sec": m_app * world * args.steps / dt,
+                               "frac_samples_evaluated": m_eval / (n_mine * S),
+                               # (round 6: this was called frac_samples_in_box; the counter only runs over the chunks a ray visits before it terminates, so it is NOT the
+                               #  in-box fraction of all nominal samples — without an alpha mask it equals frac_samples_evaluated by construction)
+                               "frac_samples_in_box_of_visited_chunks": m_bbox / (n_mine * S),
+                               "app_samples_per_ray": m_app / n_mine}
+        result["roofline"] = dominant
+        result["roofline_all"] = {"march": roof_march, "shade": roof_shade}
     if pieces_autotune is not None:
         result["config"]["pieces_autotune"] = dict(pieces_autotune, note="--autotune: decided on this card in the warm-up (model.autotune_render_pieces)")
     if pipe is not None:
@@ -889,17 +926,17 @@ def main():
         result["check"] = check
     if strong_split is not None:
         result["strong_split"] = strong_split
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(arrs, A, fr[0], with_c=(args.model == "TensorVMSplit"))
     elif rank == 0:
         result["cpu_baseline"] = None
     # The other single-GPU lines of BASELINE.json, measured by THIS run (child processes of this script, after the timed region, so that whoever runs the
-    # default command also gets them): configs[3] = the same frame as 157 direct 4096-ray tvr_render calls (train.py's batch size, no chunk merging),
+    # --full command also gets them): configs[3] = the same frame as 157 direct 4096-ray tvr_render calls (train.py's batch size, no chunk merging),
     # configs[4] = the JNeRF Instant-NGP alt path.  Informational: `value` above is configs[1].
-    if rank == 0 and world == 1 and default_workload and not args.no_extras and args.arith == "f32":
+    if args.full and rank == 0 and world == 1 and default_workload and not args.no_extras and args.arith == "f32":
         result["arith_modes"] = arith_modes(model, step_rays, S, args.eps_T, m_app)
         result["frame_stream_two_in_flight"] = frame_stream(model, step_rays, S, args.eps_T)
-    if rank == 0 and world == 1 and default_workload and not args.no_extras and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and default_workload and not args.no_extras and not args.no_cpu_baseline:
         result["other_configs"] = other_configs()
     L.lib().tvr_profile_destroy(prof)
     L.lib().tvr_profile_destroy(prof_w)

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 for round in 1 2; do
 for v in "$@"; do
   if [ "$v" = default ]; then unset TVR_LIB_PATH; else export TVR_LIB_PATH=$R/jittor-myc-nerfs_amd/lib/variants/libtvr_$v.so; fi
-  python3 $R/bench.py --steps 10 --warmup 3 --pmc off --no-cpu-baseline ${AB_ARGS} 2>/dev/null | python3 -c "
+  python3 $R/bench.py --steps 10 --warmup 3 --full --pmc off --no-cpu-baseline ${AB_ARGS} 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms']
 ra=d.get('roofline_all',{}); cm=(ra.get('march') or {}).get('clock_GHz') or 0.0; cs=(d.get('roofline') or {}).get('clock_GHz') or 0.0

@@ -68,7 +68,7 @@ def main():
     worlds = [1, 2, 4, 8]
     rows = {}
     for w in worlds:
-        base = [sys.executable, BENCH, "--steps", str(args.steps), "--warmup", "3", "--no-cpu-baseline", "--pmc", "off"]
+        base = [sys.executable, BENCH, "--steps", str(args.steps), "--warmup", "3", "--full", "--no-cpu-baseline", "--pmc", "off"]
         d = run_json(base + (["--emulate-world", str(w), "--no-overlap-exchange"] if w > 1 else []))
         rows[str(w)] = {"rays": d["config"]["rays_per_rank"], "tile": d["config"]["tile"], "ms_per_step": d["ms_per_step"], "kernel_ms": d["kernel_ms"],
                         "clock_GHz": {"march": d["roofline_all"]["march"]["clock_GHz"], "shade": d["roofline_all"]["shade"]["clock_GHz"]}}
@@ -94,7 +94,7 @@ def main():
         port = 36500 + os.getpid() % 2000
         t0 = time.time()
         d = run_json([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                      BENCH, "--gpus", "2", "--steps", str(args.steps), "--warmup", "3", "--check", "--no-cpu-baseline"], env=env, timeout=1500)
+                      BENCH, "--gpus", "2", "--steps", str(args.steps), "--warmup", "3", "--check", "--full", "--no-cpu-baseline"], env=env, timeout=1500)
         out["gloo_world2_one_card"] = {"ms_per_step": d["ms_per_step"], "strong_split": d.get("strong_split"), "check": d.get("check"), "kernel_ms": d["kernel_ms"],
                                        "wall_s": time.time() - t0,
                                        "note": "both ranks share the card (their kernels serialise) and gloo stages the 2 x 5.1 MB through the host: an upper bound of "

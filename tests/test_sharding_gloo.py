@@ -169,7 +169,7 @@ def test_bench_step_world2_on_one_card(scaling, img, tmp_path):
     env = dict(os.environ, TVR_BENCH_BACKEND="gloo", TVR_BENCH_IMG=str(img), HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = 35500 + os.getpid() % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--check", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--check", "--full", "--no-cpu-baseline"]
     if scaling != "default":
         cmd += ["--scaling", scaling]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1100)
@@ -268,7 +268,7 @@ def test_bench_exchange_over_rccl_with_one_rank():
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("TVR_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--one-rank-exchange", "--check", "--no-cpu-baseline", "--pmc", "off"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--one-rank-exchange", "--check", "--full", "--no-cpu-baseline", "--pmc", "off"],
                        env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
