@@ -25,15 +25,12 @@
 
 #define BG_MAX_BLOCKS 77                      // fragment blocks (2 KiB each) per stage image
 #define BG_BIAS_FLOATS 640                    // 4 x 128 base biases, 64 rgb-hidden, sigma, 3 rgb (padded)
-#define BG_LDS_BYTES (BG_MAX_BLOCKS * 2048 + BG_BIAS_FLOATS * 4)
 #define BG_WAVES 8
-#ifndef TVR_BG_APF
-#define TVR_BG_APF 0
-#endif
-// Round 6: the STREAMED form (default).  The fragment image lies in the order the kernel consumes it and moves through two 64 KB halves of LDS in chunks of at most
+// Round 6: the STREAMED form.  The fragment image lies in the order the kernel consumes it and moves through two 64 KB halves of LDS in chunks of at most
 // BG_HALF_BLOCKS blocks: while every wave computes on the chunk in one half, the next chunk arrives in the other by LDS-DMA (global_load_lds_dwordx4: no registers, no
-// ds_write), ONE workgroup barrier per chunk.  Round 5's form (two 154 KB stages, each loaded synchronously between two barriers: 4 barriers and 300 KB of exposed
-// L2 -> LDS traffic per 256 samples, measured at 11 % of the kernel: profiles/r06_bg_kernel.txt) stays selectable with -DTVR_BG_STREAM=0 for A/B builds.
+// ds_write), ONE workgroup barrier per chunk.  (Round 5's form — two 154 KB stages, each loaded synchronously between two barriers: 4 barriers and 300 KB of exposed
+// L2 -> LDS traffic per 256 samples, measured at 11 % of the kernel: profiles/r06_bg_kernel.txt — is described in DESIGN.md 9.)
+// TVR_BG_STREAM 2: one wave per SIMD carrying two tiles (written and correct, the open lead for this kernel); 1: the shipped form.
 #ifndef TVR_BG_STREAM
 #define TVR_BG_STREAM 1
 #endif
@@ -133,51 +130,6 @@ __device__ __forceinline__ f32x16 bias_acc(const float *__restrict__ bias32, int
     }
     return a;
 }
-// one k-step into NB accumulators (independent blocks: their MFMAs interleave): A fragments from LDS, then AR products per block
-// (AR = tvr_mlpnet_desc.arith, include/tvr.h TVR_ARITH_*: 3 = Wlo*xhi + Whi*xlo + Whi*xhi, fp32-class; 2 = Wlo*xhi + Whi*xhi, the layer inputs rounded to fp16;
-// 1 = Whi*xhi.  What a mode does not multiply is neither read nor derived — frag8<AR>, tvr_mfma.h)
-template <int NB>
-struct AFrags {
-    uint4 h[NB], l[NB];
-};
-template <int NB, int AR>
-__device__ __forceinline__ AFrags<NB> load_a(const uint4 *__restrict__ w4, const int (&blk)[NB])
-{
-    AFrags<NB> a;
-#pragma unroll
-    for (int m = 0; m < NB; ++m) {
-        a.h[m] = w4[(blk[m] * 2 + 0) * 64];
-        if constexpr (AR >= 2) a.l[m] = w4[(blk[m] * 2 + 1) * 64];
-    }
-    return a;
-}
-template <int NB, int AR>
-__device__ __forceinline__ void mma(const AFrags<NB> &a, const Frag &b, f32x16 (&acc)[NB])
-{
-    if constexpr (AR >= 2) {
-#pragma unroll
-        for (int m = 0; m < NB; ++m) acc[m] = MFMAH(a.l[m], b.hi, acc[m]);
-    }
-    if constexpr (AR >= 3) {
-#pragma unroll
-        for (int m = 0; m < NB; ++m) acc[m] = MFMAH(a.h[m], b.lo, acc[m]);
-    }
-#pragma unroll
-    for (int m = 0; m < NB; ++m) acc[m] = MFMAH(a.h[m], b.hi, acc[m]);
-}
-template <int NB, int AR>
-__device__ __forceinline__ void kstep(const uint4 *__restrict__ w4, const int (&blk)[NB], const Frag &b, f32x16 (&acc)[NB])
-{
-    mma<NB, AR>(load_a<NB, AR>(w4, blk), b, acc);
-}
-
-__device__ __forceinline__ void load_stage(uint4 *__restrict__ lds4, const uint4 *__restrict__ image, int n_blocks)
-{
-    const int n = n_blocks * 128;
-    for (int e = threadIdx.x; e < n; e += BG_WAVES * 64) lds4[e] = image[e];
-}
-
-// base layers [l0, l1) on one 32-sample tile: act in (unused when l0 == 0) -> act out
 // relu(act) of this lane's sample: accumulator register 4q + i of block mb <-> neuron 32 mb + 8 q + 4 h + i
 template <int NB>
 __device__ __forceinline__ void store_mask(unsigned long long *__restrict__ out, long long s, int hh, const f32x16 (&act)[NB])
@@ -200,215 +152,15 @@ __device__ __forceinline__ void store_relu128(float *__restrict__ out, long long
                 make_float4(relu_f(act[mb][4 * q]), relu_f(act[mb][4 * q + 1]), relu_f(act[mb][4 * q + 2]), relu_f(act[mb][4 * q + 3]));
 }
 
-template <int AR>
-__device__ __forceinline__ void base_layers(const BgProgram &P, int l0, int l1, const uint4 *__restrict__ w4, const float *__restrict__ lbias, int hh,
-                                            const float x[4], f32x16 (&act)[4], const BgTrain &T, long long s_store)
-{
-    for (int l = l0; l < l1; ++l) {
-        f32x16 out[4];
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) out[mb] = bias_acc(lbias + l * 128 + mb * 32, hh);
-        const int prev = P.base_prev[l], pe = P.base_pe[l], spm = (prev ? 8 : 0) + (pe ? P.n_pe_steps : 0), b0 = P.base_block0[l];
-        if (prev) {
-#if TVR_BG_APF
-            // the A fragments of k-step t+1 are fetched from LDS before the MFMAs of k-step t are issued (LDS latency off the MFMA path)
-            const int blk0[4] = {b0, b0 + spm, b0 + 2 * spm, b0 + 3 * spm};
-            AFrags<4> a = load_a<4, AR>(w4, blk0);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int tn = t < 7 ? t + 1 : 7;
-                const int blk[4] = {b0 + tn, b0 + spm + tn, b0 + 2 * spm + tn, b0 + 3 * spm + tn};
-                const AFrags<4> an = load_a<4, AR>(w4, blk);
-                const Frag b = relu_frag4<AR>(act, t);
-                mma<4, AR>(a, b, out);
-                a = an;
-            }
-#else
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const Frag b = relu_frag4<AR>(act, t);
-                const int blk[4] = {b0 + t, b0 + spm + t, b0 + 2 * spm + t, b0 + 3 * spm + t};
-                kstep<4, AR>(w4, blk, b, out);
-            }
-#endif
-        }
-        if (pe) {
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                if (t < P.n_pe_steps) {
-                    const Frag b = pe_frag<AR>(t, hh, x);
-                    const int o = b0 + (prev ? 8 : 0) + t;
-                    const int blk[4] = {o, o + spm, o + 2 * spm, o + 3 * spm};
-                    kstep<4, AR>(w4, blk, b, out);
-                }
-            }
-        }
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) act[mb] = out[mb];
-        if (T.A[0] && s_store >= 0) {
-            store_relu128(T.A[l], s_store, hh, act);
-            if (T.MA[l]) store_mask<4>(T.MA[l], s_store, hh, act);
-        }
-    }
-}
-
-// heads on one tile: sigma and the 64-wide rgb hidden layer share the fragments of `base`; returns (rgb, sigma) of sample col in the
-// lanes with hh == 0
-template <int AR>
-__device__ __forceinline__ float4 heads(const BgProgram &P, const uint4 *__restrict__ w4, const float *__restrict__ lbias, int hh, const float d[3],
-                                        const f32x16 (&act)[4], const BgTrain &T, long long s_store)
-{
-    f32x16 hd[3] = {{0}, bias_acc(lbias + 512, hh), bias_acc(lbias + 512 + 32, hh)};      // sigma, rgb hidden block 0 / 1
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const Frag b = relu_frag4<AR>(act, t);
-        const int blk[3] = {P.sig_block0 + t, P.rgbh_block0 + t, P.rgbh_block0 + 9 + t};
-        kstep<3, AR>(w4, blk, b, hd);
-    }
-    f32x16 rh[2] = {hd[1], hd[2]};
-    {
-        // view-direction embedding: [d, sin d, cos d, sin 2d, cos 2d] (15 values, one k-step)
-        float v[8];
-        const float v0[8] = {d[0], d[1], d[2], __sinf(d[0]), __sinf(d[1]), __sinf(d[2]), __cosf(d[0]), __cosf(d[1])};
-        const float v1[8] = {__cosf(d[2]), __sinf(2.f * d[0]), __sinf(2.f * d[1]), __sinf(2.f * d[2]), __cosf(2.f * d[0]), __cosf(2.f * d[1]), __cosf(2.f * d[2]), 0.f};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = hh ? v1[j] : v0[j];
-        const int blk[2] = {P.rgbh_block0 + 8, P.rgbh_block0 + 9 + 8};
-        kstep<2, AR>(w4, blk, frag8<AR>(v), rh);
-    }
-    if (T.Hrgb && s_store >= 0) {
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *(float4 *)(T.Hrgb + s_store * 64 + 32 * mb + 8 * q + 4 * hh) =
-                    make_float4(relu_f(rh[mb][4 * q]), relu_f(rh[mb][4 * q + 1]), relu_f(rh[mb][4 * q + 2]), relu_f(rh[mb][4 * q + 3]));
-        if (hh == 0) T.sig_pre[s_store] = hd[0][0] + lbias[576];
-        if (T.MH) store_mask<2>(T.MH, s_store, hh, rh);
-    }
-    f32x16 eo[1] = {{0}};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = relu_f(t < 2 ? rh[0][8 * (t & 1) + j] : rh[1][8 * (t & 1) + j]);
-        const int blk[1] = {P.rgbo_block0 + t};
-        kstep<1, AR>(w4, blk, frag8<AR>(v), eo);
-    }
-    return make_float4(1.0f / (1.0f + __expf(-(eo[0][0] + lbias[580]))), 1.0f / (1.0f + __expf(-(eo[0][1] + lbias[581]))),
-                       1.0f / (1.0f + __expf(-(eo[0][2] + lbias[582]))), fabsf(hd[0][0] + lbias[576]));
-}
-
-#ifndef TVR_BG_TICKETS
-#define TVR_BG_TICKETS 1          // 1: dynamic hand-out of the super-tiles (0: static stride over the workgroups)
-#endif
-#ifndef TVR_BG_DIAG
-#define TVR_BG_DIAG 0             // timing stand-ins (WRONG results, never shipped): 1 = the LDS stage images are loaded for the first super-tile only (what the reloads
-#endif                            // cost), 2 = ... and no workgroup barriers around them either (what the lockstep costs)
-#ifndef TVR_BG_NT
-#define TVR_BG_NT 1               // 32-sample tiles a wave carries through each LDS stage (their stage-A activations wait in registers)
-#endif
-
-template <int AR>
-__global__ void __launch_bounds__(BG_WAVES * 64, 1) bg_mlp_kernel(BgProgram P, const uint4 *__restrict__ image, const float *__restrict__ bias,
-                                                                 const float *__restrict__ pts, const float *__restrict__ viewdirs, long long M,
-                                                                 float *__restrict__ rgb, float *__restrict__ sigma, const BgTrain T, unsigned *__restrict__ tk)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ long long s_next;
-    uint4 *lds4 = reinterpret_cast<uint4 *>(smem);
-    float *lbias = reinterpret_cast<float *>(smem + BG_MAX_BLOCKS * 2048);
-    for (int e = threadIdx.x; e < BG_BIAS_FLOATS; e += BG_WAVES * 64) lbias[e] = bias[e];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, col = lane & 31;
-    constexpr int NT = TVR_BG_NT, PER_SUPER = 32 * BG_WAVES * NT;
-    const long long n_super = (M + PER_SUPER - 1) / PER_SUPER;
-    const uint4 *imgA = image, *imgB = image + (size_t)P.blocksA * 128;
-    const int la = min(P.split, P.D);
-
-    // Round 5: super-tiles are handed out dynamically (the first one static, later ones by an atomicAdd on `tk`, a word the launcher zeroes) — the XCDs do not run at one
-    // speed under an MFMA-heavy kernel and equal static shares leave the fast ones idle at the end (profiles/r05_shade_tail.txt).  The atomic for the tile after next is
-    // issued a whole super-tile before its value is read.  Which workgroup evaluates a sample does not matter to the sample.
-    unsigned tk_pending = 0;
-    if (tk && threadIdx.x == 0) tk_pending = atomicAdd(tk, 1u);
-    for (long long super = blockIdx.x; super < n_super;) {
-        int hh = h, lane_off = lane;
-        asm volatile("" : "+v"(hh), "+v"(lane_off));                // opaque per tile: keeps per-lane selects / LDS reads from being hoisted
-        const uint4 *w4 = lds4 + lane_off;
-        f32x16 act[NT][4];
-        // ---------------- stage A: base layers [0, split)
-#if TVR_BG_DIAG
-        const bool diag_first = super == (long long)blockIdx.x;
-        if (TVR_BG_DIAG < 2 || diag_first) __syncthreads();
-        if (diag_first) load_stage(lds4, imgA, P.blocksA);
-        if (TVR_BG_DIAG < 2 || diag_first) __syncthreads();
-#else
-        __syncthreads();                                             // everyone is done with the previous tile's stage B
-        load_stage(lds4, imgA, P.blocksA);
-        __syncthreads();
-#endif
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const long long s = ((super * NT + nt) * BG_WAVES + wave) * 32 + col, sr = min(s, M - 1);
-            const float4 p = *reinterpret_cast<const float4 *>(pts + 4 * sr);
-            const float x[4] = {p.x, p.y, p.z, p.w};
-            base_layers<AR>(P, 0, la, w4, lbias, hh, x, act[nt], T, s < M ? s : -1);
-        }
-        // ---------------- stage B: the remaining base layers and the heads
-#if TVR_BG_DIAG
-        if (TVR_BG_DIAG < 2) { __syncthreads(); __syncthreads(); }
-#else
-        __syncthreads();
-        load_stage(lds4, imgB, P.blocksB);
-        __syncthreads();
-#endif
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const long long s = ((super * NT + nt) * BG_WAVES + wave) * 32 + col, sr = min(s, M - 1);
-            const float4 p = *reinterpret_cast<const float4 *>(pts + 4 * sr);
-            const float x[4] = {p.x, p.y, p.z, p.w};
-            const float *v = viewdirs + 3 * (sr / P.samples_per_ray);
-            const float d[3] = {v[0], v[1], v[2]};
-            base_layers<AR>(P, la, P.D, w4, lbias, hh, x, act[nt], T, s < M ? s : -1);
-            const float4 r = heads<AR>(P, w4, lbias, hh, d, act[nt], T, s < M ? s : -1);
-            if (h == 0 && s < M) {
-                sigma[s] = r.w;
-                rgb[3 * s] = r.x;
-                rgb[3 * s + 1] = r.y;
-                rgb[3 * s + 2] = r.z;
-            }
-        }
-        if (tk) {
-            if (threadIdx.x == 0) {
-                const long long nx = (long long)gridDim.x + (long long)tk_pending;
-                s_next = nx;
-                if (nx < n_super) tk_pending = atomicAdd(tk, 1u);
-            }
-            __syncthreads();
-            super = s_next;                        // (the next iteration's first barrier orders this read before thread 0's next write)
-        } else {
-            super += gridDim.x;
-        }
-    }
-}
 __global__ void bg_zero_ticket_kernel(unsigned *tk) { *tk = 0u; }
 
 // ------------------------------------------------------------------------------------------------ the streamed kernel (round 6)
 typedef __attribute__((address_space(3))) void bg_lds_void;
 typedef __attribute__((address_space(1))) const void bg_glb_void;
-struct AF { uint4 h, l; };
 #define BG_SB __builtin_amdgcn_sched_barrier(0)
 #define BG_SG_MFMA(n) __builtin_amdgcn_sched_group_barrier(0x008, (n), 0)
 #define BG_SG_VALU(n) __builtin_amdgcn_sched_group_barrier(0x402, (n), 0)      // VALU | TRANS
 #define BG_SG_DSR(n) __builtin_amdgcn_sched_group_barrier(0x100, (n), 0)
-#ifndef TVR_BG_SCHED
-#define TVR_BG_SCHED 1            // sched_group_barrier windows in the units (0: hipcc's own order, A/B)
-#endif
-#ifndef TVR_BG_STAGE
-#define TVR_BG_STAGE 0            // 1: the chunk transfer as global_load_dwordx4 -> registers -> ds_write_b128 one k-step later, instead of LDS-DMA (whose issue holds the wave ~100 cycles per KB)
-#endif
-#ifndef TVR_BG_PRIOFLIP
-#define TVR_BG_PRIOFLIP 0         // experiment: the two waves of a SIMD (w and w + 4) take turns at priority 1, k-step by k-step (keeps them abreast between the chunk barriers)
-#endif
 #ifndef TVR_BG_TIMING
 #define TVR_BG_TIMING 0           // diagnostic build: per-phase s_memtime sums of every wave into the work buffer's words 8.. (scripts/bg_phase_timing.py)
 #endif
@@ -423,15 +175,6 @@ struct AF { uint4 h, l; };
 #ifndef TVR_BG_PD_PREV
 #define TVR_BG_PD_PREV 1          // ... in the previous-activation units and the heads (2: measured below)
 #endif
-// the three products of one fragment block on ONE accumulator, back to back (a dependent chain of 32x32x16 MFMAs issues back to back: profiles/r04_mfma_issue_probe.txt);
-// per accumulator the order of the additions is tvr_mfma.h's / round 5's: Wlo*xhi, Whi*xlo, Whi*xhi
-template <int AR>
-__device__ __forceinline__ void mfma3(const AF &A, const Frag &b, f32x16 &acc)
-{
-    if constexpr (AR >= 2) acc = MFMAH(A.l, b.hi, acc);
-    if constexpr (AR >= 3) acc = MFMAH(A.h, b.lo, acc);
-    acc = MFMAH(A.h, b.hi, acc);
-}
 // One unit: NG k-steps x NB row blocks whose fragment blocks lie consecutively at `lb` (this lane's LDS address of the unit's first block), for the NTW 32-sample tiles a
 // wave carries.  hipcc's own schedule puts a k-step's A-fragment reads right in front of their MFMAs — `ds_read, s_waitcnt, MFMA` ~75 times per tile (scripts/isa_trace.py on
 // round 5's kernel) — so the reads run TVR_BG_PD blocks ahead here through a ring of {hi, lo} pairs, a fragment lives for 3 NTW MFMAs (the tiles of a wave SHARE every weight
@@ -478,7 +221,6 @@ __device__ __forceinline__ void run_unit(const unsigned char *lb, f32x16 (&acc)[
 #pragma unroll
             for (int w = 0; w < NTW; ++w) acc[w][m] = MFMAH(A.h, b[w].hi, acc[w][m]);
         }
-#if TVR_BG_SCHED
 #pragma unroll
         for (int m = 0; m < NB; ++m) {
             if (g * NB + m + PD < NQ) BG_SG_DSR(AR >= 2 ? 2 : 1);
@@ -488,7 +230,6 @@ __device__ __forceinline__ void run_unit(const unsigned char *lb, f32x16 (&acc)[
                 if (g + 1 < NG) BG_SG_VALU(VPG);
             }
         }
-#endif
         if (g + 1 < NG) {
 #pragma unroll
             for (int w = 0; w < NTW; ++w) b[w] = nb[w];
@@ -523,45 +264,13 @@ __global__ void __launch_bounds__(WAVES * 64, 1) bg_mlp_stream_kernel(BgProgram 
     int dma_p = 0, dma_n = 0;                                           // this wave's next piece / the chunk's piece count
     const unsigned char *dma_src = nullptr;
     unsigned dma_dst = 0;
-#if TVR_BG_PRIOFLIP
-    unsigned flip = (unsigned)(wave >> 2);
-#endif
-#if TVR_BG_STAGE
-    uint4 st_val[NTW];
-    unsigned st_dst[NTW];
-    int st_have[NTW];
-#pragma unroll
-    for (int i = 0; i < NTW; ++i) { st_have[i] = 0; st_dst[i] = 0; st_val[i] = make_uint4(0, 0, 0, 0); }
-#endif
     auto dma_step = [&]() {
-#if TVR_BG_PRIOFLIP
-        flip ^= 1u;
-        if (flip) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-#endif
-#if TVR_BG_STAGE
-        // register-staged: the piece requested one k-step ago goes to LDS now, the next one is requested
-#pragma unroll
-        for (int i = 0; i < NTW; ++i) {
-            if (st_have[i]) {
-                *reinterpret_cast<uint4 *>(smem + st_dst[i] + lane * 16) = st_val[i];
-                st_have[i] = 0;
-            }
-            if (dma_p < dma_n) {
-                st_val[i] = *reinterpret_cast<const uint4 *>(dma_src + (size_t)dma_p * 1024);
-                st_dst[i] = dma_dst + (unsigned)dma_p * 1024u;
-                st_have[i] = 1;
-                dma_p += WAVES;
-            }
-        }
-#else
 #pragma unroll
         for (int i = 0; i < NTW; ++i)                                   // (two tiles per wave: half the waves, twice the pieces each, twice the MFMAs per k-step to put them under)
             if (dma_p < dma_n) {
                 __builtin_amdgcn_global_load_lds((bg_glb_void *)(dma_src + (size_t)dma_p * 1024), (bg_lds_void *)(smem + dma_dst + dma_p * 1024), 16, 0, 0);
                 dma_p += WAVES;
             }
-#endif
     };
     auto issue_dma = [&](int c, int half) {                             // arm the DMA of chunk c into `half`
         dma_n = P.chunk_nblk[c] * 2;
@@ -575,9 +284,6 @@ __global__ void __launch_bounds__(WAVES * 64, 1) bg_mlp_stream_kernel(BgProgram 
     auto enter_chunk = [&]() {
         BG_STAMP(ta);
         while (dma_p < dma_n) dma_step();                               // (a chunk with fewer k-steps than pieces per wave: the rest now)
-#if TVR_BG_STAGE
-        dma_step();                                                     // (the last staged piece into LDS; the barrier below waits for the ds_write)
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         BG_STAMP(tb);
         __syncthreads();
@@ -940,14 +646,10 @@ static int mlpnet_launch(const BgLayout &L, const void *packed, const void *pts,
     auto *kern = bg_mlp_stream_kernel<AR, 2, 4>;                     // one wave per SIMD, two tiles per wave
     const int lds_bytes = BG_LDS_STREAM_BYTES;
     constexpr int KW = 4, KNT = 2;
-#elif TVR_BG_STREAM
+#else
     auto *kern = bg_mlp_stream_kernel<AR, 1, BG_WAVES>;
     const int lds_bytes = BG_LDS_STREAM_BYTES;
     constexpr int KW = BG_WAVES, KNT = 1;
-#else
-    auto *kern = bg_mlp_kernel<AR>;
-    const int lds_bytes = BG_LDS_BYTES;
-    constexpr int KW = BG_WAVES, KNT = TVR_BG_NT;
 #endif
     static bool attr_set = false;
     if (!attr_set) {
@@ -959,7 +661,7 @@ static int mlpnet_launch(const BgLayout &L, const void *packed, const void *pts,
     const char *base = static_cast<const char *>(packed);
     // the ticket word: word 0 of the caller's `work` buffer (tvr_mlpnet_work_bytes), zeroed here and advanced by the kernel.  One launch per work buffer at a time;
     // launches on different streams take different work buffers and may share the (read-only) packed network.
-    unsigned *tk = TVR_BG_TICKETS ? static_cast<unsigned *>(work) : nullptr;
+    unsigned *tk = static_cast<unsigned *>(work);
     if (tk) hipLaunchKernelGGL(bg_zero_ticket_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), tk);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(KW * 64), lds_bytes, static_cast<hipStream_t>(stream), L.P, reinterpret_cast<const uint4 *>(base),
                        reinterpret_cast<const float *>(base + (size_t)L.total_blocks * 2048), static_cast<const float *>(pts), static_cast<const float *>(viewdirs),
@@ -1004,7 +706,6 @@ int tvr_mlpnet_pack(const tvr_mlpnet_desc *desc, const tvr_mlpnet_params *p, voi
     const BgProgram &P = L.P;
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::vector<PackBlock> tab((size_t)L.total_blocks);
-#if TVR_BG_STREAM
     // consumption order (BgProgram): block (k-step t, row block mb) of a part at part_blk0 + t * (row blocks of the part) + mb
     auto put = [&](int blk, const void *W, int ld, int n_out, int row0, int kind, int t, int koff, int n_valid) {
         tab[(size_t)blk] = PackBlock{static_cast<const float *>(W), ld, n_out, row0, kind, t, koff, n_valid};
@@ -1023,27 +724,6 @@ int tvr_mlpnet_pack(const tvr_mlpnet_desc *desc, const tvr_mlpnet_params *p, voi
     }
     for (int mb = 0; mb < 2; ++mb) put(P.heads_blk0 + 24 + mb, p->rgbh_W_view, 15, 64, mb * 32, K_VIEW, 0, 0, 15);
     for (int t = 0; t < 4; ++t) put(P.heads_blk0 + 26 + t, p->rgbo_W, 64, 3, 0, K_PREV, t, 0, 64);
-#else
-    auto put = [&](int stage, int blk, const void *W, int ld, int n_out, int row0, int kind, int t, int koff, int n_valid) {
-        tab[(size_t)(stage ? P.blocksA : 0) + blk] = PackBlock{static_cast<const float *>(W), ld, n_out, row0, kind, t, koff, n_valid};
-    };
-    for (int l = 0; l < P.D; ++l) {
-        const int stage = l >= P.split, prev = P.base_prev[l], pe = P.base_pe[l], spm = (prev ? 8 : 0) + (pe ? P.n_pe_steps : 0);
-        const int ld = (prev ? 128 : 0) + (pe ? P.input_ch : 0);
-        for (int mb = 0; mb < 4; ++mb) {
-            const int b0 = P.base_block0[l] + mb * spm;
-            // cat(input_pts, base): the embedding occupies the first input_ch columns, the previous activations follow (MLPNet.forward)
-            if (prev) for (int t = 0; t < 8; ++t) put(stage, b0 + t, p->base_W[l], ld, 128, mb * 32, K_PREV, t, pe ? P.input_ch : 0, 128);
-            if (pe) for (int t = 0; t < P.n_pe_steps; ++t) put(stage, b0 + (prev ? 8 : 0) + t, p->base_W[l], ld, 128, mb * 32, K_PE, t, 0, P.input_ch);
-        }
-    }
-    for (int t = 0; t < 8; ++t) put(1, P.sig_block0 + t, p->sigma_W, 128, 1, 0, K_PREV, t, 0, 128);
-    for (int mb = 0; mb < 2; ++mb) {
-        for (int t = 0; t < 8; ++t) put(1, P.rgbh_block0 + mb * 9 + t, p->rgbh_W_base, 128, 64, mb * 32, K_PREV, t, 0, 128);
-        put(1, P.rgbh_block0 + mb * 9 + 8, p->rgbh_W_view, 15, 64, mb * 32, K_VIEW, 0, 0, 15);
-    }
-    for (int t = 0; t < 4; ++t) put(1, P.rgbo_block0 + t, p->rgbo_W, 64, 3, 0, K_PREV, t, 0, 64);
-#endif
     char *base = static_cast<char *>(packed);
     float *bias = reinterpret_cast<float *>(base + (size_t)L.total_blocks * 2048);
     PackBlock *dtab = reinterpret_cast<PackBlock *>(base + (size_t)L.total_blocks * 2048 + BG_BIAS_FLOATS * 4);

@@ -267,6 +267,32 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nblk)
     return x * q + (x < r ? x : r) + i;
 }
 
+// quad-level data movement as DPP VALU ops (quad_perm) instead of ds_bpermute: no LDS hop in front of the gather addresses
+template <int CTRL>
+__device__ __forceinline__ int quad_perm_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+template <int CTRL>
+__device__ __forceinline__ float quad_perm_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
+// broadcast lane k of each quad (quad_perm:[k,k,k,k]); k is a constant after unrolling, the switch folds away
+__device__ __forceinline__ int quad_bcast_i(int v, int k)
+{
+    switch (k) {
+    case 0: return quad_perm_i<0x00>(v);
+    case 1: return quad_perm_i<0x55>(v);
+    case 2: return quad_perm_i<0xAA>(v);
+    default: return quad_perm_i<0xFF>(v);
+    }
+}
+__device__ __forceinline__ float quad_bcast_f(float v, int k) { return __int_as_float(quad_bcast_i(__float_as_int(v), k)); }
+#define QUAD_XOR1 0xB1                    // quad_perm:[1,0,3,2]
+#define QUAD_XOR2 0x4E                    // quad_perm:[2,3,0,1]
+// sum over the 64 lanes, in every lane
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // accumulator register r of lane half h  <->  row of the 32x32 tile
 __device__ __forceinline__ constexpr int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 

@@ -107,12 +107,6 @@ __global__ __launch_bounds__(64 * TG_WAVES) void gemm_tn_kernel(const float *__r
 #ifndef TL_ROWS
 #define TL_ROWS 16
 #endif
-#ifndef TVR_GEMM_SPLIT16
-#define TVR_GEMM_SPLIT16 1        // 0: the fused step's weight gradients keep the fp32 products (A/B switch)
-#endif
-#ifndef TG_DIAG
-#define TG_DIAG 0                 // timing experiments only: 1 no MFMAs (memory + staging alone), 2 no global fetch after the first chunk (matrix pipe alone)
-#endif
 #define TL_PF ((TL_ROWS * 320 + 255) / 256)          // floats (or float4s / 4) per thread and chunk, at most: 20 tiles = 320 columns
 
 // MODE 0: dword staging (any strides); 1: float4 staging of contiguous rows (lda == Ka, ldb == Kb: a chunk is one flat run of floats, any K);
@@ -315,7 +309,7 @@ __global__ __launch_bounds__(64 * TG_WAVES) void gemm_tn_lds_kernel(const float 
     }
     for (long long m = m0; m < m1; m += TL_ROWS) {
         const bool more = m + TL_ROWS < m1;
-        if (more && !((TG_DIAG & 2) && m > m0)) fetch(m + TL_ROWS, preA);   // global loads of the next chunk: in flight during this chunk's MFMAs
+        if (more) fetch(m + TL_ROWS, preA);                                 // global loads of the next chunk: in flight during this chunk's MFMAs
         __builtin_amdgcn_sched_barrier(0);
         const float *c_s = sm + cur * bufsz;
         // the operands of step u + 1 are read from LDS while the MFMAs of step u run (an MFMA that waits for its own ds_read costs the LDS
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(64 * TG_WAVES) void gemm_tn_lds_kernel(const float 
             __builtin_amdgcn_sched_barrier(0);                          // (hipcc would sink the reads behind this step's MFMAs and wait for them at once)
 #pragma unroll
             for (int q = 0; q < TG_MAXT; ++q)
-                if (q < nq && !(TG_DIAG & 1))                           // wave-uniform: tiles this wave does not have cost no matrix-pipe time
+                if (q < nq)                                             // wave-uniform: tiles this wave does not have cost no matrix-pipe time
                     acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(offA[q] >= 0 ? va[u & 1][q] : 0.0f, offB[q] >= 0 ? vb[u & 1][q] : (offB[q] == -2 ? 1.0f : 0.0f),
                                                                   acc[q], 0, 0, 0);
         }
@@ -362,120 +356,8 @@ __global__ __launch_bounds__(64 * TG_WAVES) void gemm_tn_lds_kernel(const float 
     }
 }
 
-// ------------------------------------------------------------------------------------------------ fp16-split variant (-DTVR_GEMM_F32=0; NOT the default)
-// Same reduction on v_mfma_f32_32x32x16_f16 with both operands split into fp16 hi + lo and three products per 16-row step (tvr_mfma.h;
-// error ~2^-22 relative, fp32-grade): 96 MFMA cycles per 16 rows and tile instead of 512, which moves the kernel from the fp32 matrix
-// pipe onto memory.  A wave owns one 32-column block of A (or of B when A has more than four) and walks the blocks of the other
-// operand, so every fragment is loaded and split once per wave: lane (col, h) reads rows m + 8h .. m + 8h + 7 of its column — the 8 k
-// values of an MFMA fragment — with 8 row-coalesced dword loads.
-// Measured and rejected as the default: 0.227 vs 0.26 ms at M = 3.6e5 and 0.8 vs 1.1 ms at M = 2.1e6 (the kernel is on memory and launch
-// latency, not on the fp32 matrix pipe), and fp16's exponent range is wrong for gradients — dY entries below 6e-8 vanish in the split and a
-// NerfPlusPlus background gradient came out 6e-3 off (tests/test_gpu_npp.py).  Forward activations are O(1); gradients are not.
-// (An fp32 kernel with this wave-owns-a-block fragment sharing was also tried: 0.63 vs 0.26 ms at 356 000 x 128 x 128 — slower, removed.)
-#ifndef TVR_GEMM_F32
-#define TVR_GEMM_F32 1
-#endif
-#ifndef TVR_GEMM_LDS
-#define TVR_GEMM_LDS 1
-#endif
-
-struct Rows8 {
-    float v[8];
-};
-__device__ __forceinline__ Rows8 fetch8(const float *__restrict__ X, int ld, int col, long long m, long long m1, int h)
-{
-    Rows8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const long long row = m + 8 * h + j;
-        const bool in = row < m1 && col >= 0;
-        const float v = X[(in ? row : m1 - 1) * ld + (col >= 0 ? col : 0)];      // unconditional load, clamped address (see above)
-        r.v[j] = in ? v : 0.0f;
-    }
-    return r;
-}
-
-__global__ __launch_bounds__(64 * TG_WAVES) void gemm_tn_f16_kernel(const float *__restrict__ A, const int lda, const int Ka,
-                                                                     const float *__restrict__ B, const int ldb, const int Kb,
-                                                                     const long long M_cap, float *__restrict__ P, const long long rpb_host, const unsigned *__restrict__ m_dev)
-{
-    // m_dev: the row count lives on the device (M_cap = capacity, the grid is sized for it); the slabs are then cut from the true count here
-    const long long M = m_dev ? ((long long)*m_dev < M_cap ? (long long)*m_dev : M_cap) : M_cap;
-    long long rows_per_block = rpb_host;
-    if (m_dev) {
-        rows_per_block = ((M + (long long)gridDim.x - 1) / (long long)gridDim.x + 15) / 16 * 16;
-        if (rows_per_block < 64) rows_per_block = 64;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const int nrb = (Ka + 31) >> 5, ncb = (Kb + 31) >> 5;
-    // own: the operand whose 32-column block this wave keeps; oth: the operand whose blocks it walks (at most TG_MAXT of them)
-    const bool own_is_a = nrb <= TG_WAVES;
-    const float *__restrict__ Xo = own_is_a ? A : B, *__restrict__ Xw = own_is_a ? B : A;
-    const int ldo = own_is_a ? lda : ldb, ldw = own_is_a ? ldb : lda, Ko = own_is_a ? Ka : Kb, Kw = own_is_a ? Kb : Ka;
-    const int nown = own_is_a ? nrb : ncb, nwalk = own_is_a ? ncb : nrb;
-    // with fewer than four own blocks the waves form groups that share an own block and split the walk: own block = wave % nown, and
-    // the wave's q-th walk block is group + q * groups
-    const int groups = TG_WAVES / nown, own_blk = wave % nown, group = wave / nown;
-    const bool active = group < groups;
-    const int col_o = (active && own_blk * 32 + i < Ko) ? own_blk * 32 + i : -1;
-    int col_w[TG_MAXT], blk_w[TG_MAXT];
-    f32x16 acc[TG_MAXT];
-#pragma unroll
-    for (int q = 0; q < TG_MAXT; ++q) {
-        blk_w[q] = (active && group + q * groups < nwalk) ? group + q * groups : -1;
-        col_w[q] = (blk_w[q] >= 0 && blk_w[q] * 32 + i < Kw) ? blk_w[q] * 32 + i : -1;
-        acc[q] = f32x16{0};
-    }
-    const long long m0 = (long long)blockIdx.x * rows_per_block;
-    const long long m1 = m0 >= M ? m0 : (m0 + rows_per_block < M ? m0 + rows_per_block : M);
-    if (active) {
-        Rows8 ro = fetch8(Xo, ldo, col_o, m0, m1, h), rw[TG_MAXT];
-#pragma unroll
-        for (int q = 0; q < TG_MAXT; ++q) rw[q] = fetch8(Xw, ldw, col_w[q], m0, m1, h);
-        float drain = 0.0f;
-        for (long long m = m0; m < m1; m += 16) {
-            // loads of the next 16 rows first (into fresh registers), then the splits and MFMAs of the current ones
-            const Rows8 no = fetch8(Xo, ldo, col_o, m + 16, m1, h);
-            Rows8 nw[TG_MAXT];
-#pragma unroll
-            for (int q = 0; q < TG_MAXT; ++q) nw[q] = fetch8(Xw, ldw, col_w[q], m + 16, m1, h);
-            const Frag fo = split8(ro.v);
-#pragma unroll
-            for (int q = 0; q < TG_MAXT; ++q) {
-                if (blk_w[q] >= 0) {
-                    const Frag fw = split8(rw[q].v);
-                    // C tile = (A block)^T (B block): the A fragment is the MFMA's first operand whichever operand this wave owns
-                    const Frag &fa = own_is_a ? fo : fw, &fb = own_is_a ? fw : fo;
-                    acc[q] = MFMAH(fa.lo, fb.hi, acc[q]);
-                    acc[q] = MFMAH(fa.hi, fb.lo, acc[q]);
-                    acc[q] = MFMAH(fa.hi, fb.hi, acc[q]);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            drain += acc[0][15];                                    // drains the wave's MFMAs before the next iteration reuses registers
-#pragma unroll
-            for (int q = 1; q < TG_MAXT; ++q) drain += acc[q][15];
-            __builtin_amdgcn_sched_barrier(0);
-            ro = no;
-#pragma unroll
-            for (int q = 0; q < TG_MAXT; ++q) rw[q] = nw[q];
-        }
-        if (drain == 1.2345e-30f && P == nullptr) P[0] = drain;     // keeps `drain` alive; never true
-#pragma unroll
-        for (int q = 0; q < TG_MAXT; ++q) {
-            if (blk_w[q] < 0) continue;
-            const int rb = own_is_a ? own_blk : blk_w[q], cb = own_is_a ? blk_w[q] : own_blk;
-            const int col = cb * 32 + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row < Ka && col < Kb) P[((size_t)blockIdx.x * Ka + row) * Kb + col] = acc[q][r];
-            }
-        }
-    }
-}
-
+// (A whole-kernel fp16-split variant — every product of this reduction on v_mfma_f32_32x32x16_f16, operands fetched per wave without LDS staging — was measured
+// and rejected: DESIGN_HISTORY.md.  fp16's exponent range is wrong for unscaled gradients; the F16 path above takes operands whose range is known.)
 // C[e] = sum over the slabs in a fixed order: 16 lanes per element (lane l adds slabs l, l+16, ... in order), then a fixed butterfly
 __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const float *__restrict__ P, const int n_slabs, const int n, float *__restrict__ C,
                                                              const float *__restrict__ scale)
@@ -545,30 +427,25 @@ hipError_t launch_gemm_tn(const float *A, int lda, int Ka, const float *B, int l
         if (rc == hipSuccess && bias_out) rc = hipMemsetAsync(bias_out, 0, (size_t)Ka * sizeof(float), stream);
         return rc;
     }
-    if (ones && !(TVR_GEMM_F32 && TVR_GEMM_LDS && TL_ROWS * (Ka + Kb) <= 256 * TL_PF)) return hipErrorInvalidValue;      // (only the LDS-staged kernel has the ones column)
+    if (ones && TL_ROWS * (Ka + Kb) > 256 * TL_PF) return hipErrorInvalidValue;      // (only the LDS-staged kernel has the ones column)
     const int lds = 64 * 1024;                                     // unused; caps the CU at two workgroups (see header)
     hipError_t rc = hipFuncSetAttribute((const void *)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (rc != hipSuccess) return rc;
-    if (TVR_GEMM_F32 && TVR_GEMM_LDS && TL_ROWS * (Ka + Kb) <= 256 * TL_PF) {          // (a 20 x 1 tile product, e.g. a column sum, has up to 672 columns: old kernel)
+    if (TL_ROWS * (Ka + Kb) <= 256 * TL_PF) {          // (a 20 x 1 tile product, e.g. a column sum, has up to 672 columns: old kernel)
         const int lds2 = 2 * ((TL_ROWS * (Ka + Kb) + 3) & ~3) * (int)sizeof(float);       // <= 40 KB
         // 16-B loads need contiguous rows (a chunk is then one flat run of floats) and 16-B aligned chunk starts (TL_ROWS * K * 4 B is)
         const bool al = ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0;
         const int mode = (al && lda == Ka && ldb == Kb) ? 1 : ((al && !((Ka | Kb | lda | ldb) & 3)) ? 2 : 0);
-        const bool f16 = scale_f16 != nullptr && Ka <= 32 * TG_WAVES && TVR_GEMM_SPLIT16;
+        const bool f16 = scale_f16 != nullptr && Ka <= 32 * TG_WAVES;
         const dim3 g((unsigned)grid), b(64 * TG_WAVES);
 #define TG_GO(MODE_, F16_) hipLaunchKernelGGL((gemm_tn_lds_kernel<MODE_, F16_>), g, b, lds2, stream, A, lda, Ka, B, ldb, Kb, M, scratch, rpb, m_dev, ones, scale_f16)
         if (f16) { if (mode == 1) TG_GO(1, true); else if (mode == 2) TG_GO(2, true); else TG_GO(0, true); }
         else { if (mode == 1) TG_GO(1, false); else if (mode == 2) TG_GO(2, false); else TG_GO(0, false); }
 #undef TG_GO
         if (!f16) scale_f16 = nullptr;
-    } else if (TVR_GEMM_F32) {
-        scale_f16 = nullptr;                                        // (the direct-load kernels keep the fp32 products)
-        hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)grid), dim3(64 * TG_WAVES), lds, stream, A, lda, Ka, B, ldb, Kb, M, scratch, rpb, m_dev);
     } else {
-        scale_f16 = nullptr;
-        rc = hipFuncSetAttribute((const void *)gemm_tn_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (rc != hipSuccess) return rc;
-        hipLaunchKernelGGL(gemm_tn_f16_kernel, dim3((unsigned)grid), dim3(64 * TG_WAVES), lds, stream, A, lda, Ka, B, ldb, Kb, M, scratch, rpb, m_dev);
+        scale_f16 = nullptr;                                        // (the direct-load kernel keeps the fp32 products)
+        hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)grid), dim3(64 * TG_WAVES), lds, stream, A, lda, Ka, B, ldb, Kb, M, scratch, rpb, m_dev);
     }
     const int n = Ka * (Kb + ones);
     if (ones) hipLaunchKernelGGL(gemm_tn_reduce_bias_kernel, dim3((n * 16 + 255) / 256), dim3(256), 0, stream, scratch, (int)grid, Ka, Kb, C, bias_out, scale_f16);

@@ -6,8 +6,8 @@
 //   models/tensoRF.py:209-225 compute_densityfeature, tensorBase.py:444-448 feature2density,
 //   :17-24 raw2alpha, :513 app_mask, :520 acc_map, :530-531 depth_map.
 //
-// Launch shape: persistent workgroups, one per CU (up to 16 waves), each owning every (gridDim)-th 16-ray tile of its XCD's contiguous
-// tile range; the waves of a group take rays from an LDS cursor, so the 16 rays of a tile are marched concurrently (shared texels
+// Launch shape: persistent workgroups, one per CU (up to 16 waves), each taking 16-ray tiles in order from one global counter;
+// the waves of a group take rays from an LDS cursor, so the 16 rays of a tile are marched concurrently (shared texels
 // in L1) and no wave idles while the group has rays left.  The three density LINES (3 x (L+1) x 64 B, 58 KB at 300^3) are copied
 // into LDS once per group: a third of the gather's 64-B requests then go to LDS instead of the L1/TA path that bounds this kernel.
 //
@@ -24,9 +24,6 @@
 #include "tvr_device.h"
 #include "tvr_kernels.h"
 
-#ifndef TVR_MARCH_RASTER
-#define TVR_MARCH_RASTER 1      // 1: every group sweeps the image together (tile k*grid + group) -> the queue is in ~raster order; measured march 7.9 vs 8.8 ms and shade 15.25 vs 15.65 ms against per-XCD contiguous bands (0)
-#endif
 // Small launches (a 4096-ray training batch or render chunk, a rank's share of a split frame: 16 rays per CU, one per wave) — measured in round 3
 // (scripts/march_timeline.py, profiles/r03_march_timeline.txt): a wave's chain takes 10.4 us per 64-sample chunk at 4096 rays, 8.3 at 16 384,
 // 7.2 in the full frame; the kernel ends 80 us after it starts where its share of a full frame is 49 us.  Tried and dropped: staggering the
@@ -44,62 +41,25 @@
 #define MARCH_TAIL 4u                     // rays per handout at the end of a launch (16u = off)
 #endif
 #define MARCH_HDR 560                     // LDS header: ray cursor (16 B) + 64 slots of {local tile number + 1 | tail bit, first ray} (dynamic queue) + 3 u64 statistics sums + pad
-#ifndef TVR_MARCH_DYN
-#define TVR_MARCH_DYN 1                   // 1: workgroups take 16-ray tiles from ONE global counter (in order), not a fixed stride: no tail when a launch has few tiles per group
-#endif
 #ifndef MARCH_LSTRIDE
 #define MARCH_LSTRIDE 4                   // float4 per line texel in LDS.  4 = packed; 5 (80 B: the texels of 16 consecutive cells in distinct banks) removes
 #endif                                    // the line taps' bank conflicts (34 % of the LDS-active cycles) and measures SLOWER: 8.2 vs 8.0 ms — the kernel sits on the L1 path
-
-// quad-level data movement as DPP VALU ops (quad_perm) instead of ds_bpermute: no LDS hop in front of the gather addresses
-template <int CTRL>
-__device__ __forceinline__ int quad_perm_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-template <int CTRL>
-__device__ __forceinline__ float quad_perm_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
-// broadcast lane k of each quad (quad_perm:[k,k,k,k]); k is a constant after unrolling, the switch folds away
-__device__ __forceinline__ int quad_bcast_i(int v, int k)
-{
-    switch (k) {
-    case 0: return quad_perm_i<0x00>(v);
-    case 1: return quad_perm_i<0x55>(v);
-    case 2: return quad_perm_i<0xAA>(v);
-    default: return quad_perm_i<0xFF>(v);
-    }
-}
-__device__ __forceinline__ float quad_bcast_f(float v, int k) { return __int_as_float(quad_bcast_i(__float_as_int(v), k)); }
-#define QUAD_XOR1 0xB1                    // quad_perm:[1,0,3,2]
-#define QUAD_XOR2 0x4E                    // quad_perm:[2,3,0,1]
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // vm_term<4, false> with the line taps taken from the LDS copy (same arithmetic, same order).
 // Round 5: the plane taps are addressed as wave-uniform base + 32-BIT byte offset (global_load ... v_off, s[base] offset:imm): the 64-bit per-lane address
 // arithmetic this replaced (v_mad_i64_i32, v_lshlrev_b64, 2 x v_lshl_add_u64 per plane and sub-step: multi-pass instructions) was a tenth of the kernel's VALU
 // issue time.  A density plane of the largest grid the ABI admits (4097^2 texels x 64 B) is 1.07 GB: the offsets fit 32 bits.
-#ifndef MARCH_ADDR32
-#define MARCH_ADDR32 1
-#endif
 __device__ __forceinline__ float4 vm_term_lds(const float4 *__restrict__ P, const float4 *Ls, int W, int x0, int y0, int l0,
                                               float wx, float wy, float wl, int sub)
 {
     const float ux = 1.0f - wx, uy = 1.0f - wy, ul = 1.0f - wl;
     const int Wp = W + 1;
-#if MARCH_ADDR32
     const unsigned cell = __umul24((unsigned)y0, (unsigned)Wp) + (unsigned)x0;            // both factors below 2^24 (grid <= 4096)
     unsigned o0 = (cell << 6) + ((unsigned)sub << 4), o1 = o0 + ((unsigned)Wp << 6);
     asm volatile("" : "+v"(o0), "+v"(o1));                                                // opaque: hipcc otherwise widens the sums back into 64-bit arithmetic
     const unsigned char *pb = (const unsigned char *)P;
     const float4 t00 = *(const float4 *)(pb + (size_t)o0), t01 = *(const float4 *)(pb + (size_t)o0 + 64);
     const float4 t10 = *(const float4 *)(pb + (size_t)o1), t11 = *(const float4 *)(pb + (size_t)o1 + 64);
-#else
-    const float4 *p = P + ((size_t)y0 * Wp + x0) * 4 + sub;
-    const float4 t00 = p[0], t01 = p[4], t10 = p[(size_t)Wp * 4], t11 = p[(size_t)Wp * 4 + 4];
-#endif
     const float4 *q = Ls + l0 * MARCH_LSTRIDE + sub;
     const float4 l0v = q[0], l1v = q[MARCH_LSTRIDE];
     float4 p4 = f4_mul(ux * uy, t00);
@@ -111,71 +71,9 @@ __device__ __forceinline__ float4 vm_term_lds(const float4 *__restrict__ P, cons
     return make_float4(p4.x * q4.x, p4.y * q4.y, p4.z * q4.z, p4.w * q4.w);
 }
 
-// Round 5: the same term with everything that depends on the SAMPLE alone — the four bilinear weights, the two line weights, the texel byte offset, the LDS
-// offset of the line texel — computed once per chunk by the lane that owns the sample (W4, WL, off, loff) and taken from it here by quad_perm DPP
-// (quad_bcast_*(x, k4)): written as one broadcast per use so that hipcc's DPP combine folds it into the consuming v_mul_f32 / v_fmac_f32 / v_add_u32 (VOP2 with a
-// DPP source: no v_mov_b32_dpp, no instruction at all).  Per sub-step that removes 6 broadcasts, 3 (1 - w), 12 weight products and the cell arithmetic of three
-// planes: 182 -> ~150 instructions.  Same products, same order of the FMAs: bit-identical sigma features.
-// MEASURED AND NOT ENABLED (profiles/r05_shade16_ab.txt, blocks r5r / r5s): -93 VALU instructions per chunk (-8 %), frames bit-identical (sha256), and the kernel
-// 1.8 % SLOWER in both forms (7.86 - 7.97 against 7.71 - 7.83 ms, interleaved on two boxes) — the march is bound by its 48 wave-level loads per chunk on the L1 path
-// (r05_ta_mask_probe.txt), not by its VALU count, and the 18 extra live registers per lane cost more than the instructions saved.  Kept as a build option.
-#ifndef MARCH_PRECOMP
-#define MARCH_PRECOMP 0
-#endif
-#ifndef MARCH_DPP_ASM
-#define MARCH_DPP_ASM 1       // 1: the weight operand of every interpolation op is read through quad_perm DPP by the op itself (v_mul_f32_dpp / v_fmac_f32_dpp as inline asm:
-#endif                        // hipcc's DPP combine folds a broadcast into v_mul_f32 only, and only in src0 position — 15 v_mov_b32_dpp per sub-step stayed); 0: builtins
-// r = w[quad lane K] * t   /   acc += w[quad lane K] * t   (VOP2 with a DPP source; the asm is not volatile: a pure function of its operands, free to be scheduled)
-template <int K>
-__device__ __forceinline__ float mul_q(float w, float t)
-{
-#if MARCH_DPP_ASM
-    float r;
-    asm("v_mul_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(w), "v"(t), "n"(K));
-    return r;
-#else
-    return quad_bcast_f(w, K) * t;
-#endif
-}
-template <int K>
-__device__ __forceinline__ float fma_q(float w, float t, float acc)
-{
-#if MARCH_DPP_ASM
-    asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(acc) : "v"(w), "v"(t), "n"(K));
-    return acc;
-#else
-    return __builtin_fmaf(quad_bcast_f(w, K), t, acc);
-#endif
-}
-template <int K>
-__device__ __forceinline__ float4 vm_term_pre(const float4 *__restrict__ P, const unsigned char *Lbytes, unsigned Wp64, const float W4[4], const float WL[2], unsigned off,
-                                              unsigned loff, unsigned sub16)
-{
-    const unsigned o0 = quad_bcast_i((int)off, K) + sub16, o1 = o0 + Wp64;
-    const unsigned char *pb = (const unsigned char *)P;
-    const float4 t00 = *(const float4 *)(pb + (size_t)o0), t01 = *(const float4 *)(pb + (size_t)o0 + 64);
-    const float4 t10 = *(const float4 *)(pb + (size_t)o1), t11 = *(const float4 *)(pb + (size_t)o1 + 64);
-    const unsigned lo = quad_bcast_i((int)loff, K) + sub16;
-    const float4 l0v = *(const float4 *)(Lbytes + lo), l1v = *(const float4 *)(Lbytes + lo + 16 * MARCH_LSTRIDE);
-    float4 p4, q4;
-    p4.x = mul_q<K>(W4[0], t00.x); p4.y = mul_q<K>(W4[0], t00.y); p4.z = mul_q<K>(W4[0], t00.z); p4.w = mul_q<K>(W4[0], t00.w);
-    p4.x = fma_q<K>(W4[1], t01.x, p4.x); p4.y = fma_q<K>(W4[1], t01.y, p4.y); p4.z = fma_q<K>(W4[1], t01.z, p4.z); p4.w = fma_q<K>(W4[1], t01.w, p4.w);
-    p4.x = fma_q<K>(W4[2], t10.x, p4.x); p4.y = fma_q<K>(W4[2], t10.y, p4.y); p4.z = fma_q<K>(W4[2], t10.z, p4.z); p4.w = fma_q<K>(W4[2], t10.w, p4.w);
-    p4.x = fma_q<K>(W4[3], t11.x, p4.x); p4.y = fma_q<K>(W4[3], t11.y, p4.y); p4.z = fma_q<K>(W4[3], t11.z, p4.z); p4.w = fma_q<K>(W4[3], t11.w, p4.w);
-    q4.x = mul_q<K>(WL[0], l0v.x); q4.y = mul_q<K>(WL[0], l0v.y); q4.z = mul_q<K>(WL[0], l0v.z); q4.w = mul_q<K>(WL[0], l0v.w);
-    q4.x = fma_q<K>(WL[1], l1v.x, q4.x); q4.y = fma_q<K>(WL[1], l1v.y, q4.y); q4.z = fma_q<K>(WL[1], l1v.z, q4.z); q4.w = fma_q<K>(WL[1], l1v.w, q4.w);
-    return make_float4(p4.x * q4.x, p4.y * q4.y, p4.z * q4.z, p4.w * q4.w);
-}
-// the three planes of one sub-step (K a constant after unrolling)
-template <int K>
-__device__ __forceinline__ float vm_sum_pre(const SceneDev &sc, const unsigned char *l0, const unsigned char *l1, const unsigned char *l2, const float Wq[3][4], const float Wl[3][2],
-                                            const unsigned offp[3], const unsigned offl[3], unsigned sub16)
-{
-    const float4 a = vm_term_pre<K>(sc.dplane[0], l0, ((unsigned)sc.grid[0] + 1u) << 6, Wq[0], Wl[0], offp[0], offl[0], sub16);
-    const float4 b = vm_term_pre<K>(sc.dplane[1], l1, ((unsigned)sc.grid[0] + 1u) << 6, Wq[1], Wl[1], offp[1], offl[1], sub16);
-    const float4 cc = vm_term_pre<K>(sc.dplane[2], l2, ((unsigned)sc.grid[1] + 1u) << 6, Wq[2], Wl[2], offp[2], offl[2], sub16);
-    return ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((cc.x + cc.y) + (cc.z + cc.w));
-}
+// (Round 5 also computed everything that depends on the sample alone once per chunk and read it through quad_perm DPP operands: -8 % VALU instructions, bit-identical,
+// 1.8 % slower — DESIGN.md 4.1.  Its interpolation ops were v_mul_f32_dpp / v_fmac_f32_dpp as inline asm: hipcc's DPP combine folds a broadcast into v_mul_f32 only, and
+// only in src0 position — 15 v_mov_b32_dpp per sub-step stayed with the builtins.)
 
 template <bool DENSE, bool LDSL>
 __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const SceneDev sc, const float *__restrict__ rays,
@@ -218,15 +116,8 @@ __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const Scene
     unsigned long long clk0 = 0ull, ref0 = 0ull;
     if (mo.stats && threadIdx.x == 0) { clk0 = __builtin_amdgcn_s_memtime(); ref0 = __builtin_amdgcn_s_memrealtime(); }
 
-    // this group's tiles: XCD x (groups x, x+8, ...: observed round-robin dispatch) owns a contiguous tile range; speed only
-    const int n_tiles = (n_rays + MARCH_TILE - 1) / MARCH_TILE;
-    (void)n_tiles;
-#if !TVR_MARCH_RASTER
-    const int nx = gridDim.x < 8u ? (int)gridDim.x : 8;
-    const int xcd = blockIdx.x % nx, bi = blockIdx.x / nx, nbx = ((int)gridDim.x - xcd + nx - 1) / nx;
-    const int t0 = (int)((long long)n_tiles * xcd / nx), t1 = (int)((long long)n_tiles * (xcd + 1) / nx);
-#endif
-
+    // Tiles are taken in order from ONE global counter, so the groups sweep the image together and the queue is in ~raster order (measured: march 7.9 vs 8.8 ms and
+    // shade 15.25 vs 15.65 ms against per-XCD contiguous bands), and a launch with few tiles per group has no tail.
     unsigned long long st_eval = 0, st_bbox = 0, st_term = 0;
     int last_start = 0;                                  // first ray of this wave's previous handout (dynamic queue: picks the tail granularity)
 
@@ -234,7 +125,6 @@ __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const Scene
         unsigned ci = 0;
         if (lane == 0) ci = atomicAdd(cursor, 1u);
         ci = __builtin_amdgcn_readfirstlane(ci);
-#if TVR_MARCH_DYN
         // the wave that draws the first ray of local tile k takes the next global tile and publishes it {k + 1, tile} in slot k & (MARCH_SLOTS - 1); the others
         // wait for the slot's generation to become k + 1.  Why the wait ends: the publisher stores right behind its draw (one global atomic,
         // ~2 us), and the slot is only overwritten by the publisher of local tile k + 64, which needs the group's cursor to advance by 1024 draws
@@ -293,17 +183,6 @@ __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const Scene
         last_start = ray_start;
         const int ray = ray_start + (int)(ci % MARCH_TILE);
         if (ray >= n_rays) continue;
-#elif TVR_MARCH_RASTER
-        const int tile = (int)(ci / MARCH_TILE) * (int)gridDim.x + (int)blockIdx.x;     // all groups sweep the image together
-        if (tile >= n_tiles) break;
-        const int ray = tile * MARCH_TILE + (int)(ci % MARCH_TILE);
-        if (ray >= n_rays) continue;
-#else
-        const int tile = t0 + (int)(ci / MARCH_TILE) * nbx + bi;
-        if (tile >= t1) break;
-        const int ray = tile * MARCH_TILE + (int)(ci % MARCH_TILE);
-        if (ray >= n_rays) continue;
-#endif
         float o[3], d[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -384,44 +263,10 @@ __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const Scene
 
             // ---- density feature: 4 sub-steps, quad-per-sample gather ----
             float sf = 0.0f;
-#if MARCH_PRECOMP
-            // what the sub-steps need of this lane's sample, once per chunk (vm_term_pre): plane p's weights in vm_term_lds's order for its (a, b | line) axes —
-            // plane 0 (x, y | z), plane 1 (x, z | y), plane 2 (y, z | x) — and the byte offsets of its first texel and of its line texel in LDS
-            float Wq[3][4], Wl[3][2];
-            unsigned offp[3], offl[3];
-            if (LDSL) {
-                const float ux = 1.0f - w[0], uy = 1.0f - w[1], uz = 1.0f - w[2];
-                Wq[0][0] = ux * uy; Wq[0][1] = w[0] * uy; Wq[0][2] = ux * w[1]; Wq[0][3] = w[0] * w[1];
-                Wq[1][0] = ux * uz; Wq[1][1] = w[0] * uz; Wq[1][2] = ux * w[2]; Wq[1][3] = w[0] * w[2];
-                Wq[2][0] = uy * uz; Wq[2][1] = w[1] * uz; Wq[2][2] = uy * w[2]; Wq[2][3] = w[1] * w[2];
-                Wl[0][0] = uz; Wl[0][1] = w[2]; Wl[1][0] = uy; Wl[1][1] = w[1]; Wl[2][0] = ux; Wl[2][1] = w[0];
-                const unsigned Wp0 = (unsigned)sc.grid[0] + 1u, Wp2 = (unsigned)sc.grid[1] + 1u;
-                offp[0] = (__umul24((unsigned)i0[1], Wp0) + (unsigned)i0[0]) << 6;
-                offp[1] = (__umul24((unsigned)i0[2], Wp0) + (unsigned)i0[0]) << 6;
-                offp[2] = (__umul24((unsigned)i0[2], Wp2) + (unsigned)i0[1]) << 6;
-                offl[0] = (unsigned)i0[2] * (16u * MARCH_LSTRIDE); offl[1] = (unsigned)i0[1] * (16u * MARCH_LSTRIDE); offl[2] = (unsigned)i0[0] * (16u * MARCH_LSTRIDE);
-                if (!valid) { offp[0] = offp[1] = offp[2] = 0u; offl[0] = offl[1] = offl[2] = 0u; }       // (samples outside the box: their lanes' offsets are never used, keep them harmless)
-            }
-            const unsigned sub16 = (unsigned)sub << 4;
-#endif
 #pragma unroll
             for (int k4 = 0; k4 < 4; ++k4) {
                 const bool v = quad_bcast_i((int)valid, k4) != 0;
                 if (__ballot(v) == 0ull) continue;
-#if MARCH_PRECOMP
-                if (LDSL) {
-                    float part = 0.0f;
-                    if (v) {
-                        const unsigned char *l0b = (const unsigned char *)ls0, *l1b = (const unsigned char *)ls1, *l2b = (const unsigned char *)ls2;
-                        part = k4 == 0 ? vm_sum_pre<0>(sc, l0b, l1b, l2b, Wq, Wl, offp, offl, sub16) : (k4 == 1 ? vm_sum_pre<1>(sc, l0b, l1b, l2b, Wq, Wl, offp, offl, sub16)
-                             : (k4 == 2 ? vm_sum_pre<2>(sc, l0b, l1b, l2b, Wq, Wl, offp, offl, sub16) : vm_sum_pre<3>(sc, l0b, l1b, l2b, Wq, Wl, offp, offl, sub16)));
-                    }
-                    part += quad_perm_f<QUAD_XOR1>(part);
-                    part += quad_perm_f<QUAD_XOR2>(part);
-                    if (sub == k4) sf = part;
-                    continue;
-                }
-#endif
                 const int ix = quad_bcast_i(i0[0], k4), iy = quad_bcast_i(i0[1], k4), iz = quad_bcast_i(i0[2], k4);
                 const float wx = quad_bcast_f(w[0], k4), wy = quad_bcast_f(w[1], k4), wz = quad_bcast_f(w[2], k4);
                 float part = 0.0f;
@@ -723,9 +568,6 @@ hipError_t launch_march(const SceneDev &sc, const float *rays, int n_rays, int S
     const int n_tiles = (n_rays + MARCH_TILE - 1) / MARCH_TILE;
     // one group per CU when it holds 16 waves; proportionally more groups when the lists force smaller ones
     long long grid = (long long)device_cu_count() * (16 / waves > 0 ? 16 / waves : 1);
-#ifdef TVR_EXP_GRID                                             // scripts/overlap_experiment.py only: a build_variant.sh -DTVR_EXP_GRID library
-    if (const char *g = getenv("TVR_EXP_GRID_MARCH")) { const long long v = atoll(g); if (v > 0 && v < grid) grid = v; }
-#endif
     if (grid > n_tiles) grid = n_tiles;
     if (grid < 1) grid = 1;
     tvr_dense_out none = {};

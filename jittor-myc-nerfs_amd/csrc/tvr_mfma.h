@@ -1,4 +1,4 @@
-// tvr_mfma.h — fp16 hi/lo split MFMA idioms shared by the fused-MLP kernels (tvr_ngp.hip, tvr_bg.hip).
+// tvr_mfma.h — fp16 hi/lo split MFMA idioms shared by the fused-MLP kernels (tvr_shade.hip, tvr_shade16.hip, tvr_mlp_train.hip, tvr_gemm.hip, tvr_ngp.hip, tvr_bg.hip).
 // Arithmetic: v_mfma_f32_32x32x16_f16 with every fp32 operand split into fp16 hi + lo and three products per k-step (hi*lo, lo*hi,
 // hi*hi): error ~2^-22 relative, i.e. fp32-grade.  Operand layout (lane l, col = l%32, h = l/32): A fragment = 8 halves of row col,
 // k = 8h..8h+7 of the step; B fragment = 8 halves of column col, same k; accumulator register i = row (i/4)*8 + 4h + i%4, column col.
@@ -86,4 +86,36 @@ __device__ __forceinline__ Frag frag8(const float v[8])
 {
     if constexpr (AR >= 3) return split8(v);
     else return round8(v);
+}
+
+// The products of one k-step.  AR = how many a k-step takes (tvr_scene_set_arith, tvr_mlpnet_desc.arith; include/tvr.h TVR_ARITH_*): 3 = Wlo*xhi + Whi*xlo + Whi*xhi
+// (fp32-class, the default); 2 = Wlo*xhi + Whi*xhi (weights keep their 22 bits, activations are rounded to fp16); 1 = Whi*xhi (plain fp16 operands).  Always fp32
+// accumulation, always in this order.  What a mode does not multiply need not be loaded (A.l) or derived (b.lo, frag8<AR>).
+// One {hi, lo} A fragment on ONE accumulator, back to back (a dependent chain of 32x32x16 MFMAs issues back to back: profiles/r04_mfma_issue_probe.txt)
+struct AF { uint4 h, l; };
+template <int AR = 3>
+__device__ __forceinline__ void mfma3(const AF &A, const Frag &b, f32x16 &acc)
+{
+    if constexpr (AR >= 2) acc = MFMAH(A.l, b.hi, acc);
+    if constexpr (AR >= 3) acc = MFMAH(A.h, b.lo, acc);
+    acc = MFMAH(A.h, b.hi, acc);
+}
+// The A fragments of NB independent 32-row blocks on NB accumulators: each product interleaved across the blocks (no MFMA directly follows an MFMA it depends on)
+template <int NB>
+struct AFrags {
+    uint4 h[NB], l[NB];
+};
+template <int NB, int AR = 3>
+__device__ __forceinline__ void mma(const AFrags<NB> &a, const Frag &b, f32x16 (&acc)[NB])
+{
+    if constexpr (AR >= 2) {
+#pragma unroll
+        for (int m = 0; m < NB; ++m) acc[m] = MFMAH(a.l[m], b.hi, acc[m]);
+    }
+    if constexpr (AR >= 3) {
+#pragma unroll
+        for (int m = 0; m < NB; ++m) acc[m] = MFMAH(a.h[m], b.lo, acc[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < NB; ++m) acc[m] = MFMAH(a.h[m], b.hi, acc[m]);
 }

@@ -128,27 +128,15 @@ __global__ __launch_bounds__(256) void pack_train_w1gen_kernel(const float *__re
     o[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
 }
 
-struct AFragN { uint4 h[5], l[5]; };
-
+// A fragments of NB 32-row blocks of one k-step from an LDS weight image (tvr_mfma.h: AFrags, mma)
 template <int NB>
-__device__ __forceinline__ void load_afragn(AFragN &A, const unsigned char *WH, const unsigned char *WL, int off0)
+__device__ __forceinline__ void load_afragn(AFrags<NB> &A, const unsigned char *WH, const unsigned char *WL, int off0)
 {
 #pragma unroll
     for (int rb = 0; rb < NB; ++rb) {
         A.h[rb] = *(const uint4 *)(WH + off0 + rb * 32 * TI_ROW);
         A.l[rb] = *(const uint4 *)(WL + off0 + rb * 32 * TI_ROW);
     }
-}
-
-template <int NB>
-__device__ __forceinline__ void mfma3xn(const AFragN &A, const Frag &b, f32x16 acc[NB])
-{
-#pragma unroll
-    for (int rb = 0; rb < NB; ++rb) acc[rb] = MFMAH(A.l[rb], b.hi, acc[rb]);
-#pragma unroll
-    for (int rb = 0; rb < NB; ++rb) acc[rb] = MFMAH(A.h[rb], b.lo, acc[rb]);
-#pragma unroll
-    for (int rb = 0; rb < NB; ++rb) acc[rb] = MFMAH(A.h[rb], b.hi, acc[rb]);
 }
 
 struct MlpBwdArgs {
@@ -261,7 +249,7 @@ __global__ __launch_bounds__(MT_THREADS, MT_WAVES / 4) void mlp_train_backward_k
                 b = split8(x);
             };
             Frag bcur, bnxt;
-            AFragN acur, anxt;
+            AFrags<4> acur, anxt;
             frag(0, bcur);
             load_afragn<4>(acur, smem + TI_W2T_H, smem + TI_W2T_L, rowoff);
 #pragma unroll
@@ -270,7 +258,7 @@ __global__ __launch_bounds__(MT_THREADS, MT_WAVES / 4) void mlp_train_backward_k
                     load_afragn<4>(anxt, smem + TI_W2T_H, smem + TI_W2T_L, rowoff + (s + 1) * 32);
                     frag(s + 1, bnxt);
                 }
-                mfma3xn<4>(acur, bcur, dh1);
+                mma<4>(acur, bcur, dh1);
                 acur = anxt;
                 bcur = bnxt;
                 __builtin_amdgcn_sched_barrier(0);
@@ -391,12 +379,12 @@ __global__ __launch_bounds__(MT_THREADS, MT_WAVES / 4) void mlp_train_backward_k
             // (the ten weight fragments of a step are fetched in the step itself: 144 accumulator registers leave no room for a second set;
             //  the partner wave covers the LDS latency)
             Frag bcur;
-            AFragN acur;
+            AFrags<5> acur;
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
                 load_afragn<5>(acur, smem + TI_W1T_H, smem + TI_W1T_L, rowoff + s * 32);
                 frag(s, bcur);
-                mfma3xn<5>(acur, bcur, dx);
+                mma<5>(acur, bcur, dx);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

@@ -382,15 +382,6 @@ struct GridCfg {
     uint32_t hashed;                      // bit l: level l uses the spatial hash
 };
 
-#ifndef TVR_NGP_DIAG
-#define TVR_NGP_DIAG 0            // timing stand-ins for the leave-parts-out table of profiles/r06_ngp_bound.txt (never shipped)
-#endif
-#ifndef TVR_NGP_DIAG_MASK
-#define TVR_NGP_DIAG_MASK 0xFFFFu
-#endif
-#ifndef TVR_NGP_PAIR              // 1: the x neighbours of a corner pair as one 16-byte load where the table layout allows (encode_level_pair).  Round 5: bit-identical,
-#define TVR_NGP_PAIR 0            // and SLOWER — ngp_render_kernel 15.0 - 15.7 ms against 13.0 (profiles/r05_ngp_pair_loads.txt): off
-#endif
 // grid_index (HashEncode.h:75-93).  With the reference's fixed 2^19 table a level is either dense (res^3 fits: index = x + y*res +
 // z*res^2, which can exceed the table by less than its size because corner coordinates reach res) or hashed (table size a power of
 // two).  to_grid() checks that every level is one of the two, so the generic stride loop and the modulo reduce to this:
@@ -423,64 +414,6 @@ __device__ __forceinline__ float2 encode_level(const float2 *__restrict__ tab, b
         w *= (idx & 4) ? fz : 1 - fz;
         r0 = __builtin_fmaf(w, v[idx].x, r0);
         r1 = __builtin_fmaf(w, v[idx].y, r1);
-    }
-    return make_float2(r0, r1);
-}
-
-// encode_level for the fused kernels, with the two x neighbours of a (y, z) corner pair fetched as ONE 16-byte block wherever the table layout has them side by side:
-// in a dense level always (entries x and x + 1), in a hashed level whenever cx is even (x + 1 = x | 1: the two hashes differ in bit 0 only — the aligned pair idx & ~1).
-// The vector-memory path charges a random gather per lane and line; the 8-byte load of the second neighbour stays in the instruction stream (no branch: the loads of
-// INFLIGHT levels must stay in flight together) but lanes that already hold it aim it past the end of the buffer, where the hardware returns zero without a fetch.
-// `rs`: the whole table as a raw buffer; `o0`: the level's first entry.  Same entries, same blend order as encode_level: bit-identical features.
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float2 encode_level_pair(__amdgpu_buffer_rsrc_t rs, uint32_t o0, bool hashed, uint32_t size, float scale, float px, float py, float pz)
-{
-    const uint32_t res = (uint32_t)ceilf(scale) + 1u;
-    const float x = __builtin_fmaf(px, scale, 0.5f), y = __builtin_fmaf(py, scale, 0.5f), z = __builtin_fmaf(pz, scale, 0.5f);
-    const float fx0 = floorf(x), fy0 = floorf(y), fz0 = floorf(z);
-    const uint32_t cx = (uint32_t)(int)fx0, cy = (uint32_t)(int)fy0, cz = (uint32_t)(int)fz0;
-    const float fx = x - fx0, fy = y - fy0, fz = z - fz0;
-    u32x4 q[4];
-    u32x2 sv[4];
-    bool lo0[4], lo1[4], in1[4];
-    const uint32_t hm = hashed ? 0xFFFFFFFFu : 0u;              // the level's kind as a bit mask: both index forms are computed and blended (v_bfi), no branch on a lane-half-dependent flag
-    const uint32_t res2 = res * res;
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) {
-        const uint32_t yy = cy + (yz & 1), zz = cz + (yz >> 1);
-        const uint32_t hyz = (yy * 19349663u) ^ (zz * 83492791u), dyz = yy * res + zz * res2;
-        const uint32_t d0 = cx + dyz, d1 = d0 + 1u;
-        const uint32_t e0 = min(d0 - (d0 >= size ? size : 0u), size - 1), e1 = min(d1 - (d1 >= size ? size : 0u), size - 1);      // grid_entry's dense form
-        const uint32_t h0 = (cx ^ hyz) & (size - 1), h1 = ((cx + 1u) ^ hyz) & (size - 1);                                          // ... and its hashed form
-        const uint32_t i0 = (h0 & hm) | (e0 & ~hm), i1 = (h1 & hm) | (e1 & ~hm);
-        const uint32_t bd = i0 + 1u < size ? i0 : i0 - 1u;
-        const uint32_t base = ((i0 & ~1u) & hm) | (bd & ~hm);                                 // a 16-byte block inside the level that holds entry i0 (level sizes are even)
-        lo0[yz] = i0 == base;
-        lo1[yz] = i1 == base;
-        in1[yz] = (i1 - base) < 2u;
-        q[yz] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((o0 + base) << 3), 0, 0);
-        sv[yz] = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(in1[yz] ? 0xFFFFFFF8u : ((o0 + i1) << 3)), 0, 0);
-    }
-    float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-    for (int idx = 0; idx < 8; ++idx) {
-        const int yz = idx >> 1;
-        const u32x4 Q = q[yz];
-        float vx, vy;
-        if (idx & 1) {
-            vx = __uint_as_float(in1[yz] ? (lo1[yz] ? Q.x : Q.z) : sv[yz].x);
-            vy = __uint_as_float(in1[yz] ? (lo1[yz] ? Q.y : Q.w) : sv[yz].y);
-        } else {
-            vx = __uint_as_float(lo0[yz] ? Q.x : Q.z);
-            vy = __uint_as_float(lo0[yz] ? Q.y : Q.w);
-        }
-        float w = 1.0f;
-        w *= (idx & 1) ? fx : 1 - fx;
-        w *= (idx & 2) ? fy : 1 - fy;
-        w *= (idx & 4) ? fz : 1 - fz;
-        r0 = __builtin_fmaf(w, vx, r0);
-        r1 = __builtin_fmaf(w, vy, r1);
     }
     return make_float2(r0, r1);
 }
@@ -549,16 +482,13 @@ __global__ void __launch_bounds__(256) ngp_sh_encode_kernel(const float *__restr
 #ifndef TVR_NGP_WAVES             // waves per SIMD the field kernel is compiled for
 #define TVR_NGP_WAVES 2
 #endif
-#ifndef TVR_NGP_XCD               // 1: every XCD (blockIdx % 8) works through its own contiguous eighth of the tiles
-#define TVR_NGP_XCD 0
-#endif
 enum { NGP_L_D0 = 0, NGP_L_D1 = 2 * 16 * 64, NGP_L_C0 = NGP_L_D1 + 32 * 64, NGP_L_C1 = NGP_L_C0 + 2 * 16 * 64, NGP_L_C2 = NGP_L_C1 + 2 * 32 * 64,
        NGP_IMAGE_FLOATS = NGP_L_C2 + 32 * 64 };
 // fp16 image: first block of each layer (blocks are m_block-major, then k-step)
 enum { NGP_H_D0 = 0, NGP_H_D1 = 4, NGP_H_C0 = 8, NGP_H_C1 = 12, NGP_H_C2 = 20, NGP_H_BLOCKS = 24, NGP_HIMAGE_FLOATS = NGP_H_BLOCKS * 2 * 64 * 4 };
 static_assert(NGP_HIMAGE_FLOATS == NGP_IMAGE_FLOATS, "both images are 48 KiB");
 
-
+// tvr_device.h's acc_row(i, 0), kept in this form: with the shared one (shifts and masks on a signed int) ngp_pack_f32_kernel compiles to other instructions
 __device__ __forceinline__ int acc_row(int i) { return (i / 4) * 8 + i % 4; }
 
 __global__ void __launch_bounds__(256) ngp_pack_f32_kernel(const float *__restrict__ d0, const float *__restrict__ d1, const float *__restrict__ c0, const float *__restrict__ c1,
@@ -618,20 +548,17 @@ __global__ void __launch_bounds__(256) ngp_pack_f16_kernel(const float *__restri
 // the one it depends on
 __device__ __forceinline__ void step2(const uint4 *__restrict__ w4, int blk0, int blk1, const Frag &b, f32x16 &a0, f32x16 &a1)
 {
-    const uint4 h0 = w4[(blk0 * 2 + 0) * 64], l0 = w4[(blk0 * 2 + 1) * 64], h1 = w4[(blk1 * 2 + 0) * 64], l1 = w4[(blk1 * 2 + 1) * 64];
-    a0 = MFMAH(l0, b.hi, a0);
-    a1 = MFMAH(l1, b.hi, a1);
-    a0 = MFMAH(h0, b.lo, a0);
-    a1 = MFMAH(h1, b.lo, a1);
-    a0 = MFMAH(h0, b.hi, a0);
-    a1 = MFMAH(h1, b.hi, a1);
+    AFrags<2> A;
+    A.h[0] = w4[(blk0 * 2 + 0) * 64]; A.l[0] = w4[(blk0 * 2 + 1) * 64]; A.h[1] = w4[(blk1 * 2 + 0) * 64]; A.l[1] = w4[(blk1 * 2 + 1) * 64];
+    f32x16 acc[2] = {a0, a1};
+    mma<2>(A, b, acc);
+    a0 = acc[0];
+    a1 = acc[1];
 }
 __device__ __forceinline__ void step1(const uint4 *__restrict__ w4, int blk, const Frag &b, f32x16 &a)
 {
-    const uint4 h0 = w4[(blk * 2 + 0) * 64], l0 = w4[(blk * 2 + 1) * 64];
-    a = MFMAH(l0, b.hi, a);
-    a = MFMAH(h0, b.lo, a);
-    a = MFMAH(h0, b.hi, a);
+    const AF A = {w4[(blk * 2 + 0) * 64], w4[(blk * 2 + 1) * 64]};
+    mfma3(A, b, a);
 }
 // B fragment of k-step t (0..3) of a 64-wide activation held in two accumulators
 __device__ __forceinline__ Frag relu_frag(const f32x16 &a0, const f32x16 &a1, int t)
@@ -649,9 +576,6 @@ __device__ __forceinline__ float4 field_tile(const GridCfg &g, const float2 *__r
                                              float dx, float dy, float dz)
 {
     // ---- GATHER phase: lane half hh takes the hash levels of parity hh (8 levels x 8 corners)
-#if TVR_NGP_PAIR
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)tab, 0, (int)(g.offsets[TVR_NGP_LEVELS] << 3), 0x00020000);
-#endif
     float f0[8], f1[8], shv[8];
     {
         float sh[16];
@@ -665,29 +589,11 @@ __device__ __forceinline__ float4 field_tile(const GridCfg &g, const float2 *__r
         const uint32_t o1 = hh ? g.offsets[2 * p + 2] : g.offsets[2 * p + 1];
         const float sc = hh ? g.scale[2 * p + 1] : g.scale[2 * p];
         const bool hashed = (g.hashed >> (2 * p + hh)) & 1u;
-#if TVR_NGP_DIAG == 1 || TVR_NGP_DIAG == 3        // timing stand-ins (WRONG pictures): 1 = no table gather at all, 3 = only the levels with (mask >> level) & 1 gathered
-        float2 r = make_float2(px * sc, py * sc);
-        if (TVR_NGP_DIAG == 3 && ((TVR_NGP_DIAG_MASK >> (2 * p)) & 3u)) {
-            const bool mine = (TVR_NGP_DIAG_MASK >> (2 * p + hh)) & 1u;
-            if (mine) r = encode_level(tab + o0, hashed, o1 - o0, sc, px, py, pz);
-        }
-#elif TVR_NGP_PAIR
-        const float2 r = encode_level_pair(rs, o0, hashed, o1 - o0, sc, px, py, pz);
-#else
         const float2 r = encode_level(tab + o0, hashed, o1 - o0, sc, px, py, pz);
-#endif
         f0[p] = r.x;
         f1[p] = r.y;
         if ((p + 1) % TVR_NGP_INFLIGHT == 0) __builtin_amdgcn_sched_barrier(0);      // bounds the loads in flight (registers)
     }
-#if TVR_NGP_DIAG == 2                              // timing stand-in (WRONG pictures): the gather alone, no network
-    {
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int p = 0; p < 8; ++p) { s0 += f0[p]; s1 += f1[p]; }
-        return make_float4(s0, s1, s0 - s1, -4.0f + 1e-3f * (s0 + s1 + shv[0]));
-    }
-#endif
     // ---- MATRIX phase
     float density_raw;
     f32x16 e = {0};
@@ -775,13 +681,7 @@ __global__ void __launch_bounds__(256, TVR_NGP_WAVES) ngp_field_kernel(GridCfg g
     const long long n_tiles = (n + 31) / 32;
     const float2 *__restrict__ tab = reinterpret_cast<const float2 *>(grid);
 
-#if TVR_NGP_XCD
-    // blocks are dealt round-robin to the 8 XCDs: XCD x = blockIdx % 8 walks tiles [x*T/8, (x+1)*T/8) so that neighbouring rays share an L2
-    const long long per_xcd = (n_tiles + 7) / 8, xcd = blockIdx.x & 7, t_end = min(n_tiles, (xcd + 1) * per_xcd);
-    for (long long tile = xcd * per_xcd + (long long)(blockIdx.x >> 3) * 4 + wave; tile < t_end; tile += (long long)(gridDim.x >> 3) * 4) {
-#else
     for (long long tile = (long long)blockIdx.x * 4 + wave; tile < n_tiles; tile += (long long)gridDim.x * 4) {
-#endif
         int hh = h, lane_off = lane;
         asm volatile("" : "+v"(hh), "+v"(lane_off));                // opaque per tile: nothing below may be hoisted out of the loop (registers)
         const long long sidx = tile * 32 + col;
@@ -818,12 +718,7 @@ __global__ void __launch_bounds__(256, TVR_NGP_WAVES) ngp_render_kernel(MarchCfg
         if (lane == 0) ticket = atomicAdd(queue, 1ull);
         const long long first = (long long)__shfl(ticket, 0, 64) * 64;
         if (first >= n_rays) break;
-#ifdef TVR_NGP_TILE_W                 // experiment: a ticket is an 8x8 pixel tile of a TVR_NGP_TILE_W-wide image instead of 64 consecutive rays
-        const long long tk = first / 64, tpr = TVR_NGP_TILE_W / 8;
-        const long long mine = ((tk / tpr) * 8 + (lane >> 3)) * TVR_NGP_TILE_W + (tk % tpr) * 8 + (lane & 7);
-#else
         const long long mine = first + lane;
-#endif
         const uint32_t my_n = mine < n_rays ? counts[mine] : 0u;
         if (mine < n_rays && my_n == 0) {
             rgb[3 * mine] = bg0;
@@ -1098,7 +993,6 @@ int tvr_ngp_network(const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const vo
         return tvr_set_error(TVR_ERR_INVALID, "tvr_ngp_network: NULL or misaligned argument");
     const long long tiles = (n_max + 31) / 32;
     unsigned blocks = (unsigned)(tiles < 4 * 2048 ? (tiles + 3) / 4 : 2048);
-    if (TVR_NGP_XCD) blocks = (blocks + 7) / 8 * 8;
     const bool f16 = !TVR_NGP_MLP_F32;
     hipLaunchKernelGGL(f16 ? ngp_field_kernel<true> : ngp_field_kernel<false>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), g,
                        static_cast<const float *>(grid), static_cast<const float *>(net_packed) + (f16 ? NGP_IMAGE_FLOATS : 0), static_cast<const float *>(positions),

@@ -9,7 +9,7 @@
 //   GATHER phase (global loads + VALU + LDS, no MFMA)
 //     gather   the queue entry arrives one tile ahead; lane (e, h) fetches 8 channels (2 x float4) of each tap of entry e per k-step; the
 //              interpolated plane*line products ARE the B fragments of the basis product (9 k-steps, kept as fp16 hi/lo in 72 registers);
-//              the phase ends with s_waitcnt vmcnt(0), then the wave takes its SIMD's matrix token (see TVR_MTOKEN)
+//              the phase ends with s_waitcnt vmcnt(0), then the wave takes its SIMD's matrix token (TVR_ENTER_MATRIX)
 //   MATRIX phase (MFMA + LDS + VALU, no global load)
 //     basis    F^T[32 x 32e]   = Bas[32 x 144] · h^T          A (basis) fragments: hi parts in LDS, lo parts fetched at the end of the gather phase
 //     L1       H^T[128 x 32e]  = W1[128 x 160] · X^T          A (weights) from LDS (resident for the workgroup's lifetime); the B
@@ -72,14 +72,11 @@
 #define TVR_STAMP(x)
 #endif
 #ifndef TVR_TICKET
-#define TVR_TICKET 4      // tiles per ticket of the render path's dynamic tile hand-out (0: static stride)
+#define TVR_TICKET 4      // tiles per ticket of the render path's dynamic tile hand-out
 #endif
 #ifndef TVR_TICKET_MIN
 #define TVR_TICKET_MIN 256  // tiles per wave from which the tickets are used
 #endif
-#ifndef TVR_PHASE_FREE
-#define TVR_PHASE_FREE 0  // experiment (round 5): 1 = the render kernel fetches the NEXT tile's k-step-0 taps (12 global loads per lane) between layer 1 and
-#endif                    // layer 2 of the current tile, i.e. INSIDE the matrix phase — the build that settles whether the phase rule protects anything (scripts/phase_rule_test.sh)
 #ifndef SH_WAVES
 #define SH_WAVES 8        // two waves per SIMD
 #endif
@@ -97,29 +94,6 @@
 #define TVR_PRIO_M 2      // matrix 2 / gather 0 takes 12.17 ms against 12.48 for 0 / 2 (gpurun_out/r4d, two interleaved rounds; 2 / 1: 12.28, 3 / 0: 12.18;
 #endif                    // round 3's schedule at 2 / 0: 12.81 against its own 12.62 at 0 / 2).
 
-// A fragments (hi, lo) of the four 32-row blocks of one k-step, from the LDS weight image
-struct AFrag4 { uint4 h[4], l[4]; };
-
-__device__ __forceinline__ void load_afrag4(AFrag4 &A, const unsigned char *WH, const unsigned char *WL, int off0, int rb_stride)
-{
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb) {
-        A.h[rb] = *(const uint4 *)(WH + off0 + rb * rb_stride);
-        A.l[rb] = *(const uint4 *)(WL + off0 + rb * rb_stride);
-    }
-}
-
-// one k-step of a 128-row layer: the three hi/lo products interleaved across the row blocks (no MFMA directly follows an MFMA it depends on)
-__device__ __forceinline__ void mfma3x4(const AFrag4 &A, const Frag &b, f32x16 acc[4])
-{
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, A.l[rb]), __builtin_bit_cast(h8, b.hi), acc[rb], 0, 0, 0);
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, A.h[rb]), __builtin_bit_cast(h8, b.lo), acc[rb], 0, 0, 0);
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, A.h[rb]), __builtin_bit_cast(h8, b.hi), acc[rb], 0, 0, 0);
-}
-
 // ---- round 4: the matrix phase as an explicit software pipeline (round 4) ------------------------------------------------------------
 // hipcc's own schedule of the hidden layers (round 3; scripts/isa_trace.py shows it) issued a k-step's A-fragment reads right in front of the MFMAs that
 // consume them (ds_read x4, s_waitcnt, MFMA: 70 exposed LDS round trips per tile) and clumped MFMAs (8 back to back) apart from the VALU work of the next
@@ -135,43 +109,22 @@ __device__ __forceinline__ void mfma3x4(const AFrag4 &A, const Frag &b, f32x16 a
 //     instructions being the NEXT k-step's B fragment (positional encoding / relu + fp16 split); the windows that carry a read carry fewer of them;
 //   * the fp16 split's v_fma_mix_f32 is the compiler's own instruction now (tvr_mfma.h), so that the scheduler can classify it;
 //   * layer 1's last k-step carries layer 2's prologue, the basis product is one accumulation chain with its A fragments two k-steps ahead.
-// Per accumulator the order of the additions in the hidden layers is the one mfma3x4 has: their results are bit-identical to round 3's.
+// Per accumulator the order of the additions in the hidden layers is the one tvr_mfma.h's mma has: their results are bit-identical to round 3's.
 // What it bought, honestly (profiles/r04_shade_schedule_ab.txt, interleaved rounds on one box each): the token is held 9.4 k cycles instead of 10.9 k, the tile
 // takes 23.0 k cycles per wave instead of 24.8 k, the kernel 12.2 - 12.6 ms instead of 12.6 - 13.0 (-3 %): with two in-order waves per SIMD the gather phase, the
 // token wait and layer 3 are on the same critical chain as the matrix phase, and a lone wave's hidden layers run at 39 cycles per MFMA whatever the order of their
 // instructions (32.5 without the fragment derivation, 32.1 without the fragment reads, 38.8 with both: gpurun_out/r4f) — issue-bound, not pipe-bound.
-#ifndef TVR_DIAG
-#define TVR_DIAG 0        // diagnostic builds only (wrong pictures): 1 = no fragment derivation in the hidden layers, 2 = no A-fragment reads in layer 1, 4 = layer 1 reads k-step 0's fragments in every k-step (the same LDS traffic, constant operands)
-#endif
 #define TVR_NV1 3         // VALU (+ transcendental) instructions behind each MFMA of layer 1's last k-step (layer 2's first fragment)
-// The three MFMA windows of a row block: TVR_PIPE 1 puts one fragment read in each of the first two windows and V0 / V1 / V2 VALU instructions behind the three
-// MFMAs (layer 1: 1 / 3 / 5, layer 2: 0 / 2 / 4; 2 / 3 / 4 and 1 / 4 / 4 measured 5 % slower, 0 / 3 / 6 and 0 / 4 / 5 equal); TVR_PIPE 0: both reads in front of
-// the row block and 3 / 3 / 3 (2 / 2 / 2): 3 % slower.
+// The three MFMA windows of a row block (TVR_PIPE_RB) carry one fragment read in each of the first two windows and V0 / V1 / V2 VALU instructions behind the three
+// MFMAs (layer 1: 1 / 3 / 5, layer 2: 0 / 2 / 4; 2 / 3 / 4 and 1 / 4 / 4 measured 5 % slower, 0 / 3 / 6 and 0 / 4 / 5 equal; both reads in front of
+// the row block and 3 / 3 / 3 (2 / 2 / 2): 3 % slower).
 // Round 4, second step: layer 2 runs ROW BLOCK BY ROW BLOCK over eight pre-split fragments of relu(layer 1) (the 64 registers the layer-1 accumulators
 // leave), and layer 3 of row block rb - 1 — 16 relu, 48 FMA, 12 weight reads — runs under the MFMAs of row block rb: only the last row block's share of layer 3 is
 // left behind the token hand-over.  Layer 3 was 3.0 k cycles of every wave's chain (gather -> token -> matrix -> layer 3) with nothing beside it.
-#ifndef TVR_PIPE
-#define TVR_PIPE 1
-#endif
 #ifndef TVR_PD
 #define TVR_PD 2          // A fragments are read this many row blocks ahead of their MFMAs, into a ring of TVR_PD + 2 {hi, lo} pairs
 #endif
 #define TVR_RN (TVR_PD + 2)
-#if TVR_PIPE == 0
-#define TVR_L1_V0 3
-#define TVR_L1_V1 3
-#define TVR_L1_V2 3
-#define TVR_L2_V0 2
-#define TVR_L2_V1 2
-#define TVR_L2_V2 2
-#define TVR_PIPE_RB(has_read, v0, v1, v2)                                                              \
-    do {                                                                                               \
-        if (has_read) TVR_SG_DSR(2);                                                                   \
-        TVR_SG_MFMA(1); if (v0) TVR_SG_VALU(v0);                                                       \
-        TVR_SG_MFMA(1); if (v1) TVR_SG_VALU(v1);                                                       \
-        TVR_SG_MFMA(1); if (v2) TVR_SG_VALU(v2);                                                       \
-    } while (0)
-#else
 #ifndef TVR_L1_V0
 #define TVR_L1_V0 1
 #define TVR_L1_V1 3
@@ -190,7 +143,6 @@ __device__ __forceinline__ void mfma3x4(const AFrag4 &A, const Frag &b, f32x16 a
         TVR_SG_MFMA(1); if (v1) TVR_SG_VALU(v1);                                                       \
         TVR_SG_MFMA(1); if (v2) TVR_SG_VALU(v2);                                                       \
     } while (0)
-#endif
 #ifndef TVR_L1A2_V0
 #define TVR_L1A2_V0 2     // layer-1 windows of the two-product arithmetic (two MFMAs per row block) ...
 #define TVR_L1A2_V1 4
@@ -211,45 +163,15 @@ __device__ __forceinline__ void mfma3x4(const AFrag4 &A, const Frag &b, f32x16 a
         if (has_read) TVR_SG_DSR(1);                                                                   \
         TVR_SG_MFMA(1); if (v0) TVR_SG_VALU(v0);                                                       \
     } while (0)
-#if TVR_DIAG & 16
-#define TVR_SG_MFMA(n) __builtin_amdgcn_sched_group_barrier(0x008, 2 * (n), 0)
-#else
 #define TVR_SG_MFMA(n) __builtin_amdgcn_sched_group_barrier(0x008, (n), 0)
-#endif
 #define TVR_SG_VALU(n) __builtin_amdgcn_sched_group_barrier(0x402, (n), 0)      // VALU | TRANS
 #define TVR_SG_DSR(n) __builtin_amdgcn_sched_group_barrier(0x100, (n), 0)
-struct AF { uint4 h, l; };
-// AR = the products a k-step takes (tvr_scene_set_arith): 3 = Wlo*xhi + Whi*xlo + Whi*xhi (fp32-class, the default); 2 = Wlo*xhi + Whi*xhi (weights keep their
-// 22 bits, activations are rounded to fp16); 1 = Whi*xhi (plain fp16 operands).  Always fp32 accumulation.  What a mode does not multiply is neither read nor derived.
+// AR = the products a k-step takes (tvr_mfma.h: AF, mfma3); what a mode does not multiply is neither read nor derived
 template <int AR = 3>
 __device__ __forceinline__ void load_af(AF &A, const unsigned char *WH, const unsigned char *WL, int off)
 {
     A.h = *(const uint4 *)(WH + off);
     if constexpr (AR >= 2) A.l = *(const uint4 *)(WL + off);
-}
-template <int AR = 3>
-__device__ __forceinline__ void mfma3(const AF &A, const Frag &b, f32x16 &acc)
-{
-#if TVR_DIAG & 16
-    // timing experiment (round 5, wrong pictures): what the 16x16x32 shape would cost / save IN this kernel — every 32x32x16 MFMA becomes two v_mfma_f32_16x16x32_f16 (the
-    // same cycles, FLOPs, operand registers and LDS bytes: one {hi, lo} A pair per six MFMAs, as two 16-column B tiles sharing each A fragment would issue them)
-    if constexpr (AR == 3) {
-        typedef float f32x4_ __attribute__((ext_vector_type(4)));
-        f32x4_ q0 = __builtin_shufflevector(acc, acc, 0, 1, 2, 3), q1 = __builtin_shufflevector(acc, acc, 4, 5, 6, 7);
-        const h8 al = __builtin_bit_cast(h8, A.l), ah = __builtin_bit_cast(h8, A.h), bh = __builtin_bit_cast(h8, b.hi), bl = __builtin_bit_cast(h8, b.lo);
-        q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, q0, 0, 0, 0);
-        q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bl, q1, 0, 0, 0);
-        q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, q0, 0, 0, 0);
-        q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, q1, 0, 0, 0);
-        q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, q0, 0, 0, 0);
-        q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, q1, 0, 0, 0);
-        acc = __builtin_shufflevector(__builtin_shufflevector(q0, q1, 0, 1, 2, 3, 4, 5, 6, 7), __builtin_shufflevector(acc, acc, 8, 9, 10, 11, 12, 13, 14, 15), 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-        return;
-    }
-#endif
-    if constexpr (AR >= 2) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, A.l), __builtin_bit_cast(h8, b.hi), acc, 0, 0, 0);
-    if constexpr (AR >= 3) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, A.h), __builtin_bit_cast(h8, b.lo), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, A.h), __builtin_bit_cast(h8, b.hi), acc, 0, 0, 0);
 }
 // byte offset of the A fragment of row block q & 3 of k-step q >> 2 inside a weight image
 #define TVR_AOFF(q) (((q) >> 2) * TVR_IMG_STEP + ((q) & 3) * TVR_IMG_RB)
@@ -368,7 +290,7 @@ __device__ __forceinline__ void finish_tile(const Carry &c, const unsigned char 
 // colour is  specular_tint * rgb_s + rgb_d.
 // The two waves of a SIMD (w and w + 4) run the same program.  Left alone they CONVOY: while both are in their matrix phase they share the MFMA
 // pipe, finish together, gather together (matrix pipe idle) and meet again at the next matrix phase — a stable state, whatever the start offset.
-// TVR_MTOKEN 1: a per-SIMD token in LDS makes the matrix phase mutually exclusive, which locks the pair in anti-phase (one gathers while the other
+// A per-SIMD token in LDS makes the matrix phase mutually exclusive, which locks the pair in anti-phase (one gathers while the other
 // multiplies): 13.9 -> 12.55 ms on one box, interleaved rounds.  Unequal matrix-phase priorities for the two waves instead: 14.0, no effect;
 // two tokens (basis + layer 1 | layer 2 as a two-stage pipeline): 12.98; spin back-off s_sleep 1 vs 8: equal; the token taken only at layer 1
 // (basis product outside it): 12.88; that plus all sin / cos in front of the token: 13.5 (12.97 same box); matrix-phase priority above
@@ -376,16 +298,12 @@ __device__ __forceinline__ void finish_tile(const Carry &c, const unsigned char 
 // between their MFMAs one group per MFMA (sched_group_barrier: M vvv d M vvv d ... instead of hipcc's MMMM vvvvvvvvvvvvvv): 13.01 vs 12.95.
 // Every path takes the token after its last global load has landed and gives it back before the next tile's first load, at most once per tile:
 // a wave never waits for the token while holding it, so the spin always ends.
-#ifndef TVR_MTOKEN
-#define TVR_MTOKEN 1
-#endif
 #ifndef TVR_NLO_LDS
 #define TVR_NLO_LDS 6     // k-steps whose basis LO fragments live in LDS (TensorVMSplit kernels; 6 x 864 B fit behind the image, 9 would not)
 #endif
 #ifndef TVR_MSLEEP
 #define TVR_MSLEEP 2
 #endif
-#if TVR_MTOKEN
 // The token only shapes the schedule: results do not depend on it.  The wait is therefore BOUNDED — after TVR_MTOKEN_SPINS polls (a legitimate wait
 // is the partner's matrix phase, ~6 us = ~50 polls) the wave goes ahead WITHOUT the token and gives nothing back (`have_tok`), so a lost or
 // stuck token can cost speed but never hang the grid or change a pixel.
@@ -404,27 +322,12 @@ __device__ __forceinline__ void finish_tile(const Carry &c, const unsigned char 
         have_tok = !got_;                                                                   \
     } while (0)
 #define TVR_TOKEN_GIVE(t) do { if (have_tok && lane == 0) atomicExch((t), 0); } while (0)
-#ifndef TVR_TOKEN_PHASE
-#define TVR_TOKEN_PHASE 1     // which phase the per-SIMD token makes mutually exclusive: 1 the matrix phase (shipped); 2 the GATHER phase (experiment: the two
-#endif                        // waves' matrix phases may then overlap — one's splits / sin / cos under the other's MFMAs — and "both gathering, pipe idle" cannot happen)
-#if TVR_TOKEN_PHASE == 1
 #ifndef TVR_GEN_PF
 #define TVR_GEN_PF 2       // k-steps between a thread's fetch of its uint4 of the streamed layer-1 image and the LDS store that stages it
 #endif
 // (GEN, the lockstep kernel of scenes with more than two encoding frequencies: no token — its waves meet at a barrier per layer-1 k-step anyway)
 #define TVR_ENTER_MATRIX() do { if (!GEN) TVR_TOKEN_TAKE(mtok); __builtin_amdgcn_s_setprio(TVR_PRIO_M); } while (0)
 #define TVR_LEAVE_MATRIX() do { if (!GEN) TVR_TOKEN_GIVE(mtok); __builtin_amdgcn_s_setprio(TVR_PRIO_G); } while (0)
-#define TVR_ENTER_GATHER()
-#else
-#define TVR_ENTER_MATRIX() do { TVR_TOKEN_GIVE(mtok); __builtin_amdgcn_s_setprio(TVR_PRIO_M); } while (0)
-#define TVR_LEAVE_MATRIX() __builtin_amdgcn_s_setprio(TVR_PRIO_G)
-#define TVR_ENTER_GATHER() TVR_TOKEN_TAKE(mtok)
-#endif
-#else
-#define TVR_ENTER_MATRIX() __builtin_amdgcn_s_setprio(TVR_PRIO_M)
-#define TVR_LEAVE_MATRIX() __builtin_amdgcn_s_setprio(TVR_PRIO_G)
-#define TVR_ENTER_GATHER()
-#endif
 // REFTensoRF's second row block on the same h fragments (REFTensoRF.py:126-132): A from the LDS image (8 weight rows; lanes 4..6 re-read the
 // normal rows so that both lane halves hold the normal, every other lane reads the zero row), biases as the initial accumulator.
 // Uses hf[], accA/B/C, G[], e, h, smem of the enclosing scope.
@@ -512,9 +415,7 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
         const uint4 *src = (const uint4 *)((const unsigned char *)sc.mlp_image + (BAS_ONLY ? TVR_IMG_BASH : 0));
         constexpr int nb = BAS_ONLY ? (TVR_MLP_IMAGE_BYTES - TVR_IMG_BASH) : (REF ? TVR_MLP_IMAGE_BYTES_REF : TVR_MLP_IMAGE_BYTES);
         for (int i = tid; i < nb / 16; i += SH_THREADS) ((uint4 *)smem)[i] = src[i];
-#if TVR_MTOKEN
         if (tid < 4) ((int *)(smem + nb))[tid] = 0;
-#endif
         for (int i = tid; i < NLO * 2 * TVR_IMG_BASH_ROWS; i += SH_THREADS) {            // global [s][half][32 rows] -> LDS [s][half][27 rows]
             const int sh = i / TVR_IMG_BASH_ROWS, row = i - sh * TVR_IMG_BASH_ROWS;
             ((uint4 *)(smem + BASL))[i] = ((const uint4 *)sc.basis_frag)[sh * 32 + row];
@@ -535,10 +436,8 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
         __syncthreads();
     }
 #endif
-#if TVR_MTOKEN
     bool have_tok = false;
     int *mtok = (int *)(smem + IMG_END) + (wave & 3);
-#endif
     // basis hi fragment of lane (e, h) at k-step s: rows 27..31 of the 32-row tile do not exist (their outputs are never used): clamp
     const unsigned char *bashp = smem + BASH + (h * TVR_IMG_BASH_ROWS + (e < TVR_IMG_BASH_ROWS ? e : TVR_IMG_BASH_ROWS - 1)) * 16;
     const unsigned char *baslp = bashp + (BASL - BASH);  // lo parts, same addressing, k-steps 0 .. NLO-1
@@ -563,7 +462,7 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
     // idle at the end (tvr_shade16.hip, profiles/r05_shade_tail.txt).  Only tvr_render(_z) launches the queue-to-queue mode, so the header is there; GEN keeps the static
     // stride (its layer 1 has workgroup barriers: every wave makes the same passes).  Which wave shades an entry does not matter to the entry.
     // Launches with fewer than TVR_TICKET_MIN tiles per wave keep the static stride: a ticket is a 4-tile quantum (tvr_shade16.hip).
-    constexpr bool TICKETS = TVR_TICKET > 0 && SRC == SH_SRC_QUEUE && DST == SH_DST_QUEUE && !GEN;
+    constexpr bool TICKETS = SRC == SH_SRC_QUEUE && DST == SH_DST_QUEUE && !GEN;
     constexpr int TKN = TICKETS ? TVR_TICKET : 1;
     const bool dyn = TICKETS && n_tiles >= (long long)gridDim.x * SH_WAVES * TVR_TICKET_MIN;
     unsigned *const tk = TICKETS ? const_cast<unsigned *>(a.counter) + 16 : nullptr;
@@ -580,18 +479,6 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
         qe_next = a.q_pos[le];
         qray_next = a.q_ray[le];
     }
-#if TVR_PHASE_FREE
-    constexpr bool PFREE = SRC == SH_SRC_QUEUE && !GEN && AR == 3;
-    Taps Tpre;
-    auto prefetch_next = [&]() {                                // taps of k-step 0 (plane 0, channels 8h..8h+7) of the entry in qe_next
-        float fcn[3];
-        const float pnn[3] = {qe_next.x, qe_next.y, qe_next.z};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) fcn[k] = unnorm(pnn[k], sc.gm1[k]);
-        load_taps<false>(Tpre, sc.aplane[0], sc.aline[0], sc.grid[0], sc.grid[1], sc.grid[2], fcn[0], fcn[1], fcn[2], TVR_Q0(0, h));
-    };
-    if constexpr (PFREE) { if (n_total > 0) prefetch_next(); }
-#endif
     // GEN: every wave of the workgroup makes the same number of passes (its layer 1 has workgroup barriers); a pass beyond the last tile works on dead lanes
     const long long tile_end = GEN ? ((n_tiles - (long long)lblk * SH_WAVES + tile_stride - 1) / tile_stride) * tile_stride + (long long)lblk * SH_WAVES + wave : n_tiles;
     long long tile_next = 0;
@@ -617,7 +504,6 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
         unsigned long long tg0 = 0, tgD = 0, tgF = 0, tg1 = 0, tgW = 0, tg2 = 0, tg3 = 0, tg4 = 0, tgL = 0;
 #endif
         TVR_STAMP(tg0);
-        TVR_ENTER_GATHER();
         // ---------------------------------------------------------------- GATHER phase: global loads + VALU + LDS, no MFMA ----
         TVR_STAMP(tgD);
         // queue entry: fetched one tile ahead (the loads are issued in the previous tile's gather phase and have landed by its phase
@@ -692,16 +578,10 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
                     if constexpr (H16) load_taps16(T16[s2 % (PFD + 1)], sc.aplane16[p], sc.aline16[p], sc.grid[ax], fc[ax], fc[bx], fc[vx], 2 * (s2 % 3) + h);
                     else load_taps<TVR_CHK>(T[s2 % (PFD + 1)], sc.aplane[p], sc.aline[p], sc.grid[ax], sc.grid[bx], sc.grid[vx], fc[ax], fc[bx], fc[vx], TVR_Q0(s2 % 3, h));
                 };
-#if TVR_PHASE_FREE
-                if constexpr (PFREE) T[0] = Tpre;                // issued in the previous tile's matrix phase (or in front of the loop)
-#endif
 #pragma unroll
                 for (int s = 0; s < 9; ++s) {
 #pragma unroll
                     for (int s2 = (s == 0 ? 0 : tgt(s - 1) + 1); s2 <= tgt(s); ++s2) {
-#if TVR_PHASE_FREE
-                        if (PFREE && s2 == 0) continue;
-#endif
                         issue(s2);
                     }
                     if (!REF && s == 7) {                              // (REFTensoRF: behind the loop — its extra live values leave no room earlier)
@@ -891,7 +771,7 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
                 // multiplied afterwards — reads and MFMAs in series.  Not the barrier count (groups of 2 / 4 / 5 k-steps per barrier: slower), not the order of the fragment
                 // derivation (pinned under the MFMAs: equal), not the fetch distance (1 .. 6 k-steps ahead: equal).  Now the image is staged TWO k-steps ahead (three slots), so
                 // that the fragments of row blocks 2, 3 are read under the MFMAs of row blocks 0, 1 and the NEXT k-step's fragments of row blocks 0, 1 under those of row blocks
-                // 2, 3.  Per accumulator the products come in mfma3x4's order (lo*hi, hi*lo, hi*hi): bit-identical results.
+                // 2, 3.  Per accumulator the products come in tvr_mfma.h's order (lo*hi, hi*lo, hi*hi): bit-identical results.
                 constexpr int PFG = TVR_GEN_PF;
                 uint4 wq[PFG];                                                            // wq[i]: k-step s + 2 + i, in flight
                 slot[0] = gsrc[0];                                                       // (the last readers of these slots passed a barrier since)
@@ -948,8 +828,8 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
 #pragma unroll
                 for (int rb = 0; rb < 4; ++rb) {
                     const int q = 4 * s + rb;
-                    if (q + TVR_PD < 40 && !(TVR_DIAG & 2)) load_af<AR>(ring[(q + TVR_PD) % TVR_RN], W1Hb, W1Lb, TVR_AOFF((TVR_DIAG & 8) ? 0 : ((TVR_DIAG & 4) ? ((q + TVR_PD) & 3) : q + TVR_PD)));
-                    mfma3<AR>(ring[(TVR_DIAG & 2) ? (q & 1) : (q % TVR_RN)], bcur, acc[rb]);
+                    if (q + TVR_PD < 40) load_af<AR>(ring[(q + TVR_PD) % TVR_RN], W1Hb, W1Lb, TVR_AOFF(q + TVR_PD));
+                    mfma3<AR>(ring[q % TVR_RN], bcur, acc[rb]);
                     if (s == 9 && rb == 0) {
                         // layer 2's prologue (acc[0] is complete): b2 -> the initial accumulators, W2's first two fragment pairs, relu(acc[0]) split
 #pragma unroll
@@ -957,8 +837,7 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
                         b2_init(0, a2cur);
                     }
                 }
-                if (TVR_DIAG & 1) bnxt = bcur;
-                else if (s + 1 < 10) l1_frag(s + 1, bnxt);
+                if (s + 1 < 10) l1_frag(s + 1, bnxt);
                 else { relu_frag(0, fr[0]); relu_frag(1, fr[1]); }         // acc[0] holds both k-steps' 16 hidden units
                 if (s < 9) {
 #pragma unroll
@@ -978,9 +857,6 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
                 TVR_SB;
             }
             }           // !GEN
-#if TVR_PHASE_FREE
-            if constexpr (PFREE) { TVR_SB; prefetch_next(); TVR_SB; }      // 12 global loads per lane between the MFMAs of layer 1 and those of layer 2
-#endif
             TVR_STAMP(tg3);
             {
                 f32x16 a2prev = f32x16{0};                          // the finished row block layer 3 is working through
@@ -1039,10 +915,6 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
             }
         }
         TVR_STAMP(tgL);
-#if TVR_DIAG & 1
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) cur.acc2 += acc[rb];              // keeps layer 1 alive in the build that derives no fragments
-#endif
         cur.ent = ent; cur.live = live; cur.wq = wq;
         cur.g[0] = G[3]; cur.g[1] = G[4]; cur.g[2] = G[5]; cur.g[3] = G[6];
         TVR_LEAVE_MATRIX();
@@ -1079,9 +951,6 @@ static hipError_t launch_shade_t(const SceneDev &sc, const ShadeArgs &a, hipStre
     hipError_t rc = hipFuncSetAttribute((const void *)shade_kernel<SRC, DST, REF, RC, GEN, AR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (rc != hipSuccess) return rc;
     unsigned grid = 256;       // one workgroup per CU (LDS holds the MLP weights), persistent over SH_TILE-entry tiles
-#ifdef TVR_EXP_GRID                                             // scripts/overlap_experiment.py only: a build_variant.sh -DTVR_EXP_GRID library
-    if (const char *g = getenv("TVR_EXP_GRID_SHADE")) { const long long v = atoll(g); if (v > 0 && v < 256) grid = (unsigned)v; }
-#endif
     if (SRC != SH_SRC_QUEUE) {
         const long long groups = (a.n + SH_TILE * SH_WAVES - 1) / (SH_TILE * SH_WAVES);
         if (groups < grid) grid = (unsigned)(groups > 0 ? groups : 1);

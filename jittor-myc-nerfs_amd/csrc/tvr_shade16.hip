@@ -30,9 +30,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef S16_WAVES
-#define S16_WAVES 8         // 4 (-DS16_WAVES=4): one wave per SIMD, a timing experiment (round 5: how much of the kernel's speed is the second wave's overlap)
-#endif
+#define S16_WAVES 8         // two waves per SIMD
 #define S16_THREADS (64 * S16_WAVES)
 #define S16_TILE 32
 #ifndef S16_PRIO_M
@@ -51,9 +49,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef S16_TOKEN_SPINS
 #define S16_TOKEN_SPINS 4096
 #endif
-#ifndef S16_MTOKEN
-#define S16_MTOKEN 1      // the per-SIMD matrix token (tvr_shade.hip: without it the two waves of a SIMD convoy); 0: A/B builds
-#endif
 #ifndef S16_TIMING
 #define S16_TIMING 0      // diagnostic build: per-phase s_memtime sums into stats[8..15] (scripts/phase_timing.py)
 #endif
@@ -66,51 +61,24 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define S16_SG_MFMA(n) __builtin_amdgcn_sched_group_barrier(0x008, (n), 0)
 #define S16_SG_VALU(n) __builtin_amdgcn_sched_group_barrier(0x402, (n), 0)      // VALU | TRANS
 #define S16_SG_DSR(n) __builtin_amdgcn_sched_group_barrier(0x100, (n), 0)
-#ifndef S16_FAST_SIGMOID
-#define S16_FAST_SIGMOID 1    // v_exp_f32 / v_rcp_f32 instead of expf + an IEEE division: -63 instructions per tile, 12.16 -> 11.97 ms (profiles/r05_shade16_ab.txt)
-#endif
-#ifndef S16_FAST_SINCOS
-#define S16_FAST_SINCOS 1     // sin / cos of the encoding from fract(v / 2 pi) (two VALU instructions) instead of the two-term Cody-Waite reduction (six)
-#endif
 // The kernel is bound by its SIMD's vector-issue port (492 MFMAs x 8 + ~1800 VALU x 4 cycles per tile against ~12 k cycles per tile and SIMD): every instruction
 // removed is time.  v_sin_f32 / v_cos_f32 take revolutions; v * (1 / 2 pi) carries fp32's relative rounding, i.e. a phase error of |v| * 6e-8 rad — 2e-6 at the
 // |v| <= 30 of a trained scene, 7e-5 at the |v| ~ 1100 that tests/test_gpu_parity.py::test_large_feature_magnitudes holds to the 1e-3 bar (its docstring prices exactly
 // this error); fract keeps the argument inside the instructions' domain for any magnitude.  tvr_shade.hip's other modes keep sincos_pe's Cody-Waite form.
 __device__ __forceinline__ void sincos_pe16(float x, float &s, float &c)
 {
-#if S16_FAST_SINCOS
     const float t = __builtin_amdgcn_fractf(x * 0.15915494309189535f);
     s = __builtin_amdgcn_sinf(t);
     c = __builtin_amdgcn_cosf(t);
-#else
-    sincos_pe(x, s, c);
-#endif
 }
-#ifndef S16_PIN
-#define S16_PIN 1         // 1: one empty-asm pin per interpolated float4 (keeps hipcc from spreading a tap set's consumers over the phase); 0: none
-#endif
 #ifndef S16_TICKET
-#define S16_TICKET 4      // tiles per ticket of the dynamic tile hand-out (0: the static stride of rounds 1 - 4)
+#define S16_TICKET 4      // tiles per ticket of the dynamic tile hand-out
 #endif
 #ifndef S16_TICKET_MIN
 #define S16_TICKET_MIN 256  // tiles per wave from which the tickets are used
 #endif
 #ifndef S16_GDEPTH
 #define S16_GDEPTH 1      // units of the gather in flight ahead of the one being interpolated (24 registers each)
-#endif
-#ifndef S16_DIAG_LDS
-#define S16_DIAG_LDS 0    // timing stand-ins (WRONG pictures): 1 = layers 1 / 2 read every other weight fragment from LDS (the fragment bytes of a 64-column form), 2 = none
-#endif
-#ifndef S16_SPLITB
-#define S16_SPLITB 1      // 1: tvr_mfma.h's split8b (the four pairs' operations batched: no s_nop between a pair's residuals and their packed conversion); 0: split8 (A/B)
-#endif
-#if S16_SPLITB
-#define S16_SPLIT8 split8b
-#else
-#define S16_SPLIT8 split8
-#endif
-#ifndef S16_SCHED
-#define S16_SCHED 1       // 1: sched_group_barrier windows in the matrix phase; 0: hipcc's own order (A/B)
 #endif
 
 struct AF16 { uint4 h, l; };
@@ -180,7 +148,7 @@ __device__ __forceinline__ float from_g1(float v)
 // requested behind the phase boundary and used after the two feature blocks; the normalised normal gives d.n and the reflection direction, which take the places of the
 // view direction (base rows 27..29) and of the unused row 30 (-d.n: MLPRender_Fea_Ref's input 0) in layer 1's B operands; the colour is relu(tint) * rgb_s + rgb_d.
 template <bool RC, bool REF>
-__global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_kernel(const SceneDev sc, const ShadeArgs a)
+__global__ __launch_bounds__(S16_THREADS, 2) void shade16_kernel(const SceneDev sc, const ShadeArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -227,7 +195,6 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
 
     float4 qe_next = make_float4(0.f, 0.f, 0.f, 0.f);
     unsigned qray_next = 0;
-#if S16_TICKET
     // Tiles are handed out in tickets of S16_TICKET consecutive tiles: the first ticket of a wave is its static share, every later one an atomicAdd on word 16 of the
     // scratch header (zeroed per call by zero_header with the queue counter it sits beside).  The chip's eight XCDs do not run at one speed under this kernel
     // (scripts/march_timeline.py, profiles/r05_shade_tail.txt: their workgroups finished 10.83 ... 11.71 ms after the launch with equal static shares); tickets let a
@@ -245,9 +212,6 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
     int tk_sub = 0;
     const int tk_len = dyn ? S16_TICKET : 0x7fffffff;
     const long long tk_step = dyn ? 1 : tile_stride;
-#else
-    long long tile_first = (long long)lblk * S16_WAVES + wave;
-#endif
     if (n_total > 0) {
         const long long e0 = tile_first * S16_TILE + c + (up ? 16 : 0);
         const long long le = e0 < n_total ? e0 : n_total - 1;
@@ -256,16 +220,12 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
     }
     long long tile_next = 0;
     for (long long tile = tile_first; tile < n_tiles; tile = tile_next) {
-#if S16_TICKET
         if (++tk_sub < tk_len) tile_next = tile + tk_step;               // (static mode: one endless "ticket" whose tiles lie a grid stride apart)
         else {
             tile_next = tick0 + (long long)__builtin_amdgcn_readfirstlane(tk_pending);
             tk_sub = 0;
             if (lane == 0 && tile_next < n_tiles) tk_pending = atomicAdd(tk, (unsigned)S16_TICKET);
         }
-#else
-        tile_next = tile + tile_stride;
-#endif
         const long long ent = tile * S16_TILE + c + (up ? 16 : 0);        // the entry this lane stores: A in groups 0, 1, B in groups 2, 3
         const bool live = ent < n_total;
 #if S16_TIMING
@@ -328,9 +288,7 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                     qv = __builtin_fmaf(P.wl, l1[j], qv);
                     out[4 * gq + j] = pv * qv;
                 }
-#if S16_PIN >= 1
                 asm volatile("" : "+v"(out[4 * gq]), "+v"(out[4 * gq + 1]), "+v"(out[4 * gq + 2]), "+v"(out[4 * gq + 3]));      // one pin per float4: keeps the loads' consumers together
-#endif
             }
         };
         PP pp[3];
@@ -367,7 +325,7 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                     for (int j = 0; j < 8; j += 2) rmax = absmax2(hv[j], hv[j + 1], rmax);
                     asm volatile("" : "+v"(rmax));
                 }
-                hf[u] = S16_SPLIT8(hv);
+                hf[u] = split8b(hv);
                 asm volatile("" : "+v"(hf[u].hi.x), "+v"(hf[u].hi.y), "+v"(hf[u].hi.z), "+v"(hf[u].hi.w), "+v"(hf[u].lo.x), "+v"(hf[u].lo.y), "+v"(hf[u].lo.z), "+v"(hf[u].lo.w));
                 S16_SB;
             }
@@ -427,7 +385,6 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
             }
             S16_STAMP(tg1);
             {                                          // take the SIMD's matrix token (bounded: a stuck token costs speed, never a hang or a pixel)
-#if S16_MTOKEN
                 int got, n = 0;
                 do {
                     int r = 1;
@@ -436,7 +393,6 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                     if (got) __builtin_amdgcn_s_sleep(S16_MSLEEP);
                 } while (got && ++n < S16_TOKEN_SPINS);
                 have_tok = !got;
-#endif
                 __builtin_amdgcn_s_setprio(S16_PRIO_M);
             }
             S16_STAMP(tgW);
@@ -446,10 +402,8 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                 const int s = q >> 1, rb = q & 1;
                 if (q + 2 < 10) bld(q + 2);
                 mfma6(br[q & 3], hA[s], hB[s], aF[rb][0], aF[rb][1]);
-#if S16_SCHED
                 if (q + 2 < 10) { if (((q + 2) >> 1) == 3) S16_SG_DSR(1); else S16_SG_DSR(2); }
                 S16_SG_MFMA(6);
-#endif
                 S16_SB;
             }
 #pragma unroll
@@ -506,7 +460,7 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                     if (t == 0) sincos_pe16(F[r], S1[r], C1[r]);
                     v[j] = t == 0 ? F[r] : (t == 1 ? S1[r] : (t == 2 ? 2.0f * S1[r] * C1[r] : (t == 3 ? C1[r] : __builtin_fmaf(-2.0f * S1[r], S1[r], 1.0f))));
                 }
-                b = S16_SPLIT8(v);
+                b = split8b(v);
             };
             auto relu_frag = [&](int ks, int ct, Frag &b) {           // layer 2's B fragment of k-step ks: the layer-1 accumulators of row blocks 2 ks, 2 ks + 1
                 float v[8];
@@ -518,15 +472,13 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                     for (int j = 0; j < 8; j += 2) rm = fmaxf(fmaxf(v[j], v[j + 1]), rm);
                     asm volatile("" : "+v"(rm));
                 }
-                b = S16_SPLIT8(v);
+                b = split8b(v);
             };
             S16_LDS_BASE(W1Hb, smem + TVR16_W1H + lane * 16);
             S16_LDS_BASE(W1Lb, smem + TVR16_W1L + lane * 16);
             S16_LDS_BASE(W2Hb, smem + TVR16_W2H + lane * 16);
             S16_LDS_BASE(W2Lb, smem + TVR16_W2L + lane * 16);
             AF16 ring[S16_RN];
-            AF16 dfix[2];
-            if (S16_DIAG_LDS == 3) { dfix[0].h = *(const uint4 *)(W1Hb); dfix[0].l = *(const uint4 *)(W1Lb); dfix[1].h = *(const uint4 *)(W1Hb + TVR16_FRAG); dfix[1].l = *(const uint4 *)(W1Lb + TVR16_FRAG); }
             Frag bA, bB, nA, nB;
             Frag frA[4], frB[4];
 #pragma unroll
@@ -539,11 +491,7 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
 #pragma unroll
                 for (int rb = 0; rb < 8; ++rb) {
                     const int q = 8 * s + rb;
-                    if (S16_DIAG_LDS == 2 || (S16_DIAG_LDS == 1 && ((q + S16_PD) & 1))) {        // timing stand-in (wrong pictures): no / every other fragment read
-                    } else if (S16_DIAG_LDS == 4) {    // real reads into the ring, real waits — of two fragment addresses only (same data every other step)
-                        ring[(q + S16_PD) % S16_RN].h = *(const uint4 *)(W1Hb + ((q + S16_PD) & 1) * TVR16_FRAG);
-                        ring[(q + S16_PD) % S16_RN].l = *(const uint4 *)(W1Lb + ((q + S16_PD) & 1) * TVR16_FRAG);
-                    } else if (q + S16_PD < 40) {
+                    if (q + S16_PD < 40) {
                         ring[(q + S16_PD) % S16_RN].h = *(const uint4 *)(W1Hb + (q + S16_PD) * TVR16_FRAG);
                         ring[(q + S16_PD) % S16_RN].l = *(const uint4 *)(W1Lb + (q + S16_PD) * TVR16_FRAG);
                     } else {                           // layer 2's first fragments ride in the ring behind layer 1's last
@@ -551,15 +499,10 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                         ring[(q + S16_PD) % S16_RN].h = *(const uint4 *)(W2Hb + (q2 * 8) * TVR16_FRAG);
                         ring[(q + S16_PD) % S16_RN].l = *(const uint4 *)(W2Lb + (q2 * 8) * TVR16_FRAG);
                     }
-                    if (S16_DIAG_LDS == 3) {           // every read issued, waited for and written to registers; the MFMAs take two fixed fragments
-                        { const uint4 rh = ring[q % S16_RN].h, rl = ring[q % S16_RN].l; asm volatile("" :: "v"(rh.x), "v"(rh.y), "v"(rh.z), "v"(rh.w), "v"(rl.x), "v"(rl.y), "v"(rl.z), "v"(rl.w)); }
-                        mfma6(dfix[q & 1], bA, bB, acc1[rb][0], acc1[rb][1]);
-                    } else
-                    mfma6(ring[S16_DIAG_LDS == 2 ? (q & 1) : (S16_DIAG_LDS == 1 ? (q & ~1) % S16_RN : q % S16_RN)], bA, bB, acc1[rb][0], acc1[rb][1]);
+                    mfma6(ring[q % S16_RN], bA, bB, acc1[rb][0], acc1[rb][1]);
                 }
                 if (s + 1 < 5) { l1_frag(s + 1, FA, SA, CA, nA); l1_frag(s + 1, FB, SB_, CB, nB); }
                 else { relu_frag(0, 0, frA[0]); relu_frag(0, 1, frB[0]); }              // (acc1[0], acc1[1] are complete after row block 1 of this k-step)
-#if S16_SCHED
 #pragma unroll
                 for (int rb = 0; rb < 8; ++rb) {
                     if (s + 1 < 5) {                   // {read} M V M VV {read} M V M VV M V M VV: nine VALU per row block, 72 per k-step
@@ -574,7 +517,6 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                         S16_SG_MFMA(1); S16_SG_VALU(1); S16_SG_MFMA(1); S16_SG_VALU(1);
                     }
                 }
-#endif
                 if (s + 1 < 5) { bA = nA; bB = nB; }
                 S16_SB;
             }
@@ -612,25 +554,14 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
 #pragma unroll
                     for (int ks = 0; ks < 4; ++ks) {
                         const int q = 4 * rb + ks, qn = q + S16_PD;
-                        if (S16_DIAG_LDS == 2 || ((S16_DIAG_LDS == 1 || S16_DIAG_LDS == 5) && (qn & 1))) {
-                        } else if (S16_DIAG_LDS == 4) {
-                            if (qn < 32) {
-                                ring[(40 + qn) % S16_RN].h = *(const uint4 *)(W1Hb + (qn & 1) * TVR16_FRAG);
-                                ring[(40 + qn) % S16_RN].l = *(const uint4 *)(W1Lb + (qn & 1) * TVR16_FRAG);
-                            }
-                        } else if (qn < 32) {
+                        if (qn < 32) {
                             ring[(40 + qn) % S16_RN].h = *(const uint4 *)(W2Hb + (8 * (qn & 3) + (qn >> 2)) * TVR16_FRAG);
                             ring[(40 + qn) % S16_RN].l = *(const uint4 *)(W2Lb + (8 * (qn & 3) + (qn >> 2)) * TVR16_FRAG);
                         }
-                        if (S16_DIAG_LDS == 3) {
-                            { const uint4 rh = ring[(40 + q) % S16_RN].h, rl = ring[(40 + q) % S16_RN].l; asm volatile("" :: "v"(rh.x), "v"(rh.y), "v"(rh.z), "v"(rh.w), "v"(rl.x), "v"(rl.y), "v"(rl.z), "v"(rl.w)); }
-                            mfma6(dfix[q & 1], frA[ks], frB[ks], a2A, a2B);
-                        } else
-                        mfma6(ring[S16_DIAG_LDS == 2 ? (q & 1) : ((S16_DIAG_LDS == 1 || S16_DIAG_LDS == 5) ? (40 + (q & ~1)) % S16_RN : (40 + q) % S16_RN)], frA[ks], frB[ks], a2A, a2B);
+                        mfma6(ring[(40 + q) % S16_RN], frA[ks], frB[ks], a2A, a2B);
                         if (rb == 0 && ks + 1 < 4) { relu_frag(ks + 1, 0, frA[ks + 1]); relu_frag(ks + 1, 1, frB[ks + 1]); }
                     }
                     if (rb > 0) l3_block(a2pA, a2pB);
-#if S16_SCHED
                     if (rb == 0) {
                         S16_SG_DSR(1);                                          // b2
 #pragma unroll
@@ -654,7 +585,6 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
                             S16_SG_MFMA(1); S16_SG_VALU(1); S16_SG_MFMA(1); S16_SG_VALU(2);
                         }
                     }
-#endif
                     a2pA = a2A; a2pB = a2B;
                     S16_SB;
                 }
@@ -680,14 +610,11 @@ __global__ __launch_bounds__(S16_THREADS, S16_WAVES == 4 ? 1 : 2) void shade16_k
             // (the order above interleaves c3 outermost where l3_block has r outermost: per sum s3X[c3] the additions run r = 0..3 either way)
             const float4 b3 = *(const float4 *)(smem + TVR16_B3);
             float r0 = group_sum2(s3A[0], s3B[0]), r1 = group_sum2(s3A[1], s3B[1]), r2 = group_sum2(s3A[2], s3B[2]);
-#if S16_FAST_SIGMOID
             // 1 / (1 + exp(-x)) with v_exp_f32 / v_rcp_f32 (1 ulp each) instead of expf + an IEEE division: ~25 fewer VALU instructions per tile, < 2e-7 in the colour
+            // (what it measured: DESIGN.md 4.2a)
             r0 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * (r0 + b3.x)));
             r1 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * (r1 + b3.y)));
             r2 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * (r2 + b3.z)));
-#else
-            r0 = sigmoid_f(r0 + b3.x); r1 = sigmoid_f(r1 + b3.y); r2 = sigmoid_f(r2 + b3.z);
-#endif
             if (REF) {                                 // REFTensoRF.py:232  specular_tint * clamp(rgb_s, 0) + rgb_d, for the entry this lane stores (group 0: A, group 2: B)
                 // tint sits in group 0 (row 3), rgb_d in group 1 (rows 4..6): entry A's into group 0 by one row swap, entry B's into group 2 by a row swap and a half swap
                 float tA = GA[3], tB, tdummy;
@@ -738,9 +665,6 @@ hipError_t launch_shade16(const SceneDev &sc, const ShadeArgs &a, hipStream_t st
     hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
     unsigned grid = 256;       // one workgroup per CU (the LDS holds the weights), persistent over 32-entry tiles
-#ifdef TVR_EXP_GRID
-    if (const char *gs = getenv("TVR_EXP_GRID_SHADE")) { const long long v = atoll(gs); if (v > 0 && v < 256) grid = (unsigned)v; }
-#endif
     if (ref) {
         if (rc) hipLaunchKernelGGL((shade16_kernel<true, true>), dim3(grid), dim3(S16_THREADS), lds, stream, sc, a);
         else hipLaunchKernelGGL((shade16_kernel<false, true>), dim3(grid), dim3(S16_THREADS), lds, stream, sc, a);

@@ -6,58 +6,25 @@
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef TVR_FAST_SIGMOID
-#define TVR_FAST_SIGMOID 0    // experiment (round 5): tvr_shade.hip's kernels with tvr_shade16.hip's v_exp_f32 / v_rcp_f32 sigmoid
-#endif
-#ifndef TVR_FAST_SINCOS
-#define TVR_FAST_SINCOS 0     // experiment (round 5): ... and its fract-based sin / cos argument
-#endif
-#if TVR_FAST_SIGMOID
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-#else
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-#endif
 // (the packed forms v_pk_fma_f32 / v_pk_mul_f32: half the instructions and 2 % SLOWER — beside the partner wave's MFMA stream a packed fp32 op takes
 // 52.7 cycles instead of 4.6, scripts/hwprobe/valu_rate.hip)
-// two plain v_fma_f32 / v_mul_f32, each pinned by an empty asm (without the pins, and with the SLP vectoriser off: 12.92 vs 12.75 ms)
-#ifndef TVR_PIN_PK
-#define TVR_PIN_PK 2      // 2: every fp32 op of the interpolation / layer 3 is pinned by an empty asm (keeps the SLP vectoriser from pairing them, and the ops where they
-#endif                    // are written); 1: one pin per interpolated channel pair (build with -fno-slp-vectorize); 0: none.  Each pin costs an s_nop 0 — hipcc guards
-                          // an inline asm that reads a just-written VGPR — 175 per tile at level 2; level 0 lets hipcc hoist the loads' consumers apart: 256 VGPRs + spills.
+// two plain v_fma_f32 / v_mul_f32, each pinned by an empty asm (without the pins, and with the SLP vectoriser off: 12.92 vs 12.75 ms).  Every fp32 op of the
+// interpolation / layer 3 is pinned: that keeps the SLP vectoriser from pairing them, and the ops where they are written.  Each pin costs an s_nop 0 — hipcc guards
+// an inline asm that reads a just-written VGPR — 175 per tile; without pins hipcc hoists the loads' consumers apart: 256 VGPRs + spills.
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c)
 {
     float x = __builtin_fmaf(a.x, b.x, c.x), y = __builtin_fmaf(a.y, b.y, c.y);
-#if TVR_PIN_PK >= 1
     asm volatile("" : "+v"(x)); asm volatile("" : "+v"(y));
-#endif
     return f32x2{x, y};
 }
 __device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b)
 {
     float x = a.x * b.x, y = a.y * b.y;
-#if TVR_PIN_PK >= 1
     asm volatile("" : "+v"(x)); asm volatile("" : "+v"(y));
-#endif
     return f32x2{x, y};
 }
 
-// the interpolation's own forms: pinned per op at TVR_PIN_PK 2, per channel pair at 1
-__device__ __forceinline__ f32x2 ip_fma(f32x2 a, f32x2 b, f32x2 c)
-{
-#if TVR_PIN_PK >= 2
-    return pk_fma(a, b, c);
-#else
-    return f32x2{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)};
-#endif
-}
-__device__ __forceinline__ f32x2 ip_mul(f32x2 a, f32x2 b)
-{
-#if TVR_PIN_PK >= 2
-    return pk_mul(a, b);
-#else
-    return f32x2{a.x * b.x, a.y * b.y};
-#endif
-}
 // the 6 taps (4 plane texels, 2 line texels) x 8 channels of one entry for one k-step
 struct Taps {
     float4 t[4][2], lv[2][2];
@@ -150,16 +117,13 @@ __device__ __forceinline__ void taps_eval(const Taps &T, int W, int H, int L, fl
             const f32x2 t3 = hh ? f32x2{T.t[3][g].z, T.t[3][g].w} : f32x2{T.t[3][g].x, T.t[3][g].y};
             const f32x2 l0 = hh ? f32x2{T.lv[0][g].z, T.lv[0][g].w} : f32x2{T.lv[0][g].x, T.lv[0][g].y};
             const f32x2 l1 = hh ? f32x2{T.lv[1][g].z, T.lv[1][g].w} : f32x2{T.lv[1][g].x, T.lv[1][g].y};
-            f32x2 p = ip_mul(w00, t0);
-            p = ip_fma(w01, t1, p);
-            p = ip_fma(w10, t2, p);
-            p = ip_fma(w11, t3, p);
-            f32x2 q = ip_mul(ul, l0);
-            q = ip_fma(wl, l1, q);
-            f32x2 r = ip_mul(p, q);
-#if TVR_PIN_PK == 1
-            asm volatile("" : "+v"(r.x), "+v"(r.y));
-#endif
+            f32x2 p = pk_mul(w00, t0);
+            p = pk_fma(w01, t1, p);
+            p = pk_fma(w10, t2, p);
+            p = pk_fma(w11, t3, p);
+            f32x2 q = pk_mul(ul, l0);
+            q = pk_fma(wl, l1, q);
+            f32x2 r = pk_mul(p, q);
             out[g * 4 + hh * 2] = r.x;
             out[g * 4 + hh * 2 + 1] = r.y;
         }
@@ -172,12 +136,6 @@ __device__ __forceinline__ void taps_eval(const Taps &T, int W, int H, int L, fl
 // the same as round 1's fract() form had for small |x| (scripts/accuracy_report.py), and smaller than that form's for |x| > 100.
 __device__ __forceinline__ void sincos_pe(float x, float &s, float &c)
 {
-#if TVR_FAST_SINCOS
-    const float tf = __builtin_amdgcn_fractf(x * 0.15915494309189535f);
-    s = __builtin_amdgcn_sinf(tf);
-    c = __builtin_amdgcn_cosf(tf);
-    return;
-#endif
     const float k = rintf(x * 0.15915494309189535f);
     float r = __builtin_fmaf(k, -6.2831854820251465f, x);
     r = __builtin_fmaf(k, 1.7484555e-7f, r);                   // 2pi = 6.2831854820251465 - 1.7484555e-7

@@ -17,29 +17,14 @@
 
 #define TB_WAVES 16                      // march_backward: one ray per wave, 16 rays per workgroup
 #define TB_THREADS (64 * TB_WAVES)
-#ifndef TB_DIAG
-#define TB_DIAG 0                        // timing experiments only: 1 no line atomics, 2 no pass C, 4 no plane atomics, 8 no pass A
-#endif
 #define TB_STAGE (2 * 3 * 16 * TVR_CD)   // floats per wave: [Q | P] of 3 pairs x 16 samples x 16 channels (pass A -> pass C)
 #define AHB_THREADS 1024                 // 16 waves, each walking AHB_ENTRIES / 16 consecutive entries with one lane per channel
 #define AHB_ENTRIES 2048                 // app_h_backward: queue entries per workgroup (per plane)
 
-template <int CTRL>
-__device__ __forceinline__ int qperm_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ int qbcast_i(int v, int k)
-{
-    switch (k) {
-    case 0: return qperm_i<0x00>(v);
-    case 1: return qperm_i<0x55>(v);
-    case 2: return qperm_i<0xAA>(v);
-    default: return qperm_i<0xFF>(v);
-    }
-}
-__device__ __forceinline__ float qbcast_f(float v, int k) { return __int_as_float(qbcast_i(__float_as_int(v), k)); }
 __device__ __forceinline__ float qxor_sum(float v)
 {
-    v += __int_as_float(qperm_i<0xB1>(__float_as_int(v)));
-    v += __int_as_float(qperm_i<0x4E>(__float_as_int(v)));
+    v += quad_perm_f<QUAD_XOR1>(v);
+    v += quad_perm_f<QUAD_XOR2>(v);
     return v;
 }
 
@@ -217,7 +202,7 @@ struct RayWin {
     __device__ __forceinline__ void reset() { kx = 0; ky = 0; a = 0.0f; }
     __device__ __forceinline__ void put(float *__restrict__ g, int Wp, int ch, int ti, int tj) const
     {
-        if (!(TB_DIAG & 4) && a != 0.0f) atomicAdd(g + ((long long)(ky + tj) * Wp + (kx + ti)) * TVR_CD + ch, a);
+        if (a != 0.0f) atomicAdd(g + ((long long)(ky + tj) * Wp + (kx + ti)) * TVR_CD + ch, a);
     }
     __device__ __forceinline__ void flush(float *__restrict__ g, int Wp, int ch, int ti, int tj) { put(g, Wp, ch, ti, tj); a = 0.0f; }
     // x0, y0, wx, wy are wave-uniform; v = gs * Q[ch]
@@ -257,7 +242,7 @@ struct RayLine {
     __device__ __forceinline__ void reset() { lk = 0; b = 0.0f; }
     __device__ __forceinline__ void put(float *g, int ch, int ti, int tj) const
     {
-        if (!(TB_DIAG & 1) && tj == 0 && b != 0.0f) atomicAdd(g + (size_t)(lk + ti) * TVR_CD + ch, b);
+        if (tj == 0 && b != 0.0f) atomicAdd(g + (size_t)(lk + ti) * TVR_CD + ch, b);
     }
     __device__ __forceinline__ void flush(float *g, int ch, int ti, int tj) { put(g, ch, ti, tj); b = 0.0f; }
     __device__ __forceinline__ void add(float *g, int ch, int ti, int tj, int l0, float wl, float v)
@@ -275,13 +260,6 @@ struct RayLine {
         b += (ti ? wl : 1.0f - wl) * v;
     }
 };
-
-__device__ __forceinline__ float wave_sum_f(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 template <bool LINE_LDS>
 __global__ __launch_bounds__(TB_THREADS) void march_backward_kernel(const SceneDev sc, const float *__restrict__ rays, const int n_rays, const int S,
@@ -328,7 +306,7 @@ __global__ __launch_bounds__(TB_THREADS) void march_backward_kernel(const SceneD
         // total = sum_k dL/dw_k w_k over the whole (possibly early-terminated) ray
         float tot_l = 0.0f;
         for (unsigned i = lane; i < cnt; i += 64) tot_l += grad_w[base + i] * mo.q_pos[base + i].w;
-        const float total = wave_sum_f(tot_l) + gacc * mo.acc[ray];
+        const float total = wave_sum(tot_l) + gacc * mo.acc[ray];
 
         float T = 1.0f, prefix = 0.0f;
         unsigned napp = 0;
@@ -379,10 +357,10 @@ __global__ __launch_bounds__(TB_THREADS) void march_backward_kernel(const SceneD
             float sf = 0.0f;
 #pragma unroll
             for (int k4 = 0; k4 < 4; ++k4) {
-                const bool v = qbcast_i((int)valid, k4) != 0;
+                const bool v = quad_bcast_i((int)valid, k4) != 0;
                 if (__ballot(v) == 0ull) continue;
-                const int ix = qbcast_i(i0[0], k4), iy = qbcast_i(i0[1], k4), iz = qbcast_i(i0[2], k4);
-                const float wx = qbcast_f(w[0], k4), wy = qbcast_f(w[1], k4), wz = qbcast_f(w[2], k4);
+                const int ix = quad_bcast_i(i0[0], k4), iy = quad_bcast_i(i0[1], k4), iz = quad_bcast_i(i0[2], k4);
+                const float wx = quad_bcast_f(w[0], k4), wy = quad_bcast_f(w[1], k4), wz = quad_bcast_f(w[2], k4);
                 float part = 0.0f;
                 if (v) {
                     const float4 a = vm_term<4, false>(sc.dplane[0], sc.dline[0], sc.grid[0], sc.grid[1], sc.grid[2], ix, iy, iz, wx, wy, wz, sub);
@@ -451,7 +429,7 @@ __global__ __launch_bounds__(TB_THREADS) void march_backward_kernel(const SceneD
                     const float gs = __shfl(dLdsf, src);
                     const int ix = __shfl(i0[0], src), iy = __shfl(i0[1], src), iz = __shfl(i0[2], src);
                     const float wx = __shfl(w[0], src), wy = __shfl(w[1], src), wz = __shfl(w[2], src);
-                    if (!(TB_DIAG & 8) && gs != 0.0f) {
+                    if (gs != 0.0f) {
                         float *sq = stage + (lane >> 2) * TVR_CD + 4 * sub;
                         pass_a(sc.dplane[0], sc.dline[0], sc.grid[0], ix, iy, iz, wx, wy, wz, sub, sq);
                         pass_a(sc.dplane[1], sc.dline[1], sc.grid[0], ix, iz, iy, wx, wz, wy, sub, sq + 16 * TVR_CD);
@@ -459,7 +437,7 @@ __global__ __launch_bounds__(TB_THREADS) void march_backward_kernel(const SceneD
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
-                for (int u = 0; u < ((TB_DIAG & 2) ? 0 : 16); ++u) {
+                for (int u = 0; u < 16; ++u) {
                     const int src = 16 * it + u;
                     const float gs = rdlane_f(dLdsf, src);
                     if (gs == 0.0f) continue;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: sha256 of the bench frame's pixels and depths (8 poses of scene A, 800x800x512) as rendered by the library TVR_LIB_PATH selects.
-Two libraries whose digests agree render the same frames bit for bit (used by scripts/phase_rule_test.sh; the default arithmetic unless --arith)."""
+Two libraries whose digests agree render the same frames bit for bit (the default arithmetic unless --arith)."""
 import argparse
 import hashlib
 import os
