@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define TVR_VERSION 141   /* 141 (round 6): tvr_train_forward / _backward take TensorVMSplit scenes with up to six encoding frequencies; tvr_train_work_describe.
+#define TVR_VERSION 141   /* (still 141: tvr_cp_scene_packed_bytes / tvr_cp_scene_create are ADDITIVE exports — no existing entry point, struct or layout changed)
+                           * 141 (round 6): tvr_train_forward / _backward take TensorVMSplit scenes with up to six encoding frequencies; tvr_train_work_describe.
                            * 140 (round 6): tvr_mlpnet_forward / _train_forward take packed_bytes and a caller-owned work buffer (tvr_mlpnet_work_bytes);
                            * tvr_mlpnet_packed_bytes no longer counts a ticket word; no entry point writes through a const pointer */
 
@@ -114,6 +115,21 @@ const char *tvr_last_error(void);
 size_t tvr_scene_packed_bytes(const tvr_scene_desc *desc);
 int tvr_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out);
 int tvr_scene_update(tvr_scene *scene, const tvr_scene_params *params, void *stream);
+/* A CP-decomposed field (TensorCP, tensorf-myc/models/tensoRF.py:317-447): three LINES per factor and no planes,
+ *   sigma_feature(p) = sum_r L0[r](p_z) L1[r](p_y) L2[r](p_x),   features(p) = basis_mat (A0[r](p_z) A1[r](p_y) A2[r](p_x))_r      (vecMode = [2, 1, 0])
+ * behind TensorBase's march, MLPRender_Fea and compositing.  Both calls read the same tvr_scene_desc: density_n_comp[0] = R_sigma in 1..96 and app_n_comp[0] = R_app in
+ * 1..288 (entries [1], [2] are ignored), variant 0, everything else as for TensorVMSplit; more than that is TVR_ERR_UNSUPPORTED with the field named in tvr_last_error().
+ * The result is an ordinary tvr_scene.  tvr_scene_update on it reads density_line[3] / app_line[3] ([1, R, L_i, 1], line i along axis 2 - i), basis_mat [27, R_app] and
+ * W1 .. b3; the plane pointers are ignored and may be NULL.
+ * ACCEPT a CP scene: tvr_scene_update / _touch / _destroy, tvr_scene_set_alpha, tvr_scene_set_range_check, tvr_scene_set / get_render_pieces, tvr_render_scratch_bytes(_min)
+ * (a CP render stages features, direction and colour per queue entry: 132 B more per entry than a VM scene, and that is what the two queries report), tvr_render (dense,
+ * stats, jitter, eps_T, prof and pieces as ever; no host read), tvr_density_feature, tvr_app_feature, tvr_mlp_render, tvr_filter_rays.
+ * REFUSE it with TVR_ERR_UNSUPPORTED before any launch (the message says "CP"): tvr_render_z and every *_ref call, tvr_march_forward(_z) / _backward(_z), tvr_app_h_forward /
+ * _backward, tvr_grad_scratch_bytes and tvr_train_work_bytes (they return 0), tvr_mlp_train_forward, tvr_train_forward / _backward, tvr_train_work_describe,
+ * tvr_scene_set_arith with a mode other than TVR_ARITH_F32, tvr_scene_validate_arith: CP scenes are inference-only and compute in the default arithmetic.
+ * Arithmetic: the lines, their products and the basis product are plain fp32 (FMAs); the network behind them is tvr_mlp_render's (fp16 hi / lo split, range rule below). */
+size_t tvr_cp_scene_packed_bytes(const tvr_scene_desc *desc);
+int tvr_cp_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out);
 /* CONCURRENCY: a scene's packed images are shared by every call that names the scene.  Any number of tvr_render(_z) calls may be in flight on different streams at once as
  * long as each has its own scratch and output buffers (they only READ the scene; render.py::FrameStream keeps two frames in flight this way).  Whatever WRITES the scene's
  * device state — tvr_scene_update, tvr_scene_set_alpha, tvr_scene_validate_arith, the first TVR_ARITH_F16 render after an update (it converts the fp16 copies) — must be

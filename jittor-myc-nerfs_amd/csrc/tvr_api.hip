@@ -52,6 +52,7 @@ struct PackedLayout {
     size_t dplane[3], dline[3], aplane[3], aline[3];
     size_t aplane16[3], aline16[3];            // fp16 copies of the appearance factors (TVR_ARITH_F16's gather), floats / 2
     size_t mlp_image, basis_frag, b3, w1gen, img16, basg16, refg16, total;
+    size_t cp_basis;                           // CP scenes: basis_mat as [ra / 4][27] float4 (CpDev::basis)
 };
 
 static PackedLayout packed_layout(const tvr_scene_desc &d)
@@ -82,11 +83,40 @@ static PackedLayout packed_layout(const tvr_scene_desc &d)
         L.aplane16[i] = take((H + 1) * (W + 1) * TVR_CA / 2);
         L.aline16[i] = take((Ln + 1) * TVR_CA / 2);
     }
+    L.cp_basis = 0;
+    L.total = off;
+    return L;
+}
+
+// A CP scene (tvr_cp_scene_create): three lines per factor in the slots of the VM lines — [L+1][rd] / [L+1][ra] fp32 — no planes, basis_mat in fp32 for the CP feature
+// kernel, and the network images exactly as a variant-0 scene has them (the 32x32x16 shade_kernel image; no 16x16x32 image: the CP path does not use shade16_kernel).
+#define TVR_CP_MAX_SIGMA 96
+#define TVR_CP_MAX_APP 288
+static int cp_rd(const tvr_scene_desc &d) { return (d.density_n_comp[0] + 15) / 16 * 16; }     // the march's quad gather reads 16 channels per step
+static int cp_ra(const tvr_scene_desc &d) { return (d.app_n_comp[0] + 3) / 4 * 4; }
+static PackedLayout cp_packed_layout(const tvr_scene_desc &d)
+{
+    PackedLayout L;
+    memset(&L, 0, sizeof(L));
+    size_t off = 0;
+    auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * sizeof(float), 256); return o; };
+    for (int i = 0; i < 3; ++i) {
+        const size_t Ln = d.grid[kVecH[i]];
+        L.dline[i] = take((Ln + 1) * cp_rd(d));
+        L.aline[i] = take((Ln + 1) * cp_ra(d));
+    }
+    L.cp_basis = take((size_t)cp_ra(d) * TVR_APPDIM);
+    L.mlp_image = take(TVR_MLP_IMAGE_BYTES_REF / 4);
+    L.basis_frag = take(TVR_BASIS_FRAG_BYTES / 4);
+    L.b3 = take(16);
+    L.w1gen = (d.view_pe > 2 || d.fea_pe > 2) ? take(TVR_W1GEN_BYTES / 4) : 0;
     L.total = off;
     return L;
 }
 
 struct tvr_scene {
+    bool cp;                   // a CP scene (tvr_cp_scene_create): dev.dline / dev.aline hold the CP lines, `cpd` the rest; default arithmetic only, inference only
+    CpDev cpd;
     tvr_scene_desc desc;
     PackedLayout lay;
     char *packed;
@@ -137,15 +167,24 @@ static int refresh_h16(tvr_scene *s, hipStream_t stream)
     return TVR_OK;
 }
 
-static int check_desc(const tvr_scene_desc *d)
+static int check_desc(const tvr_scene_desc *d, bool cp = false)
 {
     if (!d) return fail(TVR_ERR_INVALID, "desc is NULL");
+    if (cp) {      // a CP field has ONE component count per factor: entry [0]; [1] and [2] are ignored
+        if (d->density_n_comp[0] < 1 || d->density_n_comp[0] > TVR_CP_MAX_SIGMA)
+            return fail(TVR_ERR_UNSUPPORTED, "CP scene: density_n_comp[0]=%d; this build supports 1..%d", d->density_n_comp[0], TVR_CP_MAX_SIGMA);
+        if (d->app_n_comp[0] < 1 || d->app_n_comp[0] > TVR_CP_MAX_APP)
+            return fail(TVR_ERR_UNSUPPORTED, "CP scene: app_n_comp[0]=%d; this build supports 1..%d", d->app_n_comp[0], TVR_CP_MAX_APP);
+        if (d->variant != 0) return fail(TVR_ERR_UNSUPPORTED, "CP scene: variant=%d; a CP scene is TensorCP with MLPRender_Fea, variant must be 0", d->variant);
+        if (d->view_pe < 0 || d->view_pe > TVR_GEN_PE) return fail(TVR_ERR_UNSUPPORTED, "CP scene: view_pe=%d; this build supports 0..%d", d->view_pe, TVR_GEN_PE);
+        if (d->fea_pe < 0 || d->fea_pe > TVR_GEN_PE) return fail(TVR_ERR_UNSUPPORTED, "CP scene: fea_pe=%d; this build supports 0..%d", d->fea_pe, TVR_GEN_PE);
+    }
     for (int i = 0; i < 3; ++i) {
         if (d->grid[i] < 2 || d->grid[i] > 4096) return fail(TVR_ERR_INVALID, "grid[%d]=%d out of [2,4096]", i, d->grid[i]);
         // fewer components / narrower layers than the kernels are built for are packed with zero padding (exact); more are not supported
-        if (d->density_n_comp[i] < 1 || d->density_n_comp[i] > TVR_CD)
+        if (!cp && (d->density_n_comp[i] < 1 || d->density_n_comp[i] > TVR_CD))
             return fail(TVR_ERR_UNSUPPORTED, "density_n_comp[%d]=%d; this build supports 1..%d", i, d->density_n_comp[i], TVR_CD);
-        if (d->app_n_comp[i] < 1 || d->app_n_comp[i] > TVR_CA)
+        if (!cp && (d->app_n_comp[i] < 1 || d->app_n_comp[i] > TVR_CA))
             return fail(TVR_ERR_UNSUPPORTED, "appearance_n_comp[%d]=%d; this build supports 1..%d", i, d->app_n_comp[i], TVR_CA);
         if (!(d->aabb[3 + i] > d->aabb[i])) return fail(TVR_ERR_INVALID, "aabb hi <= lo on axis %d", i);
     }
@@ -174,17 +213,36 @@ size_t tvr_scene_packed_bytes(const tvr_scene_desc *desc)
     return packed_layout(*desc).total;
 }
 
-int tvr_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out)
+}  // extern "C"
+
+// entry points a CP scene does not have (training, explicit depths, REFTensoRF's calls, the reduced arithmetics): refused before anything is launched
+static int cp_refused(const tvr_scene *s, const char *fn)
+{
+    if (s && s->cp) return fail(TVR_ERR_UNSUPPORTED, "%s: the scene is a CP scene (tvr_cp_scene_create) — CP scenes render and answer field queries in the default arithmetic; "
+                                                     "training, explicit depths, the _ref calls and the reduced arithmetics are not built for CP", fn);
+    return TVR_OK;
+}
+#define NOT_CP(s)                                        \
+    do {                                                 \
+        int rcp_ = cp_refused((s), __func__);            \
+        if (rcp_ != TVR_OK) return rcp_;                 \
+    } while (0)
+
+static int scene_create_impl(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out, bool cp)
 {
     if (!out) return fail(TVR_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    int rc = check_desc(desc);
+    int rc = check_desc(desc, cp);
     if (rc != TVR_OK) return rc;
-    PackedLayout L = packed_layout(*desc);
+    PackedLayout L = cp ? cp_packed_layout(*desc) : packed_layout(*desc);
     if (!packed_dev || packed_bytes < L.total) return fail(TVR_ERR_SCRATCH, "packed buffer %zu B < required %zu B", packed_bytes, L.total);
     if ((uintptr_t)packed_dev % 256) return fail(TVR_ERR_SCRATCH, "packed buffer must be 256-byte aligned");
     tvr_scene *s = new (std::nothrow) tvr_scene;
     if (!s) return fail(TVR_ERR_INVALID, "out of host memory");
+    s->cp = cp;
+    s->cpd.rd = cp ? cp_rd(*desc) : 0;
+    s->cpd.ra = cp ? cp_ra(*desc) : 0;
+    s->cpd.basis = cp ? (const float4 *)((char *)packed_dev + L.cp_basis) : nullptr;
     s->desc = *desc;
     s->lay = L;
     s->packed = (char *)packed_dev;
@@ -216,7 +274,7 @@ int tvr_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed
     v.b3 = (const float *)(s->packed + L.b3);
     v.gen = (desc->view_pe > 2 || desc->fea_pe > 2) ? 1 : 0;
     v.w1gen = v.gen ? (const void *)(s->packed + L.w1gen) : nullptr;
-    v.img16 = !v.gen ? (const void *)(s->packed + L.img16) : nullptr;
+    v.img16 = (!v.gen && !cp) ? (const void *)(s->packed + L.img16) : nullptr;
     v.basg16 = v.img16 ? (const void *)(s->packed + L.basg16) : nullptr;
     v.refg16 = (v.img16 && desc->variant == 1) ? (const void *)(s->packed + L.refg16) : nullptr;
     v.near_ = desc->near_;
@@ -230,8 +288,28 @@ int tvr_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed
     v.range_check = 1;
     v.arith = TVR_ARITH_F32;
     v.avol = nullptr;
+    if (cp)
+        for (int k = 0; k < 3; ++k) { v.dplane[k] = v.aplane[k] = nullptr; v.aplane16[k] = v.aline16[k] = nullptr; }
     *out = s;
     return TVR_OK;
+}
+
+extern "C" {
+
+int tvr_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out)
+{
+    return scene_create_impl(desc, packed_dev, packed_bytes, out, false);
+}
+
+size_t tvr_cp_scene_packed_bytes(const tvr_scene_desc *desc)
+{
+    if (check_desc(desc, true) != TVR_OK) return 0;
+    return cp_packed_layout(*desc).total;
+}
+
+int tvr_cp_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out)
+{
+    return scene_create_impl(desc, packed_dev, packed_bytes, out, true);
 }
 
 int tvr_scene_update(tvr_scene *s, const tvr_scene_params *p, void *stream_)
@@ -239,7 +317,13 @@ int tvr_scene_update(tvr_scene *s, const tvr_scene_params *p, void *stream_)
     if (!s || !p) return fail(TVR_ERR_INVALID, "scene/params is NULL");
     hipStream_t stream = (hipStream_t)stream_;
     const tvr_scene_desc &d = s->desc;
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < 3 && s->cp; ++i) {              // CP: lines only ([1, R, L_i, 1]); the plane pointers are ignored
+        if (!p->density_line[i] || !p->app_line[i]) return fail(TVR_ERR_INVALID, "CP scene: line pointer %d is NULL", i);
+        const int Ln = d.grid[kVecH[i]];
+        HIP_TRY(launch_pack_plane(p->density_line[i], (float *)(s->packed + s->lay.dline[i]), d.density_n_comp[0], s->cpd.rd, Ln, 1, stream));
+        HIP_TRY(launch_pack_plane(p->app_line[i], (float *)(s->packed + s->lay.aline[i]), d.app_n_comp[0], s->cpd.ra, Ln, 1, stream));
+    }
+    for (int i = 0; i < 3 && !s->cp; ++i) {
         if (!p->density_plane[i] || !p->density_line[i] || !p->app_plane[i] || !p->app_line[i])
             return fail(TVR_ERR_INVALID, "plane/line pointer %d is NULL", i);
         const int W = d.grid[kMatH[i][0]], H = d.grid[kMatH[i][1]], Ln = d.grid[kVecH[i]];
@@ -254,7 +338,9 @@ int tvr_scene_update(tvr_scene *s, const tvr_scene_params *p, void *stream_)
     sh.featureC = d.featureC; sh.fea_pe = d.fea_pe; sh.view_pe = d.view_pe;
     sh.n_in = TVR_APPDIM + 3 + 2 * TVR_APPDIM * d.fea_pe + 6 * d.view_pe + (d.variant == 1 ? 1 : 0);
     sh.k_app = 0;
-    for (int i = 0; i < 3; ++i) { sh.app_n_comp[i] = d.app_n_comp[i]; sh.app_off[i] = sh.k_app; sh.k_app += d.app_n_comp[i]; }
+    for (int i = 0; i < 3; ++i) { sh.app_n_comp[i] = s->cp ? 0 : d.app_n_comp[i]; sh.app_off[i] = sh.k_app; sh.k_app += sh.app_n_comp[i]; }
+    // (CP: the image's basis fragments are packed as zeros — shade_kernel<SH_SRC_FEAT> copies but never multiplies them — and basis_mat goes to the CP feature kernel in fp32)
+    if (s->cp) HIP_TRY(launch_cp_pack_basis(p->basis_mat, d.app_n_comp[0], s->cpd.ra, (float4 *)(s->packed + s->lay.cp_basis), stream));
     if (s->dev.gen) {       // more than two frequencies: layer 1's image is the 26-k-step general one in global memory; the LDS image's W1 region is two staging slots
         HIP_TRY(launch_zero_f32((float *)(img + TVR_IMG_W1H), (TVR_IMG_W2H - TVR_IMG_W1H) / 4, stream));
         HIP_TRY(launch_pack_mlp(p->W1, p->b1, s->packed + s->lay.w1gen, nullptr, 5, sh, stream));
@@ -337,6 +423,7 @@ int tvr_scene_set_arith(tvr_scene *s, int32_t mode)
 {
     if (!s) return fail(TVR_ERR_INVALID, "tvr_scene_set_arith: scene is NULL");
     if (mode != TVR_ARITH_F32 && mode != TVR_ARITH_F16ACT && mode != TVR_ARITH_F16) return fail(TVR_ERR_INVALID, "tvr_scene_set_arith: mode %d is none of TVR_ARITH_*", (int)mode);
+    if (mode != TVR_ARITH_F32) NOT_CP(s);
     s->arith_req = mode;
     s->dev.arith = (mode == TVR_ARITH_F32 || s->arith_valid == mode) ? mode : TVR_ARITH_F32;
     if (s->dev.arith != mode)
@@ -387,8 +474,8 @@ int tvr_scene_destroy(tvr_scene *s)
 
 // scratch carving shared by the size query and tvr_render
 #define TVR_RAY_ORDER_MAX_RAYS 65536      // march_forward_impl: batches up to this many rays get a ray-ordered queue
-struct ScratchLayout { size_t counter, ray_off, ray_cnt, acc, q_pos, q_out, q_ray, q_j, ray_new, total; };
-static ScratchLayout scratch_layout(int64_t n_rays, int32_t S)
+struct ScratchLayout { size_t counter, ray_off, ray_cnt, acc, q_pos, q_out, q_ray, q_j, ray_new, cp_feat, cp_dir, cp_rgb, total; };
+static ScratchLayout scratch_layout(int64_t n_rays, int32_t S, bool cp = false)
 {
     ScratchLayout L;
     size_t off = 0;
@@ -403,6 +490,10 @@ static ScratchLayout scratch_layout(int64_t n_rays, int32_t S)
     L.q_ray = take(cap * 4);
     L.q_j = take(cap * 4);
     L.ray_new = take(n_rays * 4);          // the training queue's ray-ordered offsets (launch_queue_ray_order); behind everything the public layout names
+    // a CP scene's render stages per queue entry what its feature kernel hands the network: features [cap,27], view direction [cap,3], colour [cap,3] (132 B more per entry)
+    L.cp_feat = cp ? take(cap * TVR_APPDIM * 4) : 0;
+    L.cp_dir = cp ? take(cap * 12) : 0;
+    L.cp_rgb = cp ? take(cap * 12) : 0;
     L.total = off;
     return L;
 }
@@ -429,9 +520,10 @@ static PiecePlan piece_plan(const tvr_scene *s, int64_t n_rays)
 size_t tvr_render_scratch_bytes(const tvr_scene *s, int64_t n_rays, int32_t n_samples)
 {
     if (n_rays <= 0 || n_samples <= 0) return 256;
-    const size_t whole = scratch_layout(n_rays, n_samples).total;
+    const bool cp = s && s->cp;
+    const size_t whole = scratch_layout(n_rays, n_samples, cp).total;
     const PiecePlan P = piece_plan(s, n_rays);             // two pieces in flight, each with a scratch of its own carved from the caller's buffer
-    const size_t two = P.K > 1 ? 2 * scratch_layout(P.rays, n_samples).total : 0;
+    const size_t two = P.K > 1 ? 2 * scratch_layout(P.rays, n_samples, cp).total : 0;
     return whole > two ? whole : two;
 }
 
@@ -441,7 +533,8 @@ size_t tvr_render_scratch_bytes_min(const tvr_scene *s, int64_t n_rays, int32_t 
 {
     if (n_rays <= 0 || n_samples <= 0) return 256;
     const PiecePlan P = piece_plan(s, n_rays);
-    return P.K > 1 ? 2 * scratch_layout(P.rays, n_samples).total : scratch_layout(n_rays, n_samples).total;
+    const bool cp = s && s->cp;
+    return P.K > 1 ? 2 * scratch_layout(P.rays, n_samples, cp).total : scratch_layout(n_rays, n_samples, cp).total;
 }
 
 }  // extern "C"
@@ -464,6 +557,32 @@ static int render_one(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S
     mo.lam6 = lam6_out;
     HIP_TRY(launch_zero_header(mo.counter, stream));                   // [0] queue length, [1] the march's tile counter, [2] its fault flag, [3] unused here
     if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
+    if (s->cp) {
+        // CP: march -> features (+ the entries' view directions) -> the network on the staged features -> colours + weights into q_out; every kernel behind the march takes
+        // the entry count from the device (word 0 of the header), the grids are sized for the capacity: no host read
+        const long long cap = (long long)n_rays * S;
+        float *feat = (float *)(b + L.cp_feat), *dir = (float *)(b + L.cp_dir), *crgb = (float *)(b + L.cp_rgb);
+        HIP_TRY(launch_cp_march(s->dev, s->cpd, rays, (int)n_rays, S, sm, eps_T, mo, dense, stream));
+        if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
+        HIP_TRY(launch_cp_app_feature(s->dev, s->cpd, (const float *)mo.q_pos, 4, cap, mo.counter, mo.q_ray, rays, feat, dir, stream));
+        ShadeArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.counter = mo.counter;
+        sa.n = cap;
+        sa.viewdirs = dir;
+        sa.feats = feat;
+        sa.out = crgb;
+        HIP_TRY(launch_shade(s->dev, SH_SRC_FEAT, SH_DST_RGB, sa, stream));
+        HIP_TRY(launch_cp_rgbw(mo, crgb, cap, stream));
+        if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
+        if (dense && dense->rgb) {
+            HIP_TRY(hipMemsetAsync(dense->rgb, 0, (size_t)n_rays * S * 3 * sizeof(float), stream));
+            HIP_TRY(launch_scatter_rgb(mo, S, dense->rgb, stream));
+        }
+        HIP_TRY(launch_composite(mo, (int)n_rays, white_bg, rgb_out, stream));
+        if (ev) HIP_TRY(hipEventRecord(ev[3], stream));
+        return TVR_OK;
+    }
     HIP_TRY(launch_march(s->dev, rays, (int)n_rays, S, sm, eps_T, mo, dense, stream));
     if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
     ShadeArgs sa;
@@ -510,7 +629,7 @@ static int render_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     if ((size_t)n_rays * (size_t)S >= (1ull << 32)) return fail(TVR_ERR_INVALID, "n_rays*n_samples must be < 2^32 per call (chunk the rays)");
     if (!(eps_T >= 0.0f) || eps_T > s->desc.weight_thres)
         return fail(TVR_ERR_INVALID, "eps_T=%g must be in [0, weight_thres=%g] so that no appearance sample is skipped", eps_T, s->desc.weight_thres);
-    const size_t need = dense ? scratch_layout(n_rays, S).total : tvr_render_scratch_bytes_min(s, n_rays, S);
+    const size_t need = dense ? scratch_layout(n_rays, S, s->cp).total : tvr_render_scratch_bytes_min(s, n_rays, S);
     if (!scratch || scratch_bytes < need) return fail(TVR_ERR_SCRATCH, "scratch %zu B < required %zu B", scratch_bytes, need);
     if ((uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "scratch must be 256-byte aligned");
     if (prof && prof->n_calls >= prof->max_calls) return fail(TVR_ERR_INVALID, "profile is full (%d calls)", prof->max_calls);
@@ -524,7 +643,7 @@ static int render_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     if (P.K == 1) {
         hipEvent_t *ev = nullptr;
         if (prof && !(ev = profile_slot(prof))) return fail(TVR_ERR_HIP, "tvr_profile: hipEventCreate failed");
-        int rc = render_one(s, rays, n_rays, S, white_bg, sm, eps_T, rgb_out, depth_out, lam6_out, (char *)scratch, scratch_layout(n_rays, S), dense, stats, ev, stream);
+        int rc = render_one(s, rays, n_rays, S, white_bg, sm, eps_T, rgb_out, depth_out, lam6_out, (char *)scratch, scratch_layout(n_rays, S, s->cp), dense, stats, ev, stream);
         if (rc != TVR_OK) return rc;
         if (prof) prof->n_calls++;
         return TVR_OK;
@@ -536,7 +655,7 @@ static int render_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     // result is independent of the batch it arrives in (bit for bit: tests/test_gpu_parity.py), so the pixels are those of the one-piece call.
     int rc = ensure_side_streams(s);
     if (rc != TVR_OK) return rc;
-    const ScratchLayout Lp = scratch_layout(P.rays, S);
+    const ScratchLayout Lp = scratch_layout(P.rays, S, s->cp);
     HIP_TRY(hipEventRecord(s->ev_fork, stream));
     for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamWaitEvent(s->side[i], s->ev_fork, 0));
     // (equal pieces: a half- or third-size first piece on stream 1 — a stagger from the start — measured 18.71 - 18.76 ms against 18.64 - 18.67, profiles/r06_split_frame.txt)
@@ -576,6 +695,7 @@ int tvr_render_z(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, int
                  float *rgb_out, float *depth_out, float *t_last_tiny_out, void *scratch, size_t scratch_bytes, const tvr_dense_out *dense,
                  uint64_t *stats, void *stream)
 {
+    NOT_CP(s);
     if (!z_vals) return fail(TVR_ERR_INVALID, "z_vals is NULL");
     const MarchSampling sm = {nullptr, z_vals};
     return render_impl(s, rays, n_rays, S, white_bg, sm, eps_T, rgb_out, depth_out, t_last_tiny_out, scratch, scratch_bytes, dense, stats, nullptr, stream);
@@ -622,6 +742,7 @@ int tvr_scratch_describe(int64_t n_rays, int32_t n_samples, tvr_scratch_layout *
 static int march_forward_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const MarchSampling &sm, float eps_T, float *depth_out,
                               float *lam6_out, void *scratch, size_t scratch_bytes, void *stream_)
 {
+    NOT_CP(s);
     int rc = scene_ready(s);
     if (rc != TVR_OK) return rc;
     if (!rays || !depth_out || n_rays <= 0) return fail(TVR_ERR_INVALID, "rays/depth_out NULL or n_rays <= 0");
@@ -660,6 +781,7 @@ __global__ __launch_bounds__(256) void maxdiff_kernel(const float *__restrict__ 
 int tvr_scene_validate_arith(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, int32_t white_bg, float eps_T, float tol, void *scratch, size_t scratch_bytes,
                              float *work, size_t work_bytes, float *max_diff_out, int64_t *probe_app_samples_out, void *stream_)
 {
+    NOT_CP(s);
     if (!s || !s->params_set) return fail(TVR_ERR_INVALID, "tvr_scene_validate_arith: scene is NULL or tvr_scene_update has not run");
     if (!max_diff_out) return fail(TVR_ERR_INVALID, "tvr_scene_validate_arith: max_diff_out is NULL");
     *max_diff_out = 0.0f;
@@ -746,6 +868,7 @@ int tvr_filter_rays(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, 
 size_t tvr_grad_scratch_bytes(const tvr_scene *s)
 {
     if (!s) return 0;
+    if (cp_refused(s, __func__) != TVR_OK) return 0;
     return s->lay.mlp_image;      // the VM blocks come first in the packed layout; the gradient images mirror them
 }
 
@@ -767,6 +890,7 @@ static int march_backward_impl(tvr_scene *s, const float *rays, int64_t n_rays, 
                                size_t fwd_scratch_bytes, const float *grad_w, const float *grad_acc, const float *lam6, const float *grad_lam6,
                                void *grad_scratch, size_t grad_scratch_bytes, const tvr_vm_grads *out, void *stream_, long long gw_cap = -1)
 {
+    NOT_CP(s);
     int rc = scene_ready(s);
     if (rc != TVR_OK) return rc;
     if (!rays || !fwd_scratch || !grad_w || !grad_acc || !grad_scratch || !out || n_rays <= 0) return fail(TVR_ERR_INVALID, "NULL argument");
@@ -817,6 +941,7 @@ int tvr_march_backward_z(tvr_scene *s, const float *rays, int64_t n_rays, int32_
 
 int tvr_app_h_forward(tvr_scene *s, const float *xyz, int64_t m, float *h_out, size_t h_bytes, void *stream)
 {
+    NOT_CP(s);
     if (m > 0) NEED("h_out [m,144]", h_bytes, m, TVR_KAPP);
     int rc = scene_ready(s);
     if (rc != TVR_OK) return rc;
@@ -833,6 +958,7 @@ static int mlp_train_forward_impl(tvr_scene *s, int variant, const float *h, con
                                   void *stream)
 {
     const char *fn = variant ? "tvr_mlp_train_forward_ref" : "tvr_mlp_train_forward";
+    { int rcp = cp_refused(s, fn); if (rcp != TVR_OK) return rcp; }
     if (m > 0) {
         int rc_;
         if ((rc_ = need_bytes(fn, "rgb [m,3]", rgb_bytes, m, 3)) != TVR_OK) return rc_;
@@ -936,6 +1062,7 @@ int tvr_mlp_train_backward_ref(const float *W1, const float *W2, const float *W3
 static int app_h_backward_impl(tvr_scene *s, const float *xyz, int xyz_stride, int64_t m, const unsigned *m_dev, const float *dh, void *grad_scratch,
                                size_t grad_scratch_bytes, const tvr_vm_grads *out, void *stream_)
 {
+    NOT_CP(s);
     int rc = scene_ready(s);
     if (rc != TVR_OK) return rc;
     if (!grad_scratch || !out || m < 0 || (m > 0 && (!xyz || !dh))) return fail(TVR_ERR_INVALID, "NULL argument");
@@ -986,6 +1113,7 @@ static WorkLayout work_layout(int64_t n_rays, int32_t S, int64_t cap, bool gen =
 static int train_args_ok(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const void *fwd_scratch, size_t fwd_bytes, const void *work, size_t work_bytes,
                          int64_t app_cap)
 {
+    NOT_CP(s);
     int rc = scene_ready(s);
     if (rc != TVR_OK) return rc;
     const tvr_scene_desc &d = s->desc;
@@ -1009,11 +1137,13 @@ extern "C" {
 size_t tvr_train_work_bytes(const tvr_scene *s, int64_t n_rays, int32_t n_samples, int64_t app_cap)
 {
     if (n_rays <= 0 || n_samples <= 0 || app_cap <= 0) return 0;
+    if (cp_refused(s, __func__) != TVR_OK) return 0;
     return work_layout(n_rays, n_samples, app_cap, s && s->dev.gen).total;           // (a scene with more than two encoding frequencies has the wider X)
 }
 
 int tvr_train_work_describe(const tvr_scene *s, int64_t n_rays, int32_t n_samples, int64_t app_cap, tvr_train_work_layout *out)
 {
+    NOT_CP(s);
     if (!s || !out || n_rays <= 0 || n_samples <= 0 || app_cap <= 0) return fail(TVR_ERR_INVALID, "tvr_train_work_describe: NULL argument or a count <= 0");
     const bool gen = s->dev.gen != 0;
     const WorkLayout W = work_layout(n_rays, n_samples, app_cap, gen);
@@ -1154,6 +1284,7 @@ int tvr_train_backward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
 int tvr_app_h_backward(tvr_scene *s, const float *xyz, int64_t m, const float *dh, size_t dh_bytes, void *grad_scratch, size_t grad_scratch_bytes,
                        const tvr_vm_grads *out, void *stream_)
 {
+    NOT_CP(s);
     if (m > 0) NEED("dh [m,144]", dh_bytes, m, TVR_KAPP);
     return app_h_backward_impl(s, xyz, 3, m, nullptr, dh, grad_scratch, grad_scratch_bytes, out, stream_);
 }
@@ -1352,7 +1483,8 @@ int tvr_density_feature(tvr_scene *s, const float *xyz, int64_t m, float *out, s
     if (!s || !s->params_set) return fail(TVR_ERR_INVALID, "scene is NULL or tvr_scene_update has not run");
     if (m == 0) return TVR_OK;
     if (!xyz || !out || m < 0) return fail(TVR_ERR_INVALID, "xyz/out NULL or m < 0");
-    HIP_TRY(launch_density_feature(s->dev, xyz, m, out, (hipStream_t)stream));
+    if (s->cp) HIP_TRY(launch_cp_density_feature(s->dev, s->cpd, xyz, m, out, (hipStream_t)stream));
+    else HIP_TRY(launch_density_feature(s->dev, xyz, m, out, (hipStream_t)stream));
     return TVR_OK;
 }
 
@@ -1362,6 +1494,10 @@ int tvr_app_feature(tvr_scene *s, const float *xyz, int64_t m, float *out, size_
     if (!s || !s->params_set) return fail(TVR_ERR_INVALID, "scene is NULL or tvr_scene_update has not run");
     if (m == 0) return TVR_OK;
     if (!xyz || !out || m < 0) return fail(TVR_ERR_INVALID, "xyz/out NULL or m < 0");
+    if (s->cp) {
+        HIP_TRY(launch_cp_app_feature(s->dev, s->cpd, xyz, 3, m, nullptr, nullptr, nullptr, out, nullptr, (hipStream_t)stream));
+        return TVR_OK;
+    }
     ShadeArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.n = m;
@@ -1373,6 +1509,7 @@ int tvr_app_feature(tvr_scene *s, const float *xyz, int64_t m, float *out, size_
 
 int tvr_app_feature_ref(tvr_scene *s, const float *xyz, int64_t m, float *features, size_t features_bytes, float *extra, size_t extra_bytes, void *stream)
 {
+    NOT_CP(s);
     if (m > 0) {
         NEED("features [m,27]", features_bytes, m, TVR_APPDIM);
         NEED("extra [m,8]", extra_bytes, m, 8);
@@ -1395,6 +1532,7 @@ int tvr_app_feature_ref(tvr_scene *s, const float *xyz, int64_t m, float *featur
 int tvr_mlp_render_ref(tvr_scene *s, const float *viewdirs, const float *features, const float *dot_product, int64_t m, float *rgb,
                        size_t rgb_bytes, void *stream)
 {
+    NOT_CP(s);
     if (m > 0) NEED("rgb [m,3]", rgb_bytes, m, 3);
     int rc = scene_ready(s);
     if (rc != TVR_OK) return rc;

@@ -30,6 +30,13 @@ struct MarchSampling {
     const float *zv;          // [n_rays,S] or nullptr (NerfPlusPlus.sample_ray, nerfplusplus.py:239-269)
 };
 
+// a CP scene (TensorCP, models/tensoRF.py:317-447) beside its SceneDev: the lines sit where SceneDev has the VM lines (dline[i] / aline[i], line i along axis 2 - i),
+// packed [L+1][rd] / [L+1][ra] fp32 (zero pad texel at index L, zero pad channels); SceneDev itself is unchanged, so no existing kernel's arguments move
+struct CpDev {
+    int rd, ra;               // channels per packed texel: density components rounded up to 16, appearance components rounded up to 4
+    const float4 *basis;      // basis_mat [27, R_app] as [ra / 4][27] float4: entry (g, c) holds columns 4 g .. 4 g + 3 of row c (zero behind R_app)
+};
+
 // packed (channels-last, zero-padded) gradient images of the VM factors, same geometry as the packed scene
 struct TrainGrads {
     float *dplane[3], *dline[3], *aplane[3], *aline[3];
@@ -146,3 +153,15 @@ hipError_t launch_copy_f32(float *dst, const float *src, int n, hipStream_t stre
 hipError_t launch_zero_header(unsigned *counter, hipStream_t stream);
 hipError_t launch_f32_to_f16(const float *in, void *out, long long n, hipStream_t stream);      // n a multiple of 4; round to nearest even
 hipError_t launch_zero_f32(float *p, long long n, hipStream_t stream);
+
+// tvr_cp.hip: the CP field's own kernels.  launch_cp_march has launch_march's contract; launch_cp_app_feature writes features [m,27] for xyz [m, xyz_stride]
+// (m_dev: optional device-side count, m is then the capacity) and, with q_ray / rays given, the entries' view directions dirs [m,3];
+// launch_cp_rgbw carries rgb [cap,3] and the queue's weights into q_out for composite_kernel / scatter_rgb_kernel (and counts the appearance samples into stats)
+hipError_t launch_cp_march(const SceneDev &sc, const CpDev &cp, const float *rays, int n_rays, int S, const MarchSampling &sm, float eps_T, const MarchOut &mo,
+                           const tvr_dense_out *dense, hipStream_t stream);
+hipError_t launch_cp_density_feature(const SceneDev &sc, const CpDev &cp, const float *xyz, long long m, float *out, hipStream_t stream);
+hipError_t launch_cp_app_feature(const SceneDev &sc, const CpDev &cp, const float *xyz, int xyz_stride, long long m, const unsigned *m_dev, const unsigned *q_ray,
+                                 const float *rays, float *feats, float *dirs, hipStream_t stream);
+hipError_t launch_cp_rgbw(const MarchOut &mo, const float *rgb, long long cap, hipStream_t stream);
+hipError_t launch_cp_pack_basis(const float *basis, int r_app, int ra, float4 *out, hipStream_t stream);
+int march_cu_count();

@@ -441,9 +441,9 @@ __global__ __launch_bounds__(SH_THREADS, SH_MINW) void shade_kernel(const SceneD
     // basis hi fragment of lane (e, h) at k-step s: rows 27..31 of the 32-row tile do not exist (their outputs are never used): clamp
     const unsigned char *bashp = smem + BASH + (h * TVR_IMG_BASH_ROWS + (e < TVR_IMG_BASH_ROWS ? e : TVR_IMG_BASH_ROWS - 1)) * 16;
     const unsigned char *baslp = bashp + (BASL - BASH);  // lo parts, same addressing, k-steps 0 .. NLO-1
-    // SRC_QUEUE: the count lives on the device.  SRC_H (training forward): optionally too — a.n is then the capacity of the buffers
+    // SRC_QUEUE: the count lives on the device.  SRC_H (training forward) and SRC_FEAT (the CP render path's staged features): optionally too — a.n is then the capacity of the buffers
     long long n_total = (SRC == SH_SRC_QUEUE) ? (long long)(*a.counter) : a.n;
-    if (SRC == SH_SRC_H && a.counter) n_total = (long long)(*a.counter) < a.n ? (long long)(*a.counter) : a.n;
+    if ((SRC == SH_SRC_H || SRC == SH_SRC_FEAT) && a.counter) n_total = (long long)(*a.counter) < a.n ? (long long)(*a.counter) : a.n;
     const long long n_tiles = (n_total + SH_TILE - 1) / SH_TILE;
     unsigned long long clk0 = 0ull, ref0 = 0ull;              // clock probe (stats only), as in the march kernel
     if (a.stats && SRC == SH_SRC_QUEUE && tid == 0) { clk0 = __builtin_amdgcn_s_memtime(); ref0 = __builtin_amdgcn_s_memrealtime(); }

@@ -265,12 +265,14 @@ class TensorBase(torch.nn.Module):
             pass
 
     _variant = 0                  # tvr_scene_desc.variant
+    _cp = False                   # a CP field (cp.TensorCP): lines only, tvr_cp_scene_packed_bytes / tvr_cp_scene_create
     def _extra_linears(self):     # variant 1: (normal, diffuse, specular, rho) Linear modules
         return []
 
     def _param_list(self):
         m = self.renderModule.mlp
-        ps = (list(self.density_plane) + list(self.density_line) + list(self.app_plane) + list(self.app_line)
+        planes = [] if self._cp else list(self.density_plane) + list(self.app_plane)
+        ps = (planes + list(self.density_line) + list(self.app_line)
               + [self.basis_mat.weight, m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias])
         for lin in self._extra_linears():
             ps += [lin.weight, lin.bias]
@@ -299,8 +301,12 @@ class TensorBase(torch.nn.Module):
             d = L.SceneDesc()
             d.aabb[:] = [float(x) for x in self.aabb.reshape(-1)]
             d.grid[:] = [int(x) for x in self.gridSize]
-            d.density_n_comp[:] = [int(x) for x in self.density_n_comp]
-            d.app_n_comp[:] = [int(x) for x in self.app_n_comp]
+            if self._cp:                                   # one component count per factor (entry [0]; the reference's configs write n_lamb_sigma = [96])
+                d.density_n_comp[:] = [int(self.density_n_comp[0])] * 3
+                d.app_n_comp[:] = [int(self.app_n_comp[0])] * 3
+            else:
+                d.density_n_comp[:] = [int(x) for x in self.density_n_comp]
+                d.app_n_comp[:] = [int(x) for x in self.app_n_comp]
             d.app_dim, d.featureC, d.view_pe, d.fea_pe = self.app_dim, self.featureC, self.view_pe, self.fea_pe
             d.near_, d.far_ = float(self.near_far[0]), float(self.near_far[1])
             d.step_size = float(self.stepSize)
@@ -309,12 +315,14 @@ class TensorBase(torch.nn.Module):
             d.weight_thres = float(self.rayMarch_weight_thres)
             d.fea2dense_act = 0 if self.fea2denseAct == "softplus" else 1
             d.variant = self._variant
-            nbytes = lib.tvr_scene_packed_bytes(C.byref(d))
+            packed_bytes, create = ((lib.tvr_cp_scene_packed_bytes, lib.tvr_cp_scene_create) if self._cp
+                                    else (lib.tvr_scene_packed_bytes, lib.tvr_scene_create))
+            nbytes = packed_bytes(C.byref(d))
             if nbytes == 0:
                 raise L.TvrError("unsupported field configuration: " + lib.tvr_last_error().decode())
             self._packed = L.dev_bytes(nbytes, self.device, what="tvr_scene packed")
             h = C.c_void_p()
-            L.check(lib.tvr_scene_create(C.byref(d), self._packed.data_ptr(), nbytes, C.byref(h)), "tvr_scene_create")
+            L.check(create(C.byref(d), self._packed.data_ptr(), nbytes, C.byref(h)), "tvr_cp_scene_create" if self._cp else "tvr_scene_create")
             self._scene = h
             self._sig = None
             self._alpha_dirty = True
@@ -326,8 +334,9 @@ class TensorBase(torch.nn.Module):
                     raise L.TvrError("field parameters must be contiguous fp32 tensors on the model's device")
             sp = L.SceneParams()
             for i in range(3):
-                sp.density_plane[i], sp.density_line[i] = self.density_plane[i].data_ptr(), self.density_line[i].data_ptr()
-                sp.app_plane[i], sp.app_line[i] = self.app_plane[i].data_ptr(), self.app_line[i].data_ptr()
+                sp.density_line[i], sp.app_line[i] = self.density_line[i].data_ptr(), self.app_line[i].data_ptr()
+                if not self._cp:                       # (a CP scene has no planes: the pointers stay NULL)
+                    sp.density_plane[i], sp.app_plane[i] = self.density_plane[i].data_ptr(), self.app_plane[i].data_ptr()
             m = self.renderModule.mlp
             sp.basis_mat = self.basis_mat.weight.data_ptr()
             sp.W1, sp.b1 = m[0].weight.data_ptr(), m[0].bias.data_ptr()

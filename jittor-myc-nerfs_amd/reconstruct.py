@@ -24,12 +24,14 @@ import numpy as np
 import torch
 
 from .evaluation import BlenderRays, evaluation, evaluation_path
+from .cp import TensorCP
 from .field import TensorVMSplit, load_checkpoint
 from .losses import TVLoss
 from .render import N_to_reso, OctreeRender_trilinear_fast, cal_n_samples
 from .variants import NerfPlusPlus, REFTensoRF
 
-MODELS = {"TensorVMSplit": TensorVMSplit, "REFTensoRF": REFTensoRF, "NerfPlusPlus": NerfPlusPlus}
+MODELS = {"TensorVMSplit": TensorVMSplit, "TensorCP": TensorCP, "REFTensoRF": REFTensoRF, "NerfPlusPlus": NerfPlusPlus}
+RENDER_ONLY_MODELS = ("TensorCP",)       # constructed, loaded and rendered (render_test); their training kernels are not built
 
 
 def parse_config_file(path: str) -> Dict[str, object]:
@@ -157,6 +159,9 @@ def reconstruction(args, device="cuda", log=print, train_dataset=None, val_datas
     """train.py:113-371.  Returns (tensorf, logfolder, PSNRs_test of the last visualisation or final test).
     `train_dataset` / `val_dataset`: ready-made datasets (objects with all_rays, all_rgbs, scene_bbox, white_bg, near_far as BlenderRays has them) instead of the
     Blender folder under args.datadir — synthetic training sets (scripts/reconstruction_timing.py)."""
+    if getattr(args, "model_name", None) in RENDER_ONLY_MODELS:          # before any data is touched
+        raise NotImplementedError(f"model_name {args.model_name!r}: CP training is not built (no backward kernels for the CP march and features yet); "
+                                  "a CP checkpoint renders through --render_only 1 --ckpt ...")
     if args.dataset_name != "blender":
         raise NotImplementedError("only the Blender loader exists in the reference (dataLoader/__init__.py)")
     if args.model_name not in MODELS:

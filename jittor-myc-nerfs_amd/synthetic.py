@@ -1,4 +1,4 @@
-"""Seeded synthetic TensorVMSplit scenes — numpy only, no device code.
+"""Seeded synthetic TensorVMSplit (and, make_cp_scene_arrays, TensorCP) scenes — numpy only, no device code.
 
 The reference's own initialisation (0.1*randn with density_shift=-10, tensoRF.py:148-149) renders
 nothing (softplus(-10) ~ 4.5e-5), so benchmarks and parity tests use a soft opaque blob instead:
@@ -99,6 +99,41 @@ def make_scene_arrays(gridSize: Sequence[int], aabb, seed: int = SEED,
         sf = 30.6 * np.exp(-r2 / (2 * blob_sigma ** 2))
         out["alpha_volume"] = (sf > 0.5).astype(np.float32)    # generous (dilated) occupancy of the blob
         out["alpha_aabb"] = out["aabb"].copy()
+    return out
+
+
+def make_cp_scene_arrays(gridSize: Sequence[int], aabb, r_sigma: int, r_app: int, seed: int = SEED, app_dim: int = 27, featureC: int = 128,
+                         view_pe: int = 2, fea_pe: int = 2, peak: float = 32.0) -> Dict[str, np.ndarray]:
+    """A CP scene (TensorCP, tensoRF.py:317-376) that has surfaces.  A sum of separable Gaussian bumps is exactly rank R: density line i (along axis VEC_MODE[i]),
+    component r, is exp(-((t - c[r, axis]) / w[r, axis])^2) on t = linspace(-1, 1, L), centres in [-0.5, 0.5], widths in 0.25 .. 0.5; the amplitude goes on line 0 and
+    is chosen so that the largest sigma_feature on a 17^3 lattice is `peak` (25 .. 40 against density_shift = -10: opaque cores, soft rims).  Appearance lines are
+    low-frequency cosines plus a little noise, basis_mat ~ 1.5 / sqrt(r_app) * randn; the network arrays are make_scene_arrays' own."""
+    rng = np.random.default_rng(seed)
+    g = [int(x) for x in gridSize]
+    out: Dict[str, np.ndarray] = {"aabb": np.asarray(aabb, np.float32).reshape(2, 3), "gridSize": np.asarray(g, np.int32)}
+    ctr = rng.uniform(-0.5, 0.5, size=(r_sigma, 3))
+    wid = rng.uniform(0.25, 0.5, size=(r_sigma, 3))
+
+    def bumps(t, axis):                                  # [r_sigma, len(t)]
+        return np.exp(-((t[None, :] - ctr[:, axis, None]) / wid[:, axis, None]) ** 2)
+    t17 = np.linspace(-1.0, 1.0, 17)
+    dense = np.einsum("rz,ry,rx->zyx", bumps(t17, 2), bumps(t17, 1), bumps(t17, 0))
+    amp = peak / dense.max()
+    for i in range(3):
+        axis = VEC_MODE[i]
+        ln = bumps(np.linspace(-1.0, 1.0, g[axis]), axis) * (amp if i == 0 else 1.0)
+        out[f"density_line.{i}"] = ln[None, :, :, None].astype(np.float32)
+    for i in range(3):
+        axis = VEC_MODE[i]
+        t = np.linspace(-1.0, 1.0, g[axis])
+        freq, phase = rng.uniform(0.5, 2.0, size=(r_app, 1)), rng.uniform(0.0, 2 * np.pi, size=(r_app, 1))
+        ln = np.cos(np.pi * freq * t[None, :] + phase) + 0.05 * rng.standard_normal((r_app, g[axis]))
+        out[f"app_line.{i}"] = ln[None, :, :, None].astype(np.float32)
+    out["basis_mat"] = (1.5 / np.sqrt(r_app) * rng.standard_normal((app_dim, r_app))).astype(np.float32)
+    net = make_scene_arrays([2, 2, 2], aabb, seed=seed, density_n_comp=(1, 1, 1), appearance_n_comp=(1, 1, 1), app_dim=app_dim, featureC=featureC,
+                            view_pe=view_pe, fea_pe=fea_pe)
+    for k in ("W1", "b1", "W2", "b2", "W3", "b3"):
+        out[k] = net[k]
     return out
 
 
