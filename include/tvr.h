@@ -539,6 +539,31 @@ int tvr_npp_bg_points(const void *rays_o, const void *rays_d, int64_t n_rays, co
                       void *pts, void *z, void *stream);
 int tvr_npp_bg_composite(const void *rgb, const void *sigma, const void *z, int64_t n_rays, int32_t n_samples, void *rgb_out, void *stream);
 
+/* Iso-surface of a dense fp32 volume as an indexed triangle mesh: marching cubes (train.py:41-59 `export_mesh` -> utils.py:146-207, where the reference calls
+ * skimage.measure.marching_cubes on the CPU).  ADDITIVE exports: TVR_VERSION is unchanged.
+ *   volume [dims[0]][dims[1]][dims[2]] fp32, z fastest (TensorBase.getDenseAlpha's layout); a grid point is INSIDE iff value >= level.
+ *   Grid point p = (i * dims[1] + j) * dims[2] + k owns the edges that leave it along +x, +y, +z.  Vertices: one per grid edge whose ends straddle the level, ordered by
+ *   (owner point, axis x < y < z) — the mesh is indexed and welded by construction; for end values a (owner) and b: t = (level - a) / (b - a), voxel coordinate = index + t,
+ *   world = origin + coordinate * spacing (fp32, each operation rounded on its own).  Triangles: ordered by cell (the point at the cell's minimum corner), then by the case
+ *   table's order (csrc/tvr_mc_table.h, generated by scripts/gen_mc_table.py); normals (right-hand rule) point from inside to outside, flip != 0 reverses each triangle.
+ *   The output is a function of the arguments alone: bit-identical from run to run.
+ * Two steps, because the sizes of the outputs are results:
+ *   tvr_mesh_count fills `scratch` (tvr_mesh_scratch_bytes(dims), 256-byte aligned) and leaves {n_vertices, n_triangles} in counts_dev[2]; the caller reads them once,
+ *   allocates verts [n_vertices,3] fp32 and faces [n_triangles,3] int32, and calls
+ *   tvr_mesh_emit with the SAME volume, dims, level and scratch.  n_vertices / n_triangles are the capacities of the two outputs: no store happens at or beyond them whatever
+ *   volume and scratch hold, and if they are not the counted totals *fault_flag_dev becomes 1 and nothing is written (the flag is only ever set; the caller zeroes it).
+ *   Zero vertices / triangles is a valid result (verts / faces may then be NULL).
+ * Errors, all before any launch: TVR_ERR_INVALID for a NULL pointer, a dimension below 2, a scratch / output buffer smaller than stated above or a misaligned scratch, counts
+ *   outside 0 .. 3 points / 5 points; TVR_ERR_UNSUPPORTED for 3 * points >= 2^31 (indices are int32).  tvr_mesh_scratch_bytes returns 0 for such dims.
+ * The scan is reduce / scan / add over tiles of TVR_MESH_TILE points; one workgroup walks the tile sums TVR_MESH_SCAN_CHUNK at a time (no workgroup waits for another). */
+#define TVR_MESH_TILE 1024
+#define TVR_MESH_SCAN_CHUNK 256
+size_t tvr_mesh_scratch_bytes(const int32_t dims[3]);
+int tvr_mesh_count(const float *volume, const int32_t dims[3], float level, void *scratch, size_t scratch_bytes, int64_t *counts_dev, void *stream);
+int tvr_mesh_emit(const float *volume, const int32_t dims[3], float level, const float origin[3], const float spacing[3], const void *scratch, size_t scratch_bytes,
+                  float *verts, size_t verts_bytes, int64_t n_vertices, int32_t *faces, size_t faces_bytes, int64_t n_triangles, int32_t flip,
+                  uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

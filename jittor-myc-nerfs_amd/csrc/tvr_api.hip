@@ -1648,3 +1648,65 @@ int tvr_profile_destroy(tvr_profile *p)
 }
 
 }  // extern "C"
+
+// ---- marching cubes (tvr_mesh.hip) --------------------------------------------------------------------------------------------------------------------------
+// dims -> points, or a negative status with the message set
+static int mesh_points(const char *fn, const int32_t dims[3], long long *points)
+{
+    if (!dims) return fail(TVR_ERR_INVALID, "%s: dims is NULL", fn);
+    for (int a = 0; a < 3; ++a)
+        if (dims[a] < 2) return fail(TVR_ERR_INVALID, "%s: dims[%d] = %d, a volume needs at least 2 points along every axis", fn, a, dims[a]);
+    const long long n = (long long)dims[0] * dims[1] * dims[2];
+    if (3 * n >= (1ll << 31))
+        return fail(TVR_ERR_UNSUPPORTED, "%s: %lld points: vertex indices are int32 and 3 * points must stay below 2^31", fn, n);
+    *points = n;
+    return TVR_OK;
+}
+
+size_t tvr_mesh_scratch_bytes(const int32_t dims[3])
+{
+    long long n;
+    if (mesh_points(__func__, dims, &n) != TVR_OK) return 0;
+    return mesh_scratch_bytes(n);
+}
+
+static int mesh_scratch_check(const char *fn, const void *scratch, size_t scratch_bytes, long long n)
+{
+    if (!scratch) return fail(TVR_ERR_INVALID, "%s: scratch is NULL", fn);
+    if ((uintptr_t)scratch % 256) return fail(TVR_ERR_INVALID, "%s: scratch is not 256-byte aligned", fn);
+    if (scratch_bytes < mesh_scratch_bytes(n))
+        return fail(TVR_ERR_INVALID, "%s: scratch holds %zu B, tvr_mesh_scratch_bytes asks for %zu B", fn, scratch_bytes, mesh_scratch_bytes(n));
+    return TVR_OK;
+}
+
+int tvr_mesh_count(const float *volume, const int32_t dims[3], float level, void *scratch, size_t scratch_bytes, int64_t *counts_dev, void *stream)
+{
+    long long n;
+    int rc = mesh_points(__func__, dims, &n);
+    if (rc != TVR_OK) return rc;
+    if (!volume || !counts_dev) return fail(TVR_ERR_INVALID, "%s: volume / counts_dev is NULL", __func__);
+    if ((rc = mesh_scratch_check(__func__, scratch, scratch_bytes, n)) != TVR_OK) return rc;
+    HIP_TRY(launch_mesh_count(volume, dims, level, mesh_carve(n, scratch), (long long *)counts_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_emit(const float *volume, const int32_t dims[3], float level, const float origin[3], const float spacing[3], const void *scratch, size_t scratch_bytes,
+                  float *verts, size_t verts_bytes, int64_t n_vertices, int32_t *faces, size_t faces_bytes, int64_t n_triangles, int32_t flip,
+                  uint32_t *fault_flag_dev, void *stream)
+{
+    long long n;
+    int rc = mesh_points(__func__, dims, &n);
+    if (rc != TVR_OK) return rc;
+    if (!volume || !origin || !spacing || !fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: volume / origin / spacing / fault_flag_dev is NULL", __func__);
+    if ((rc = mesh_scratch_check(__func__, scratch, scratch_bytes, n)) != TVR_OK) return rc;
+    if (n_vertices < 0 || n_vertices > 3 * n || n_triangles < 0 || n_triangles > 5 * n)
+        return fail(TVR_ERR_INVALID, "%s: n_vertices %lld / n_triangles %lld outside 0 .. 3 / 5 x %lld points", __func__, (long long)n_vertices, (long long)n_triangles, n);
+    if ((n_vertices && !verts) || (n_triangles && !faces)) return fail(TVR_ERR_INVALID, "%s: verts / faces is NULL", __func__);
+    if (verts_bytes < (size_t)n_vertices * 3 * sizeof(float))
+        return fail(TVR_ERR_INVALID, "%s: verts holds %zu B, %lld vertices x 3 fp32 need %zu B", __func__, verts_bytes, (long long)n_vertices, (size_t)n_vertices * 12);
+    if (faces_bytes < (size_t)n_triangles * 3 * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: faces holds %zu B, %lld triangles x 3 int32 need %zu B", __func__, faces_bytes, (long long)n_triangles, (size_t)n_triangles * 12);
+    HIP_TRY(launch_mesh_emit(volume, dims, level, origin, spacing, mesh_carve(n, const_cast<void *>(scratch)), verts, n_vertices, faces, n_triangles, flip, fault_flag_dev,
+                             (hipStream_t)stream));
+    return TVR_OK;
+}

@@ -165,3 +165,20 @@ hipError_t launch_cp_app_feature(const SceneDev &sc, const CpDev &cp, const floa
 hipError_t launch_cp_rgbw(const MarchOut &mo, const float *rgb, long long cap, hipStream_t stream);
 hipError_t launch_cp_pack_basis(const float *basis, int r_app, int ra, float4 *out, hipStream_t stream);
 int march_cu_count();
+
+// tvr_mesh.hip: marching cubes over a dense fp32 volume [nx][ny][nz] (z fastest).  The scratch buffer carved for a volume of `points` grid points: a header with the
+// totals, per tile of TVR_MESH_TILE points its base (vertices | triangles << 32), per point one count byte and the two exclusive bases (arrays padded to whole tiles)
+struct MeshScratch {
+    unsigned long long *totals, *tile_base;
+    unsigned char *cnt8;
+    unsigned *vbase, *tbase;
+    unsigned n_tiles;
+    size_t total;
+};
+MeshScratch mesh_carve(long long points, void *scratch);
+size_t mesh_scratch_bytes(long long points);
+// count + scan: fills the scratch, leaves {vertices, triangles} in counts_dev[2]
+hipError_t launch_mesh_count(const float *vol, const int dims[3], float level, const MeshScratch &s, long long *counts_dev, hipStream_t stream);
+// emit from a filled scratch; n_vertices / n_triangles are the capacities of verts / faces AND must equal the counted totals, else *fault = 1 and nothing is written
+hipError_t launch_mesh_emit(const float *vol, const int dims[3], float level, const float origin[3], const float spacing[3], const MeshScratch &s, float *verts,
+                            long long n_vertices, int *faces, long long n_triangles, int flip, unsigned *fault, hipStream_t stream);

@@ -836,6 +836,30 @@ class TensorBase(torch.nn.Module):
         return alpha, dense_xyz
 
     @torch.no_grad()
+    def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False):
+        """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
+        (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
+
+        spacing: where the N = gridSize samples of an axis are taken to sit between aabb[0] and aabb[1]
+          * "reference" — utils.py:166-179 exactly: voxel size = extent / N, origin aabb[0].  The samples were taken at extent / (N - 1) (getDenseAlpha's linspace), so
+            this convention shrinks the mesh by (N - 1) / N towards aabb[0] against the sampled positions;
+          * "samples" — voxel size = extent / (N - 1): vertices lie where the field was sampled.
+        flip: reverse every triangle.  Normals point out of the dense region (mesh.py); the reference reverses skimage's order, which cannot be compared here."""
+        from . import mesh
+        alpha, _ = self.getDenseAlpha(gridSize)
+        aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
+        n = torch.tensor([float(s) for s in alpha.shape], dtype=torch.float32, device=alpha.device)
+        if spacing == "reference":
+            voxel = (aabb[1] - aabb[0]) / n
+        elif spacing == "samples":
+            voxel = (aabb[1] - aabb[0]) / (n - 1)
+        else:
+            raise ValueError(f"spacing {spacing!r}: 'reference' or 'samples'")
+        verts, faces = mesh.marching_cubes(alpha, level, spacing=voxel.tolist(), origin=aabb[0].tolist(), flip=flip)
+        mesh.write_ply(path, verts, faces)
+        return verts, faces
+
+    @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):                                      # :385-409
         gridSize = [int(g) for g in gridSize]
         alpha, dense_xyz = self.getDenseAlpha(gridSize)

@@ -1,0 +1,127 @@
+"""Iso-surface extraction and the PLY file behind `--export_mesh 1` (reference tensorf-myc/utils.py:146-207 `convert_sdf_samples_to_ply`, which calls
+skimage.measure.marching_cubes and plyfile on the CPU).  Here the extraction is the HIP marching cubes of csrc/tvr_mesh.hip (include/tvr.h tvr_mesh_*,
+DESIGN.md §4.10) and the PLY reader / writer is numpy.  There is no CPU fallback for the extraction: a CPU tensor raises TvrError like every other product path.
+
+Orientation: triangle normals (right-hand rule) point from `>= level` to `< level`, i.e. out of the dense region.  The reference reverses the vertex order
+skimage returns (utils.py:171); whether that equals this orientation cannot be checked without skimage, hence `flip`."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .autograd_ops import _stream_ptr
+
+MESH_TILE = 1024            # include/tvr.h TVR_MESH_TILE: points per scan tile
+MESH_SCAN_CHUNK = 256       # include/tvr.h TVR_MESH_SCAN_CHUNK: tile sums per step of the one workgroup that scans them
+
+
+def _volume_on_device(volume) -> torch.Tensor:
+    if not torch.is_tensor(volume) or volume.device.type != "cuda":
+        where = volume.device if torch.is_tensor(volume) else type(volume).__name__
+        raise L.TvrError(f"marching_cubes runs on an MI355X (HIP) device only; the volume is on {where}. There is no CPU fallback.")
+    if volume.dim() != 3:
+        raise L.TvrError(f"marching_cubes takes a volume [nx, ny, nz]; got shape {tuple(volume.shape)}")
+    return volume.detach().to(torch.float32).contiguous()
+
+
+def _dims(volume):
+    return (C.c_int32 * 3)(*[int(s) for s in volume.shape])
+
+
+def mesh_count(volume: torch.Tensor, level: float):
+    """First step (tvr_mesh_count): (volume as passed to the library, filled scratch buffer, n_vertices, n_triangles).  Reads the two totals from the device once."""
+    vol = _volume_on_device(volume)
+    lib, dims = L.lib(), _dims(vol)
+    nbytes = lib.tvr_mesh_scratch_bytes(dims)
+    if nbytes == 0:
+        raise L.TvrError("marching_cubes: " + lib.tvr_last_error().decode(errors="replace"))
+    scratch = L.dev_bytes(nbytes, vol.device, what="mesh scratch")
+    counts = L.dev_empty((2,), torch.int64, vol.device, what="mesh counts")
+    L.check(lib.tvr_mesh_count(vol.data_ptr(), dims, float(level), scratch.data_ptr(), L.nbytes(scratch), counts.data_ptr(), _stream_ptr(vol.device)), "tvr_mesh_count")
+    n_vertices, n_triangles = (int(x) for x in counts.cpu().tolist())
+    return vol, scratch, n_vertices, n_triangles
+
+
+def mesh_emit(vol: torch.Tensor, level: float, scratch: torch.Tensor, n_vertices: int, n_triangles: int, spacing=(1, 1, 1), origin=(0, 0, 0), flip: bool = False):
+    """Second step (tvr_mesh_emit) into buffers of exactly the declared counts: (verts [V,3] float32, faces [F,3] int32, fault flag [1] int32 on the device).
+    Counts that are not the ones mesh_count found raise the flag and leave the buffers unwritten."""
+    lib, dims = L.lib(), _dims(vol)
+    verts = L.dev_empty((int(n_vertices), 3), torch.float32, vol.device, what="mesh verts")
+    faces = L.dev_empty((int(n_triangles), 3), torch.int32, vol.device, what="mesh faces")
+    flag = L.dev_bytes(4, vol.device, zero=True, what="mesh fault flag").view(torch.int32)
+    org, sp = (C.c_float * 3)(*[float(x) for x in origin]), (C.c_float * 3)(*[float(x) for x in spacing])
+    L.check(lib.tvr_mesh_emit(vol.data_ptr(), dims, float(level), org, sp, scratch.data_ptr(), L.nbytes(scratch), verts.data_ptr() if n_vertices else None,
+                              L.nbytes(verts), int(n_vertices), faces.data_ptr() if n_triangles else None, L.nbytes(faces), int(n_triangles), 1 if flip else 0,
+                              flag.data_ptr(), _stream_ptr(vol.device)), "tvr_mesh_emit")
+    return verts, faces, flag
+
+
+def marching_cubes(volume: torch.Tensor, level: float, spacing=(1, 1, 1), origin=(0, 0, 0), flip: bool = False):
+    """Iso-surface `volume == level` of a dense fp32 device volume [nx, ny, nz] -> (verts [V,3] float32, faces [F,3] int32), both on the volume's device.
+
+    A grid point is inside iff value >= level.  One vertex per grid edge whose ends straddle the level, at `origin + (index + t) * spacing` with
+    t = (level - a) / (b - a) along the edge; vertices are ordered by (owner grid point, axis), triangles by cell — the result is indexed, welded and the same
+    bit for bit on every run.  Normals point from inside to outside; `flip=True` reverses every triangle.  An empty surface gives empty tensors."""
+    vol, scratch, n_vertices, n_triangles = mesh_count(volume, level)
+    verts, faces, flag = mesh_emit(vol, level, scratch, n_vertices, n_triangles, spacing, origin, flip)
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_emit raised its fault flag: the counted totals and the declared capacities disagree (include/tvr.h)")
+    return verts, faces
+
+
+# ---- PLY: the subset plyfile writes for the reference (utils.py:192-207) -----------------------------------------------------------------------------------
+_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def ply_header(n_vertices: int, n_faces: int) -> bytes:
+    return (f"ply\nformat binary_little_endian 1.0\nelement vertex {int(n_vertices)}\nproperty float x\nproperty float y\nproperty float z\n"
+            f"element face {int(n_faces)}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
+
+
+def _host(a, dtype):
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a).reshape(-1, 3), dtype=dtype)
+
+
+def write_ply(path, verts, faces) -> None:
+    """Binary little-endian PLY with the two elements the reference writes through plyfile: `vertex` (float x, y, z) and `face`
+    (property list uchar int vertex_indices, three indices per face).  verts [V,3], faces [F,3]: tensors (any device) or arrays."""
+    v, f = _host(verts, "<f4"), _host(faces, "<i4")
+    rows = np.empty(len(f), dtype=_FACE_DTYPE)
+    rows["n"] = 3
+    rows["v"] = f
+    with open(path, "wb") as out:
+        out.write(ply_header(len(v), len(f)))
+        out.write(v.tobytes())
+        out.write(rows.tobytes())
+
+
+def read_ply(path):
+    """Reads back what write_ply writes: (verts [V,3] float32, faces [F,3] int32) as numpy arrays.  Anything outside that subset is a ValueError."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    counts = {}
+    for line in lines:
+        tok = line.split()
+        if tok[:1] == ["element"]:
+            counts[tok[1]] = int(tok[2])
+    if set(counts) != {"vertex", "face"} or data[:end + len(b"end_header\n")] != ply_header(counts["vertex"], counts["face"]):
+        raise ValueError(f"{path}: only binary little-endian PLY with float x y z vertices and uchar/int triangle lists is read")
+    nv, nf = counts["vertex"], counts["face"]
+    if len(body) != nv * _VERTEX_DTYPE.itemsize + nf * _FACE_DTYPE.itemsize:
+        raise ValueError(f"{path}: body of {len(body)} B does not hold {nv} vertices and {nf} triangles")
+    v = np.frombuffer(body, dtype="<f4", count=nv * 3).reshape(nv, 3).astype(np.float32)
+    rows = np.frombuffer(body, dtype=_FACE_DTYPE, count=nf, offset=nv * _VERTEX_DTYPE.itemsize)
+    if nf and not (rows["n"] == 3).all():
+        raise ValueError(f"{path}: a face is not a triangle")
+    return v, rows["v"].astype(np.int32).reshape(nf, 3)

@@ -1,13 +1,15 @@
 """The callers of the render path in the reference's own shape (tensorf-myc/train.py, tensorf-myc/opt.py): option parser for the shipped
-`configs/*.txt` files, `reconstruction` (train.py:113-371) and `render_test` (train.py:62-110), on the HIP field and renderer.
+`configs/*.txt` files, `reconstruction` (train.py:113-371) `render_test` (train.py:62-110) and `export_mesh` (train.py:41-59), on the HIP field and renderer.
 
     python -m jittor_myc_nerfs_amd.reconstruct --config configs/Scar.txt [--datadir ...]
 
 What differs from the reference, on purpose:
   * the optimizer is torch.optim.Adam (fused); the per-group lr decay, the lr reset after upsampling, the regulariser schedule and the
     checkpoint contents (`kwargs`, `state_dict`, packed alpha mask, `lr`, `global_step`) are the reference's;
-  * no TensorBoard writer, no `export_mesh` (skimage / plyfile are not available here), no `ndc_ray` datasets (the reference ships only
-    the Blender loader); `set_nerfplusplus` is called for NerfPlusPlus only (train.py:172 calls it unconditionally and fails for the others);
+  * no TensorBoard writer, no `ndc_ray` datasets (the reference ships only the Blender loader); `set_nerfplusplus` is called for NerfPlusPlus only
+    (train.py:172 calls it unconditionally and fails for the others);
+  * `--export_mesh 1` (train.py:41-59) extracts the surface with the HIP marching cubes (mesh.py) instead of skimage and writes the PLY without plyfile; the
+    level and the grid are options (`mesh_level`, `mesh_grid`), and the command ends after the export instead of falling through into a training run;
   * progress is a plain print every `progress_refresh_rate` iterations.
 Host-side plumbing only: every pixel comes from the HIP kernels through `OctreeRender_trilinear_fast`.
 """
@@ -76,7 +78,10 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--dataset_name", type=str, default="blender", choices=["blender", "llff", "nsvf", "dtu", "tankstemple", "own_data"])
     for name in ("with_depth", "lindisp", "white_bkgd"):
         p.add_argument("--" + name, action="store_true")
-    for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int)):
+    # (not reference options) export_mesh: the iso-level train.py:59 hard-codes (its comment: 0.005 for Scarf, 0.0005 for Coffee) and an optional [nx, ny, nz] grid for the
+    # dense alpha volume (default: the checkpoint's gridSize, as the reference)
+    p.add_argument("--mesh_level", type=float, default=0.0005)
+    for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int), ("mesh_grid", int)):
         p.add_argument("--" + name, type=typ, action="append")
     argv = sys.argv[1:] if cmd is None else list(cmd)
     pre, _ = p.parse_known_args(argv)
@@ -150,6 +155,24 @@ def render_test(args, device="cuda"):
                                       f"{logfolder}/imgs_path_all/", N_vis=-1, N_samples=-1, white_bg=test_dataset.white_bg, ndc_ray=args.ndc_ray,
                                       device=device)
     return out
+
+
+@torch.no_grad()
+def export_mesh(args, device="cuda"):
+    """train.py:41-59: the checkpoint's field -> getDenseAlpha -> iso-surface at `mesh_level` -> `<ckpt minus .th>.ply` (TensorBase.export_mesh: the reference's
+    voxel-size convention, utils.py:166-179).  Returns the path written.
+    Departure from the reference: train.py:402-409 calls export_mesh and then FALLS THROUGH into render_test or a full reconstruction; here main() returns after the
+    export unless `--render_only 1` with a render flag asks for the renders as well."""
+    if not args.ckpt or not os.path.exists(args.ckpt):
+        raise FileNotFoundError(f"export_mesh needs a checkpoint: --ckpt {args.ckpt!r} does not exist")
+    grid = list(args.mesh_grid) if getattr(args, "mesh_grid", None) else None
+    if grid is not None and len(grid) != 3:
+        raise ValueError(f"mesh_grid takes three sizes [nx, ny, nz]; got {grid}")
+    tensorf, _ = _build_from_ckpt(args, load_checkpoint(args.ckpt), device)
+    path = f"{args.ckpt[:-3]}.ply"
+    verts, faces = tensorf.export_mesh(path, level=getattr(args, "mesh_level", 0.0005), gridSize=grid)
+    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles)")
+    return path
 
 
 FAULT_POLL_EVERY = 16        # iterations between two reads of the training-fault accumulator (field.check_training_faults)
@@ -323,7 +346,9 @@ def main(cmd: Optional[List[str]] = None):
     np.random.seed(20211202)
     args = config_parser(cmd)
     if args.export_mesh:
-        raise NotImplementedError("export_mesh needs skimage.measure.marching_cubes and plyfile (utils.py:146), neither available here")
+        path = export_mesh(args)
+        if not (args.render_only and (args.render_test or args.render_path)):
+            return path
     if args.render_only and (args.render_test or args.render_path):
         return render_test(args)
     return reconstruction(args)
