@@ -123,7 +123,7 @@ int tvr_scene_update(tvr_scene *scene, const tvr_scene_params *params, void *str
  * W1 .. b3; the plane pointers are ignored and may be NULL.
  * ACCEPT a CP scene: tvr_scene_update / _touch / _destroy, tvr_scene_set_alpha, tvr_scene_set_range_check, tvr_scene_set / get_render_pieces, tvr_render_scratch_bytes(_min)
  * (a CP render stages features, direction and colour per queue entry: 132 B more per entry than a VM scene, and that is what the two queries report), tvr_render (dense,
- * stats, jitter, eps_T, prof and pieces as ever; no host read), tvr_density_feature, tvr_app_feature, tvr_mlp_render, tvr_filter_rays.
+ * stats, jitter, eps_T, prof and pieces as ever; no host read), tvr_density_feature, tvr_density_gradient, tvr_app_feature, tvr_mlp_render, tvr_filter_rays.
  * REFUSE it with TVR_ERR_UNSUPPORTED before any launch (the message says "CP"): tvr_render_z and every *_ref call, tvr_march_forward(_z) / _backward(_z), tvr_app_h_forward /
  * _backward, tvr_grad_scratch_bytes and tvr_train_work_bytes (they return 0), tvr_mlp_train_forward, tvr_train_forward / _backward, tvr_train_work_describe,
  * tvr_scene_set_arith with a mode other than TVR_ARITH_F32, tvr_scene_validate_arith: CP scenes are inference-only and compute in the default arithmetic.
@@ -238,6 +238,18 @@ int tvr_render_z(tvr_scene *scene, const float *rays, int64_t n_rays, int32_t n_
 
 /* TensorVMSplit.compute_densityfeature (tensoRF.py:209-225): xyz_norm [m,3] -> out [m]. */
 int tvr_density_feature(tvr_scene *scene, const float *xyz_norm, int64_t m, float *out, size_t out_bytes, void *stream);
+/* The spatial gradient of tvr_density_feature's value f as a symmetric difference (the reference has no counterpart; a surface normal is -grad / |grad|):
+ *   grad[i][k] = (f(p_i + h_k e_k) - f(p_i - h_k e_k)) * (0.5 / h_k),   k = x, y, z in the order of xyz_norm, h_k = half_width[k] in normalised-coordinate units.
+ * f is exactly tvr_density_feature's: arbitrary coordinates, align_corners = True, zeros padding.  The shifted coordinate p +- h, the difference and the product with
+ * 0.5 / h_k are separately rounded fp32, and every f is evaluated by tvr_density_feature's own expressions in its order: sigma_feature [m] (or NULL) receives f(p_i)
+ * bit-equal to tvr_density_feature, and grad is bit-equal to the same quotient of tvr_density_feature at the shifted points — from ONE kernel that evaluates each
+ * factor only where the shift moves it (VM: a term's plane at 5 positions and its line at 3 instead of 7 + 7; CP: each line at 3 instead of 7).
+ * Not the analytic derivative of the interpolant: that one is one-sided and jumps across grid lines, which is where marching-cubes vertices lie; the symmetric
+ * difference is defined and continuous everywhere.  VM scenes of every variant and CP scenes are accepted.
+ * Errors, all before any launch: TVR_ERR_SCRATCH for grad_bytes < m * 12 or (sigma_feature given) sigma_bytes < m * 4; TVR_ERR_INVALID for a NULL scene / xyz_norm /
+ * half_width / grad, m < 0, or a half width that is not finite and > 0.  m == 0 succeeds and launches nothing. */
+int tvr_density_gradient(tvr_scene *scene, const float *xyz_norm, int64_t m, const float half_width[3], float *sigma_feature /* [m] or NULL */, size_t sigma_bytes,
+                         float *grad /* [m,3] */, size_t grad_bytes, void *stream);
 /* TensorVMSplit.compute_appfeature (tensoRF.py:228-244): xyz_norm [m,3] -> out [m,app_dim]. */
 int tvr_app_feature(tvr_scene *scene, const float *xyz_norm, int64_t m, float *out, size_t out_bytes, void *stream);
 /* MLPRender_Fea.execute (tensorBase.py:76-86): viewdirs [m,3], features [m,app_dim] -> rgb [m,3]. */

@@ -1488,6 +1488,28 @@ int tvr_density_feature(tvr_scene *s, const float *xyz, int64_t m, float *out, s
     return TVR_OK;
 }
 
+int tvr_density_gradient(tvr_scene *s, const float *xyz, int64_t m, const float half_width[3], float *sigma_feature, size_t sigma_bytes, float *grad, size_t grad_bytes,
+                         void *stream)
+{
+    if (m > 0) {
+        NEED("grad [m,3]", grad_bytes, m, 3);
+        if (sigma_feature) NEED("sigma_feature [m]", sigma_bytes, m, 1);
+    }
+    if (!s || !s->params_set) return fail(TVR_ERR_INVALID, "scene is NULL or tvr_scene_update has not run");
+    if (!half_width) return fail(TVR_ERR_INVALID, "half_width is NULL");
+    float inv2h[3];
+    for (int k = 0; k < 3; ++k) {
+        if (!(half_width[k] > 0.0f) || !(half_width[k] <= 3.4028234664e38f)) return fail(TVR_ERR_INVALID, "half_width[%d] = %g must be finite and > 0", k, half_width[k]);
+        inv2h[k] = 0.5f / half_width[k];
+    }
+    if (m == 0) return TVR_OK;
+    if (!xyz || !grad || m < 0) return fail(TVR_ERR_INVALID, "xyz/grad NULL or m < 0");
+    if (m >= (1ll << 38)) return fail(TVR_ERR_INVALID, "m = %lld: at most 2^38 - 1 points per call", (long long)m);
+    if (s->cp) HIP_TRY(launch_cp_density_gradient(s->dev, s->cpd, xyz, m, half_width, inv2h, sigma_feature, grad, (hipStream_t)stream));
+    else HIP_TRY(launch_density_gradient(s->dev, xyz, m, half_width, inv2h, sigma_feature, grad, (hipStream_t)stream));
+    return TVR_OK;
+}
+
 int tvr_app_feature(tvr_scene *s, const float *xyz, int64_t m, float *out, size_t out_bytes, void *stream)
 {
     if (m > 0) NEED("out [m,27]", out_bytes, m, TVR_APPDIM);

@@ -89,6 +89,56 @@ hipError_t launch_cp_density_feature(const SceneDev &sc, const CpDev &cp, const 
     return hipGetLastError();
 }
 
+// ---- b'. tvr_density_gradient on a CP scene: one lane per point -------------------------------------------------------------------------------------------
+//   grad[k] = (f(p + h_k e_k) - f(p - h_k e_k)) * (0.5 / h_k),  f = cp_density_feature_kernel's value.  A shift along an axis moves one of the three line factors:
+// each line is interpolated at {centre, +h, -h} (18 float4 taps per group of four components where seven calls of the kernel above read 42) and the seven
+// products are formed and summed in that kernel's order, so the centre is bit-equal to it and the quotient is the one of its values at the shifted points.
+__device__ __forceinline__ float4 cp_lerp4(const float4 *__restrict__ line, const CpTap t, int tpt, int g)
+{
+    return f4_fma(t.w, line[(size_t)t.i1 * tpt + g], f4_mul(t.u, line[(size_t)t.i0 * tpt + g]));
+}
+__device__ __forceinline__ float cp_dot4(float4 a, float4 b, float4 c)
+{
+    const float t0 = (a.x * b.x) * c.x, t1 = (a.y * b.y) * c.y, t2 = (a.z * b.z) * c.z, t3 = (a.w * b.w) * c.w;
+    return (t0 + t1) + (t2 + t3);
+}
+
+__global__ __launch_bounds__(256) void cp_density_gradient_kernel(const SceneDev sc, const CpDev cp, const float *__restrict__ xyz, const long long m, const float3 h,
+                                                                  const float3 inv2h, float *__restrict__ sigma_feature, float *__restrict__ grad)
+{
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= m) return;
+    const float px = xyz[s * 3], py = xyz[s * 3 + 1], pz = xyz[s * 3 + 2];
+    // [0] centre, [1] +h, [2] -h
+    const CpTap tx[3] = {cp_tap(px, sc.gm1[0], sc.grid[0]), cp_tap(px + h.x, sc.gm1[0], sc.grid[0]), cp_tap(px - h.x, sc.gm1[0], sc.grid[0])};
+    const CpTap ty[3] = {cp_tap(py, sc.gm1[1], sc.grid[1]), cp_tap(py + h.y, sc.gm1[1], sc.grid[1]), cp_tap(py - h.y, sc.gm1[1], sc.grid[1])};
+    const CpTap tz[3] = {cp_tap(pz, sc.gm1[2], sc.grid[2]), cp_tap(pz + h.z, sc.gm1[2], sc.grid[2]), cp_tap(pz - h.z, sc.gm1[2], sc.grid[2])};
+    const int tpt = cp.rd >> 2;
+    float fc = 0.0f, fxp = 0.0f, fxm = 0.0f, fyp = 0.0f, fym = 0.0f, fzp = 0.0f, fzm = 0.0f;
+    for (int g = 0; g < tpt; ++g) {
+        const float4 a = cp_lerp4(sc.dline[0], tz[0], tpt, g), b = cp_lerp4(sc.dline[1], ty[0], tpt, g), c = cp_lerp4(sc.dline[2], tx[0], tpt, g);
+        fc = fc + cp_dot4(a, b, c);
+        fxp = fxp + cp_dot4(a, b, cp_lerp4(sc.dline[2], tx[1], tpt, g));
+        fxm = fxm + cp_dot4(a, b, cp_lerp4(sc.dline[2], tx[2], tpt, g));
+        fyp = fyp + cp_dot4(a, cp_lerp4(sc.dline[1], ty[1], tpt, g), c);
+        fym = fym + cp_dot4(a, cp_lerp4(sc.dline[1], ty[2], tpt, g), c);
+        fzp = fzp + cp_dot4(cp_lerp4(sc.dline[0], tz[1], tpt, g), b, c);
+        fzm = fzm + cp_dot4(cp_lerp4(sc.dline[0], tz[2], tpt, g), b, c);
+    }
+    if (sigma_feature) sigma_feature[s] = fc;
+    grad[s * 3 + 0] = (fxp - fxm) * inv2h.x;
+    grad[s * 3 + 1] = (fyp - fym) * inv2h.y;
+    grad[s * 3 + 2] = (fzp - fzm) * inv2h.z;
+}
+
+hipError_t launch_cp_density_gradient(const SceneDev &sc, const CpDev &cp, const float *xyz, long long m, const float h[3], const float inv2h[3], float *sigma_feature,
+                                      float *grad, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cp_density_gradient_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, sc, cp, xyz, m, make_float3(h[0], h[1], h[2]),
+                       make_float3(inv2h[0], inv2h[1], inv2h[2]), sigma_feature, grad);
+    return hipGetLastError();
+}
+
 // ---- c. appearance features: entries in, features [., 27] out ---------------------------------------------------------------------------------------------
 // One lane per entry.  Per group of four components: 6 float4 taps (3 lines x 2), 12 interpolation ops, 8 products, then 27 x 4 fp32 FMAs against the basis group,
 // whose address is the same in every lane (scalar loads).  fp32 throughout: nothing passes through fp16 here; the range rule of tvr.h applies where the features

@@ -69,6 +69,9 @@ hipError_t launch_march(const SceneDev &sc, const float *rays, int n_rays, int S
 hipError_t launch_composite(const MarchOut &mo, int n_rays, int white_bg, float *rgb, hipStream_t stream);
 hipError_t launch_scatter_rgb(const MarchOut &mo, int S, float *rgb_dense, hipStream_t stream);
 hipError_t launch_density_feature(const SceneDev &sc, const float *xyz, long long m, float *out, hipStream_t stream);
+// symmetric-difference gradient of launch_density_feature's value: grad [m,3] = (f(p + h e_k) - f(p - h e_k)) * inv2h[k]; sigma_feature [m] or nullptr receives f(p)
+hipError_t launch_density_gradient(const SceneDev &sc, const float *xyz, long long m, const float h[3], const float inv2h[3], float *sigma_feature, float *grad,
+                                   hipStream_t stream);
 hipError_t launch_alpha_sample(const SceneDev &sc, const float *xyz, long long m, float *out, hipStream_t stream);
 hipError_t launch_shade(const SceneDev &sc, int src, int dst, const ShadeArgs &a, hipStream_t stream);
 // tvr_shade16.hip: the render path (queue -> queue, TensorVMSplit, default arithmetic, at most two encoding frequencies) on 16x16x32 tiles, and its fragment images
@@ -160,6 +163,8 @@ hipError_t launch_zero_f32(float *p, long long n, hipStream_t stream);
 hipError_t launch_cp_march(const SceneDev &sc, const CpDev &cp, const float *rays, int n_rays, int S, const MarchSampling &sm, float eps_T, const MarchOut &mo,
                            const tvr_dense_out *dense, hipStream_t stream);
 hipError_t launch_cp_density_feature(const SceneDev &sc, const CpDev &cp, const float *xyz, long long m, float *out, hipStream_t stream);
+hipError_t launch_cp_density_gradient(const SceneDev &sc, const CpDev &cp, const float *xyz, long long m, const float h[3], const float inv2h[3], float *sigma_feature,
+                                      float *grad, hipStream_t stream);
 hipError_t launch_cp_app_feature(const SceneDev &sc, const CpDev &cp, const float *xyz, int xyz_stride, long long m, const unsigned *m_dev, const unsigned *q_ray,
                                  const float *rays, float *feats, float *dirs, hipStream_t stream);
 hipError_t launch_cp_rgbw(const MarchOut &mo, const float *rgb, long long cap, hipStream_t stream);

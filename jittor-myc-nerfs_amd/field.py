@@ -777,6 +777,65 @@ class TensorBase(torch.nn.Module):
                 "tvr_app_feature")
         return out
 
+    def _device_points(self, x, what):
+        if not torch.is_tensor(x) or x.device.type != "cuda":
+            where = x.device if torch.is_tensor(x) else type(x).__name__
+            raise L.TvrError(f"{what} runs on an MI355X (HIP) device only; the points are on {where}. There is no CPU fallback.")
+        return _f32c(x, self.device).view(-1, 3)
+
+    def compute_density_gradient(self, xyz_sampled, half_width=None):
+        """(sigma_feature [m], grad [m,3]) at normalised coordinates (tvr_density_gradient; the reference has no counterpart): sigma_feature is
+        compute_densityfeature's value bit for bit, grad[:, k] = (f(p + h_k e_k) - f(p - h_k e_k)) * (0.5 / h_k), a symmetric difference of that value.
+        half_width: one number or three (x, y, z), in normalised units; None = one cell of the field's own grid per axis, 2 / (gridSize_k - 1)."""
+        x = self._device_points(xyz_sampled, "compute_density_gradient")
+        sc = self._ensure_scene()
+        if half_width is None:
+            hw = [2.0 / (int(g) - 1) for g in self.gridSize]
+        elif hasattr(half_width, "__len__"):
+            hw = [float(v) for v in half_width]
+            if len(hw) != 3:
+                raise ValueError(f"half_width takes one number or three (x, y, z); got {len(hw)}")
+        else:
+            hw = [float(half_width)] * 3
+        h = (C.c_float * 3)(*hw)
+        sigma = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
+        grad = torch.empty((x.shape[0], 3), dtype=torch.float32, device=self.device)
+        L.check(L.lib().tvr_density_gradient(sc, x.data_ptr(), x.shape[0], C.byref(h), sigma.data_ptr(), L.nbytes(sigma), grad.data_ptr(), L.nbytes(grad),
+                                             _stream_ptr(self.device)), "tvr_density_gradient")
+        return sigma, grad
+
+    @torch.no_grad()
+    def surface_normals(self, xyz_world, half_width=None):
+        """[m,3] fp32 unit normals at world positions: -grad / |grad| of the density feature, pointing from dense to empty (the orientation of mesh.py's triangles).
+        The gradient of compute_density_gradient is in normalised units; d/dx_k = (2 / (aabb1_k - aabb0_k)) d/dnorm_k.  The length is sqrt(max(|g|^2, 1e-30)),
+        so a zero gradient gives a zero vector, never NaN."""
+        x = self._device_points(xyz_world, "surface_normals")
+        _, g = self.compute_density_gradient(self.normalize_coord(x), half_width)
+        g = -(g * self.invaabbSize.to(device=g.device, dtype=torch.float32))
+        return g / torch.sqrt(torch.clamp((g * g).sum(-1, keepdim=True), min=1e-30))
+
+    @torch.no_grad()
+    def mesh_vertex_attributes(self, verts, normals=True, colors=True, half_width=None):
+        """Per-vertex attributes of a mesh whose vertices [V,3] lie in world coordinates where the field was sampled: a dict with "normals" [V,3] float32
+        (surface_normals) and / or "colors" [V,3] uint8, on the device.  The colour is the field's own shading at the vertex viewed head-on — the view direction
+        is the negated normal: round(255 * clamp(renderModule(None, -normal, compute_appfeature(normalize_coord(v))), 0, 1))."""
+        v = self._device_points(verts, "mesh_vertex_attributes")
+        out = {}
+        if not (normals or colors):
+            return out
+        n = self.surface_normals(v, half_width) if v.shape[0] else torch.empty((0, 3), dtype=torch.float32, device=self.device)
+        if normals:
+            out["normals"] = n
+        if colors:
+            out["colors"] = self._vertex_colors(v, n)
+        return out
+
+    def _vertex_colors(self, v, n):
+        if v.shape[0] == 0:
+            return torch.empty((0, 3), dtype=torch.uint8, device=self.device)
+        rgb = self.renderModule(None, -n, self.compute_appfeature(self.normalize_coord(v)))
+        return torch.round(255.0 * rgb.clamp(0, 1)).to(torch.uint8)
+
     def _mlp_render(self, viewdirs, features):
         sc = self._ensure_scene()
         self._settle_range_check()
@@ -836,7 +895,7 @@ class TensorBase(torch.nn.Module):
         return alpha, dense_xyz
 
     @torch.no_grad()
-    def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False):
+    def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False):
         """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
         (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
 
@@ -844,7 +903,10 @@ class TensorBase(torch.nn.Module):
           * "reference" — utils.py:166-179 exactly: voxel size = extent / N, origin aabb[0].  The samples were taken at extent / (N - 1) (getDenseAlpha's linspace), so
             this convention shrinks the mesh by (N - 1) / N towards aabb[0] against the sampled positions;
           * "samples" — voxel size = extent / (N - 1): vertices lie where the field was sampled.
-        flip: reverse every triangle.  Normals point out of the dense region (mesh.py); the reference reverses skimage's order, which cannot be compared here."""
+        flip: reverse every triangle.  Normals point out of the dense region (mesh.py); the reference reverses skimage's order, which cannot be compared here.
+        normals / colors: add per-vertex `nx ny nz` / `red green blue` (mesh_vertex_attributes) to the file; with both off the file is the reference's bare geometry.
+        The attributes are evaluated where the field was SAMPLED: with spacing="reference" the written (shrunken) vertices are mapped back by N / (N - 1) about aabb[0]
+        for the query only.  flip does not touch the normals: they follow the field."""
         from . import mesh
         alpha, _ = self.getDenseAlpha(gridSize)
         aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
@@ -856,8 +918,24 @@ class TensorBase(torch.nn.Module):
         else:
             raise ValueError(f"spacing {spacing!r}: 'reference' or 'samples'")
         verts, faces = mesh.marching_cubes(alpha, level, spacing=voxel.tolist(), origin=aabb[0].tolist(), flip=flip)
-        mesh.write_ply(path, verts, faces)
+        if not (normals or colors):
+            mesh.write_ply(path, verts, faces)
+            return verts, faces
+        at = self.mesh_sample_positions(verts, alpha.shape, spacing)
+        attrs = self.mesh_vertex_attributes(at, normals=normals, colors=colors)
+        mesh.write_ply(path, verts, faces, normals=attrs.get("normals"), colors=attrs.get("colors"))
         return verts, faces
+
+    def mesh_sample_positions(self, verts, gridSize, spacing):
+        """Where the field was sampled for the vertices export_mesh writes: the vertices themselves for spacing="samples"; for "reference" (voxel = extent / N)
+        the vertices scaled by N / (N - 1) about aabb[0]."""
+        if spacing == "samples":
+            return verts
+        if spacing != "reference":
+            raise ValueError(f"spacing {spacing!r}: 'reference' or 'samples'")
+        aabb = self.aabb.to(device=verts.device, dtype=torch.float32)
+        n = torch.tensor([float(s) for s in gridSize], dtype=torch.float32, device=verts.device)
+        return aabb[0] + (verts - aabb[0]) * (n / (n - 1))
 
     @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):                                      # :385-409

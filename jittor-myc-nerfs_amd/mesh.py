@@ -77,8 +77,18 @@ _VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 _FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
-def ply_header(n_vertices: int, n_faces: int) -> bytes:
-    return (f"ply\nformat binary_little_endian 1.0\nelement vertex {int(n_vertices)}\nproperty float x\nproperty float y\nproperty float z\n"
+_NORMAL_FIELDS = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+_COLOR_FIELDS = [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+
+
+def _vertex_dtype(normals: bool, colors: bool) -> np.dtype:
+    return np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + (_NORMAL_FIELDS if normals else []) + (_COLOR_FIELDS if colors else []))
+
+
+def ply_header(n_vertices: int, n_faces: int, normals: bool = False, colors: bool = False) -> bytes:
+    extra = ("property float nx\nproperty float ny\nproperty float nz\n" if normals else "") + \
+            ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if colors else "")
+    return (f"ply\nformat binary_little_endian 1.0\nelement vertex {int(n_vertices)}\nproperty float x\nproperty float y\nproperty float z\n{extra}"
             f"element face {int(n_faces)}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
 
 
@@ -88,16 +98,34 @@ def _host(a, dtype):
     return np.ascontiguousarray(np.asarray(a).reshape(-1, 3), dtype=dtype)
 
 
-def write_ply(path, verts, faces) -> None:
+def write_ply(path, verts, faces, normals=None, colors=None) -> None:
     """Binary little-endian PLY with the two elements the reference writes through plyfile: `vertex` (float x, y, z) and `face`
-    (property list uchar int vertex_indices, three indices per face).  verts [V,3], faces [F,3]: tensors (any device) or arrays."""
+    (property list uchar int vertex_indices, three indices per face).  verts [V,3], faces [F,3]: tensors (any device) or arrays.
+    normals [V,3] float / colors [V,3] uint8 (optional, not in the reference's files) append `float nx ny nz` / `uchar red green blue` to the vertex element."""
     v, f = _host(verts, "<f4"), _host(faces, "<i4")
     rows = np.empty(len(f), dtype=_FACE_DTYPE)
     rows["n"] = 3
     rows["v"] = f
+    if normals is None and colors is None:
+        body = v.tobytes()
+    else:
+        vr = np.empty(len(v), dtype=_vertex_dtype(normals is not None, colors is not None))
+        vr["x"], vr["y"], vr["z"] = v[:, 0], v[:, 1], v[:, 2]
+        for given, fields, dt, what in ((normals, _NORMAL_FIELDS, "<f4", "normals"), (colors, _COLOR_FIELDS, "u1", "colors")):
+            if given is None:
+                continue
+            a = given.detach().cpu().numpy() if torch.is_tensor(given) else np.asarray(given)
+            if what == "colors" and a.dtype != np.uint8:
+                raise ValueError(f"colors must be uint8 (0..255), got {a.dtype}")
+            a = _host(a, dt)
+            if len(a) != len(v):
+                raise ValueError(f"{what} holds {len(a)} rows for {len(v)} vertices")
+            for j, (name, _) in enumerate(fields):
+                vr[name] = a[:, j]
+        body = vr.tobytes()
     with open(path, "wb") as out:
-        out.write(ply_header(len(v), len(f)))
-        out.write(v.tobytes())
+        out.write(ply_header(len(v), len(f), normals is not None, colors is not None))
+        out.write(body)
         out.write(rows.tobytes())
 
 
@@ -125,3 +153,47 @@ def read_ply(path):
     if nf and not (rows["n"] == 3).all():
         raise ValueError(f"{path}: a face is not a triangle")
     return v, rows["v"].astype(np.int32).reshape(nf, 3)
+
+
+def read_ply_attributes(path):
+    """Reads back every file write_ply can write: (verts [V,3] float32, faces [F,3] int32, attributes) with attributes a dict that holds "normals" [V,3] float32 and /
+    or "colors" [V,3] uint8 when the file has them.  Any other property set, format or body size is a ValueError."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    head = data[:end + len(b"end_header\n")]
+    body = data[len(head):]
+    counts = {}
+    try:
+        for line in head.decode("ascii").split("\n"):
+            tok = line.split()
+            if tok[:1] == ["element"]:
+                counts[tok[1]] = int(tok[2])
+    except (UnicodeDecodeError, IndexError, ValueError):
+        raise ValueError(f"{path}: malformed PLY header") from None
+    if set(counts) != {"vertex", "face"}:
+        raise ValueError(f"{path}: a vertex and a face element are read, the file declares {sorted(counts)}")
+    nv, nf = counts["vertex"], counts["face"]
+    if nv < 0 or nf < 0:
+        raise ValueError(f"{path}: negative element count")
+    for has_n, has_c in ((False, False), (True, False), (False, True), (True, True)):
+        if head == ply_header(nv, nf, has_n, has_c):
+            break
+    else:
+        raise ValueError(f"{path}: only binary little-endian PLY with float x y z [nx ny nz] [uchar red green blue] vertices and uchar/int triangle lists is read")
+    vdt = _vertex_dtype(has_n, has_c)
+    if len(body) != nv * vdt.itemsize + nf * _FACE_DTYPE.itemsize:
+        raise ValueError(f"{path}: body of {len(body)} B does not hold {nv} vertices and {nf} triangles")
+    vr = np.frombuffer(body, dtype=vdt, count=nv)
+    rows = np.frombuffer(body, dtype=_FACE_DTYPE, count=nf, offset=nv * vdt.itemsize)
+    if nf and not (rows["n"] == 3).all():
+        raise ValueError(f"{path}: a face is not a triangle")
+    attrs = {}
+    if has_n:
+        attrs["normals"] = np.stack((vr["nx"], vr["ny"], vr["nz"]), -1).astype(np.float32).reshape(nv, 3)
+    if has_c:
+        attrs["colors"] = np.stack((vr["red"], vr["green"], vr["blue"]), -1).astype(np.uint8).reshape(nv, 3)
+    verts = np.stack((vr["x"], vr["y"], vr["z"]), -1).astype(np.float32).reshape(nv, 3)
+    return verts, rows["v"].astype(np.int32).reshape(nf, 3), attrs

@@ -9,7 +9,8 @@ What differs from the reference, on purpose:
   * no TensorBoard writer, no `ndc_ray` datasets (the reference ships only the Blender loader); `set_nerfplusplus` is called for NerfPlusPlus only
     (train.py:172 calls it unconditionally and fails for the others);
   * `--export_mesh 1` (train.py:41-59) extracts the surface with the HIP marching cubes (mesh.py) instead of skimage and writes the PLY without plyfile; the
-    level and the grid are options (`mesh_level`, `mesh_grid`), and the command ends after the export instead of falling through into a training run;
+    level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
+    geometry), and the command ends after the export instead of falling through into a training run;
   * progress is a plain print every `progress_refresh_rate` iterations.
 Host-side plumbing only: every pixel comes from the HIP kernels through `OctreeRender_trilinear_fast`.
 """
@@ -81,6 +82,9 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # (not reference options) export_mesh: the iso-level train.py:59 hard-codes (its comment: 0.005 for Scarf, 0.0005 for Coffee) and an optional [nx, ny, nz] grid for the
     # dense alpha volume (default: the checkpoint's gridSize, as the reference)
     p.add_argument("--mesh_level", type=float, default=0.0005)
+    # (not reference options) per-vertex normals (nx ny nz) / colours (red green blue) in the exported PLY; 0 = the reference's bare geometry
+    p.add_argument("--mesh_normals", type=int, default=0)
+    p.add_argument("--mesh_colors", type=int, default=0)
     for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int), ("mesh_grid", int)):
         p.add_argument("--" + name, type=typ, action="append")
     argv = sys.argv[1:] if cmd is None else list(cmd)
@@ -170,7 +174,8 @@ def export_mesh(args, device="cuda"):
         raise ValueError(f"mesh_grid takes three sizes [nx, ny, nz]; got {grid}")
     tensorf, _ = _build_from_ckpt(args, load_checkpoint(args.ckpt), device)
     path = f"{args.ckpt[:-3]}.ply"
-    verts, faces = tensorf.export_mesh(path, level=getattr(args, "mesh_level", 0.0005), gridSize=grid)
+    verts, faces = tensorf.export_mesh(path, level=getattr(args, "mesh_level", 0.0005), gridSize=grid, normals=bool(getattr(args, "mesh_normals", 0)),
+                                       colors=bool(getattr(args, "mesh_colors", 0)))
     print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles)")
     return path
 

@@ -101,6 +101,10 @@ class REFTensoRF(TensorVMSplit):
     def _mlp_render(self, viewdirs, features):
         raise L.TvrError("REFTensoRF shades with MLPRender_Fea_Ref: call renderModule(pts, reflection, features, dot_product, k)")
 
+    def _vertex_colors(self, v, n):
+        raise NotImplementedError("REFTensoRF shades through reflection heads that need a ray (MLPRender_Fea_Ref: reflection direction, dot product, roughness): "
+                                  "mesh vertex colours are not built for REFTensoRF; normals are (mesh_vertex_attributes(verts, colors=False))")
+
     def _mlp_render_ref(self, viewdirs, features, dot_product):
         sc = self._ensure_scene()
         v = _f32c(viewdirs, self.device).view(-1, 3)
