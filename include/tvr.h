@@ -250,6 +250,24 @@ int tvr_density_feature(tvr_scene *scene, const float *xyz_norm, int64_t m, floa
  * half_width / grad, m < 0, or a half width that is not finite and > 0.  m == 0 succeeds and launches nothing. */
 int tvr_density_gradient(tvr_scene *scene, const float *xyz_norm, int64_t m, const float half_width[3], float *sigma_feature /* [m] or NULL */, size_t sigma_bytes,
                          float *grad /* [m,3] */, size_t grad_bytes, void *stream);
+/* The normal map of a ray batch: tvr_render's march (same rays, jitter, eps_T, alpha mask; uniform steps only) followed by ONE kernel that turns the march's queue of
+ * appearance samples e = {x_e = normalize_coord(o + d z), w_e > weight_thres} into
+ *   N_i = sum_e w_e n_e,   n_e = v_e / sqrt(max(|v_e|^2, 1e-30)),   v_e = -(g_e * inv_aabb_size),   g_e = tvr_density_gradient's value at x_e for half_width
+ * (a zero gradient gives a zero vector, never NaN).  N is world-space fp32 and is NOT renormalised: |N_i| <= acc_i up to rounding, a ray without an entry gives 0, and
+ * 0.5 N + 0.5 acc + (1 - acc) bg is the picture a viewer expects, edges blending into the background as the colour does.  The sum over e runs in an order that depends
+ * on the ray's own entries only: the result is bit-reproducible and independent of the batch, of chunking and of which wave took the ray.
+ *   normal_out [n,3]; acc_out [n] or NULL: the march's acc (the sum of ALL weights of the ray); depth_out [n] or NULL: tvr_render's depth.
+ * Header clear, march, normal kernel on the caller's stream: no allocation, no synchronisation, no shade, nothing per entry written to memory besides the march's queue.
+ * The scratch (tvr_render_normals_scratch_bytes; 256-byte aligned) holds the header, the per-ray arrays and the queue's positions and ray indices: 20 B per sample of
+ * capacity, n * S of them.  TensorVMSplit, REFTensoRF (the same VM density field) and CP scenes are accepted; explicit depths (tvr_render_z) are not offered.
+ * If the march raises its fault flag, every output of the call is NaN, as tvr_render's pixels are.
+ * Errors, all before any launch: TVR_ERR_INVALID for a NULL scene / rays / normal_out / half_width, n_rays < 0, n_samples or eps_T outside tvr_render's ranges,
+ * n_rays * n_samples >= 2^32, or a half width that is not finite and > 0 (the message names half_width); TVR_ERR_SCRATCH for an undersized normal_out / acc_out /
+ * depth_out / scratch (the message names the buffer) or a misaligned scratch.  n_rays == 0 succeeds and launches nothing.  ADDITIVE exports: TVR_VERSION is unchanged. */
+size_t tvr_render_normals_scratch_bytes(const tvr_scene *scene, int64_t n_rays, int32_t n_samples);
+int tvr_render_normals(tvr_scene *scene, const float *rays, int64_t n_rays, int32_t n_samples, const float *jitter /* [n] or NULL */, float eps_T,
+                       const float half_width[3], float *normal_out /* [n,3] */, size_t normal_bytes, float *acc_out /* [n] or NULL */, size_t acc_bytes,
+                       float *depth_out /* [n] or NULL */, size_t depth_bytes, void *scratch, size_t scratch_bytes, void *stream);
 /* TensorVMSplit.compute_appfeature (tensoRF.py:228-244): xyz_norm [m,3] -> out [m,app_dim]. */
 int tvr_app_feature(tvr_scene *scene, const float *xyz_norm, int64_t m, float *out, size_t out_bytes, void *stream);
 /* MLPRender_Fea.execute (tensorBase.py:76-86): viewdirs [m,3], features [m,app_dim] -> rgb [m,3]. */

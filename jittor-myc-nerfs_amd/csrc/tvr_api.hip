@@ -1510,6 +1510,78 @@ int tvr_density_gradient(tvr_scene *s, const float *xyz, int64_t m, const float 
     return TVR_OK;
 }
 
+// tvr_render_normals' scratch: the header, the per-ray arrays the march writes (depth among them: the march writes one whether or not the caller wants it) and the
+// queue's positions and ray indices; neither q_out / q_j nor a CP scene's staging regions (nothing is shaded)
+struct NormalsLayout { size_t counter, ray_off, ray_cnt, acc, depth, q_pos, q_ray, total; };
+static NormalsLayout normals_layout(int64_t n_rays, int32_t S)
+{
+    NormalsLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    const size_t cap = (size_t)n_rays * (size_t)S;
+    L.counter = take(256);
+    L.ray_off = take(n_rays * 4);
+    L.ray_cnt = take(n_rays * 4);
+    L.acc = take(n_rays * 4);
+    L.depth = take(n_rays * 4);
+    L.q_pos = take(cap * 16);
+    L.q_ray = take(cap * 4);
+    L.total = off;
+    return L;
+}
+
+size_t tvr_render_normals_scratch_bytes(const tvr_scene *, int64_t n_rays, int32_t n_samples)
+{
+    if (n_rays <= 0 || n_samples <= 0) return 256;
+    return normals_layout(n_rays, n_samples).total;
+}
+
+int tvr_render_normals(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, const float half_width[3], float *normal_out,
+                       size_t normal_bytes, float *acc_out, size_t acc_bytes, float *depth_out, size_t depth_bytes, void *scratch, size_t scratch_bytes, void *stream_)
+{
+    if (!s || !s->params_set) return fail(TVR_ERR_INVALID, "tvr_render_normals: scene is NULL or tvr_scene_update has not run");
+    if (!half_width) return fail(TVR_ERR_INVALID, "tvr_render_normals: half_width is NULL");
+    float inv2h[3];
+    for (int k = 0; k < 3; ++k) {
+        if (!(half_width[k] > 0.0f) || !(half_width[k] <= 3.4028234664e38f))
+            return fail(TVR_ERR_INVALID, "tvr_render_normals: half_width[%d] = %g must be finite and > 0", k, half_width[k]);
+        inv2h[k] = 0.5f / half_width[k];
+    }
+    if (n_rays < 0) return fail(TVR_ERR_INVALID, "tvr_render_normals: n_rays < 0");
+    if (n_rays == 0) return TVR_OK;
+    if (!rays || !normal_out) return fail(TVR_ERR_INVALID, "tvr_render_normals: rays / normal_out NULL");
+    if (S <= 0 || S > 4096) return fail(TVR_ERR_INVALID, "tvr_render_normals: n_samples=%d out of [1,4096]", S);
+    if ((size_t)n_rays * (size_t)S >= (1ull << 32)) return fail(TVR_ERR_INVALID, "tvr_render_normals: n_rays*n_samples must be < 2^32 per call (chunk the rays)");
+    if (!(eps_T >= 0.0f) || eps_T > s->desc.weight_thres)
+        return fail(TVR_ERR_INVALID, "tvr_render_normals: eps_T=%g must be in [0, weight_thres=%g] so that no appearance sample is skipped", eps_T, s->desc.weight_thres);
+    NEED("normal_out [n,3]", normal_bytes, n_rays, 3);
+    if (acc_out) NEED("acc_out [n]", acc_bytes, n_rays, 1);
+    if (depth_out) NEED("depth_out [n]", depth_bytes, n_rays, 1);
+    const NormalsLayout L = normals_layout(n_rays, S);
+    if (!scratch || scratch_bytes < L.total) return fail(TVR_ERR_SCRATCH, "tvr_render_normals: scratch %zu B < required %zu B", scratch_bytes, L.total);
+    if ((uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "tvr_render_normals: scratch must be 256-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    char *b = (char *)scratch;
+    MarchOut mo;
+    mo.counter = (unsigned *)(b + L.counter);
+    mo.ray_off = (unsigned *)(b + L.ray_off);
+    mo.ray_cnt = (unsigned *)(b + L.ray_cnt);
+    mo.acc = (float *)(b + L.acc);
+    mo.depth = depth_out ? depth_out : (float *)(b + L.depth);
+    mo.q_pos = (float4 *)(b + L.q_pos);
+    mo.q_out = mo.q_pos;                                               // (nothing is shaded: the march never touches q_out)
+    mo.q_ray = (unsigned *)(b + L.q_ray);
+    mo.q_j = nullptr;
+    mo.stats = nullptr;
+    mo.lam6 = nullptr;
+    const MarchSampling sm = {jitter, nullptr};
+    HIP_TRY(launch_zero_header(mo.counter, stream));                   // [0] queue length, [1] the march's tile counter, [2] its fault flag, [16] the normal pass's ray tickets
+    if (s->cp) HIP_TRY(launch_cp_march(s->dev, s->cpd, rays, (int)n_rays, S, sm, eps_T, mo, nullptr, stream));
+    else HIP_TRY(launch_march(s->dev, rays, (int)n_rays, S, sm, eps_T, mo, nullptr, stream));
+    HIP_TRY(launch_normals(s->dev, s->cp ? &s->cpd : nullptr, mo, (int)n_rays, half_width, inv2h, normal_out, acc_out, depth_out, stream));
+    return TVR_OK;
+}
+
 int tvr_app_feature(tvr_scene *s, const float *xyz, int64_t m, float *out, size_t out_bytes, void *stream)
 {
     if (m > 0) NEED("out [m,27]", out_bytes, m, TVR_APPDIM);

@@ -10,6 +10,7 @@
 #include "tvr_device.h"
 #include "tvr_kernels.h"
 #include "tvr_march_body.h"
+#include "tvr_gradient.h"
 
 // ---- a. the march: the shared body with CP = true -------------------------------------------------------------------------------------------------------------
 template <bool DENSE>
@@ -47,22 +48,7 @@ hipError_t launch_cp_march(const SceneDev &sc, const CpDev &cp, const float *ray
     return launch_cp_march_t<false>(sc, cp, rays, n_rays, S, sm, eps_T, mo, none, waves, lds, (unsigned)grid, stream);
 }
 
-// cell and weights of a normalised coordinate on an axis of L points, for ARBITRARY coordinates: the two taps' weights are zero where the tap lies outside the
-// line (grid_sample's zeros padding), and the indices are clamped into the packed line so that nothing is read out of bounds
-struct CpTap { int i0, i1; float u, w; };
-__device__ __forceinline__ CpTap cp_tap(float c, float gm1, int L)
-{
-    const float f = unnorm(c, gm1);
-    const float fl = floorf(fminf(fmaxf(f, -2.0f), gm1 + 2.0f));
-    const int l0 = (int)fl;
-    const float w = f - fl;
-    CpTap t;
-    t.u = (l0 >= 0 && l0 < L) ? 1.0f - w : 0.0f;
-    t.w = (l0 + 1 >= 0 && l0 + 1 < L) ? w : 0.0f;
-    t.i0 = min(max(l0, 0), L - 1);
-    t.i1 = min(max(l0 + 1, 0), L - 1);
-    return t;
-}
+// (cp_tap, the cell and weights of a normalised coordinate on an axis of L points, lives in tvr_gradient.h beside the gradient's per-point code)
 
 // ---- b. compute_densityfeature at arbitrary points: one lane per point ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cp_density_feature_kernel(const SceneDev sc, const CpDev cp, const float *__restrict__ xyz, const long long m, float *__restrict__ out)
@@ -93,42 +79,17 @@ hipError_t launch_cp_density_feature(const SceneDev &sc, const CpDev &cp, const 
 //   grad[k] = (f(p + h_k e_k) - f(p - h_k e_k)) * (0.5 / h_k),  f = cp_density_feature_kernel's value.  A shift along an axis moves one of the three line factors:
 // each line is interpolated at {centre, +h, -h} (18 float4 taps per group of four components where seven calls of the kernel above read 42) and the seven
 // products are formed and summed in that kernel's order, so the centre is bit-equal to it and the quotient is the one of its values at the shifted points.
-__device__ __forceinline__ float4 cp_lerp4(const float4 *__restrict__ line, const CpTap t, int tpt, int g)
-{
-    return f4_fma(t.w, line[(size_t)t.i1 * tpt + g], f4_mul(t.u, line[(size_t)t.i0 * tpt + g]));
-}
-__device__ __forceinline__ float cp_dot4(float4 a, float4 b, float4 c)
-{
-    const float t0 = (a.x * b.x) * c.x, t1 = (a.y * b.y) * c.y, t2 = (a.z * b.z) * c.z, t3 = (a.w * b.w) * c.w;
-    return (t0 + t1) + (t2 + t3);
-}
-
 __global__ __launch_bounds__(256) void cp_density_gradient_kernel(const SceneDev sc, const CpDev cp, const float *__restrict__ xyz, const long long m, const float3 h,
                                                                   const float3 inv2h, float *__restrict__ sigma_feature, float *__restrict__ grad)
 {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= m) return;
-    const float px = xyz[s * 3], py = xyz[s * 3 + 1], pz = xyz[s * 3 + 2];
-    // [0] centre, [1] +h, [2] -h
-    const CpTap tx[3] = {cp_tap(px, sc.gm1[0], sc.grid[0]), cp_tap(px + h.x, sc.gm1[0], sc.grid[0]), cp_tap(px - h.x, sc.gm1[0], sc.grid[0])};
-    const CpTap ty[3] = {cp_tap(py, sc.gm1[1], sc.grid[1]), cp_tap(py + h.y, sc.gm1[1], sc.grid[1]), cp_tap(py - h.y, sc.gm1[1], sc.grid[1])};
-    const CpTap tz[3] = {cp_tap(pz, sc.gm1[2], sc.grid[2]), cp_tap(pz + h.z, sc.gm1[2], sc.grid[2]), cp_tap(pz - h.z, sc.gm1[2], sc.grid[2])};
-    const int tpt = cp.rd >> 2;
-    float fc = 0.0f, fxp = 0.0f, fxm = 0.0f, fyp = 0.0f, fym = 0.0f, fzp = 0.0f, fzm = 0.0f;
-    for (int g = 0; g < tpt; ++g) {
-        const float4 a = cp_lerp4(sc.dline[0], tz[0], tpt, g), b = cp_lerp4(sc.dline[1], ty[0], tpt, g), c = cp_lerp4(sc.dline[2], tx[0], tpt, g);
-        fc = fc + cp_dot4(a, b, c);
-        fxp = fxp + cp_dot4(a, b, cp_lerp4(sc.dline[2], tx[1], tpt, g));
-        fxm = fxm + cp_dot4(a, b, cp_lerp4(sc.dline[2], tx[2], tpt, g));
-        fyp = fyp + cp_dot4(a, cp_lerp4(sc.dline[1], ty[1], tpt, g), c);
-        fym = fym + cp_dot4(a, cp_lerp4(sc.dline[1], ty[2], tpt, g), c);
-        fzp = fzp + cp_dot4(cp_lerp4(sc.dline[0], tz[1], tpt, g), b, c);
-        fzm = fzm + cp_dot4(cp_lerp4(sc.dline[0], tz[2], tpt, g), b, c);
-    }
-    if (sigma_feature) sigma_feature[s] = fc;
-    grad[s * 3 + 0] = (fxp - fxm) * inv2h.x;
-    grad[s * 3 + 1] = (fyp - fym) * inv2h.y;
-    grad[s * 3 + 2] = (fzp - fzm) * inv2h.z;
+    float f[7];
+    cp_grad_point(sc, cp, xyz[s * 3], xyz[s * 3 + 1], xyz[s * 3 + 2], h, f);
+    if (sigma_feature) sigma_feature[s] = f[0];
+    grad[s * 3 + 0] = (f[1] - f[2]) * inv2h.x;
+    grad[s * 3 + 1] = (f[3] - f[4]) * inv2h.y;
+    grad[s * 3 + 2] = (f[5] - f[6]) * inv2h.z;
 }
 
 hipError_t launch_cp_density_gradient(const SceneDev &sc, const CpDev &cp, const float *xyz, long long m, const float h[3], const float inv2h[3], float *sigma_feature,

@@ -171,6 +171,12 @@ hipError_t launch_cp_rgbw(const MarchOut &mo, const float *rgb, long long cap, h
 hipError_t launch_cp_pack_basis(const float *basis, int r_app, int ra, float4 *out, hipStream_t stream);
 int march_cu_count();
 
+// tvr_normals.hip: the march's queue -> normal [n,3] = sum over a ray's entries of weight x unit(-gradient of the density feature x inv_aabb_size); acc_out [n] or nullptr
+// receives mo.acc, and with the march's fault flag set every output of the call (depth_out [n] or nullptr included) is NaN.  cp: the CP scene's part, or nullptr (VM).
+// Draws its ray tickets from a word of the scratch header that launch_zero_header cleared in front of the march.
+hipError_t launch_normals(const SceneDev &sc, const CpDev *cp, const MarchOut &mo, int n_rays, const float h[3], const float inv2h[3], float *normal_out, float *acc_out,
+                          float *depth_out, hipStream_t stream);
+
 // tvr_mesh.hip: marching cubes over a dense fp32 volume [nx][ny][nz] (z fastest).  The scratch buffer carved for a volume of `points` grid points: a header with the
 // totals, per tile of TVR_MESH_TILE points its base (vertices | triangles << 32), per point one count byte and the two exclusive bases (arrays padded to whole tiles)
 struct MeshScratch {

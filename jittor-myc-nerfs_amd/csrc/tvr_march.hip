@@ -24,6 +24,7 @@
 #include "tvr_device.h"
 #include "tvr_kernels.h"
 #include "tvr_march_body.h"
+#include "tvr_gradient.h"
 
 // (Round 5 also computed everything that depends on the sample alone once per chunk and read it through quad_perm DPP operands: -8 % VALU instructions, bit-identical,
 // 1.8 % slower — DESIGN.md 4.1.  Its interpolation ops were v_mul_f32_dpp / v_fmac_f32_dpp as inline asm: hipcc's DPP combine folds a broadcast into v_mul_f32 only, and
@@ -133,85 +134,8 @@ __global__ __launch_bounds__(256) void density_feature_kernel(const SceneDev sc,
 
 // ---- symmetric-difference gradient of the density feature (tvr_density_gradient) -------------------------------------------------------------------------------
 //   grad[k] = (f(p + h_k e_k) - f(p - h_k e_k)) * (0.5 / h_k),   f = density_feature_kernel's value (arbitrary coordinates, zeros padding)
-// Same mapping as density_feature_kernel: a quad per point, lane `sub` holds 4 of the 16 channels, quad reduction at the end.  A shift along axis k moves only the
-// factor that depends on k, so a VM term (plane over axes A, B; line over C) needs its plane at 5 positions (centre, A+-, B+-) and its line at 3 (centre, C+-)
-// instead of 7 + 7: 78 float4 loads per lane where seven density_feature_kernel calls issue 126.  Each of the seven values is formed by vm_term's own expressions in
-// vm_term's order and summed in density_feature_kernel's order, so the centre is bit-equal to tvr_density_feature at p and the gradient is bit-equal to the same
-// difference quotient of tvr_density_feature at the shifted points (shifted coordinate and quotient in separately rounded fp32).
-struct AxisTap { int i0; float w; };
-__device__ __forceinline__ AxisTap axis_tap(float c, float gm1)
-{
-    const float f = unnorm(c, gm1);
-    const float fl = floorf(fminf(fmaxf(f, -2.0f), gm1 + 2.0f));
-    AxisTap t;
-    t.i0 = (int)fl;
-    t.w = f - fl;
-    return t;
-}
-
-// vm_term<4, true>'s bilinear plane factor and linear line factor, one quad-lane's 4 channels each
-__device__ __forceinline__ float4 vm_plane4(const float4 *__restrict__ P, int W, int H, AxisTap tx, AxisTap ty, int sub)
-{
-    const int x0 = tx.i0, y0 = ty.i0;
-    const float wx = tx.w, wy = ty.w, ux = 1.0f - wx, uy = 1.0f - wy;
-    const int Wp = W + 1;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool xi0 = (x0 >= 0) & (x0 < W), xi1 = (x0 + 1 >= 0) & (x0 + 1 < W);
-    const bool yi0 = (y0 >= 0) & (y0 < H), yi1 = (y0 + 1 >= 0) & (y0 + 1 < H);
-    const int xc = min(max(x0, 0), W - 1), yc = min(max(y0, 0), H - 1);
-    const int xd = min(max(x0 + 1, 0), W - 1), yd = min(max(y0 + 1, 0), H - 1);
-    // the clamped addresses are always inside the plane: load unconditionally and select (a conditional load compiles to a branch per texel and component)
-    const float4 r00 = P[((size_t)yc * Wp + xc) * 4 + sub], r01 = P[((size_t)yc * Wp + xd) * 4 + sub];
-    const float4 r10 = P[((size_t)yd * Wp + xc) * 4 + sub], r11 = P[((size_t)yd * Wp + xd) * 4 + sub];
-    const float4 t00 = (xi0 & yi0) ? r00 : z, t01 = (xi1 & yi0) ? r01 : z, t10 = (xi0 & yi1) ? r10 : z, t11 = (xi1 & yi1) ? r11 : z;
-    float4 p4 = f4_mul(ux * uy, t00);
-    p4 = f4_fma(wx * uy, t01, p4);
-    p4 = f4_fma(ux * wy, t10, p4);
-    p4 = f4_fma(wx * wy, t11, p4);
-    return p4;
-}
-
-__device__ __forceinline__ float4 vm_line4(const float4 *__restrict__ Ln, int L, AxisTap tl, int sub)
-{
-    const int l0 = tl.i0;
-    const float wl = tl.w, ul = 1.0f - wl;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool li0 = (l0 >= 0) & (l0 < L), li1 = (l0 + 1 >= 0) & (l0 + 1 < L);
-    const int lc = min(max(l0, 0), L - 1), ld = min(max(l0 + 1, 0), L - 1);
-    const float4 r0 = Ln[(size_t)lc * 4 + sub], r1 = Ln[(size_t)ld * 4 + sub];
-    const float4 l0v = li0 ? r0 : z, l1v = li1 ? r1 : z;
-    float4 q4 = f4_mul(ul, l0v);
-    q4 = f4_fma(wl, l1v, q4);
-    return q4;
-}
-
-// sum of the 4 channels of plane * line in density_feature_kernel's order
-__device__ __forceinline__ float vm_dot4(float4 p4, float4 q4)
-{
-    const float4 a = make_float4(p4.x * q4.x, p4.y * q4.y, p4.z * q4.z, p4.w * q4.w);
-    return (a.x + a.y) + (a.z + a.w);
-}
-
-// One VM term at the seven positions.  ta / tb / tl: the taps of the plane's two axes and of the line's axis at {centre, +h, -h}.
-// v[0] centre, v[1], v[2] the plane's first axis +-, v[3], v[4] its second axis +-, v[5], v[6] the line's axis +-.
-// The scheduling barriers bound what is in flight to one group of loads (10, 8, 8 float4), so that the 78 loads of the three terms are not all hoisted to the top:
-// 125 VGPRs, four waves per SIMD to hide the gather's latency behind.
-__device__ __forceinline__ void vm_grad_term(const float4 *__restrict__ P, const float4 *__restrict__ Ln, int W, int H, int L, const AxisTap ta[3], const AxisTap tb[3],
-                                             const AxisTap tl[3], int sub, float v[7])
-{
-    const float4 pc = vm_plane4(P, W, H, ta[0], tb[0], sub), lc = vm_line4(Ln, L, tl[0], sub);
-    v[0] = vm_dot4(pc, lc);
-    v[5] = vm_dot4(pc, vm_line4(Ln, L, tl[1], sub));
-    v[6] = vm_dot4(pc, vm_line4(Ln, L, tl[2], sub));
-    __builtin_amdgcn_sched_barrier(0);
-    v[1] = vm_dot4(vm_plane4(P, W, H, ta[1], tb[0], sub), lc);
-    v[2] = vm_dot4(vm_plane4(P, W, H, ta[2], tb[0], sub), lc);
-    __builtin_amdgcn_sched_barrier(0);
-    v[3] = vm_dot4(vm_plane4(P, W, H, ta[0], tb[1], sub), lc);
-    v[4] = vm_dot4(vm_plane4(P, W, H, ta[0], tb[2], sub), lc);
-    __builtin_amdgcn_sched_barrier(0);
-}
-
+// Same mapping as density_feature_kernel: a quad per point, lane `sub` holds 4 of the 16 channels, quad reduction at the end.  The per-point arithmetic is
+// vm_grad_point's (tvr_gradient.h), which the normal pass (tvr_normals.hip) evaluates too.
 __global__ __launch_bounds__(256) void density_gradient_kernel(const SceneDev sc, const float *__restrict__ xyz, const long long m, const float3 h, const float3 inv2h,
                                                                float *__restrict__ sigma_feature, float *__restrict__ grad)
 {
@@ -222,21 +146,7 @@ __global__ __launch_bounds__(256) void density_gradient_kernel(const SceneDev sc
     float f[7];
 #pragma unroll
     for (int j = 0; j < 7; ++j) f[j] = 0.0f;
-    if (s < m) {
-        const float px = xyz[s * 3], py = xyz[s * 3 + 1], pz = xyz[s * 3 + 2];
-        // per axis: the taps at {centre, +h, -h}; the shifted coordinate is a separately rounded fp32 sum
-        const AxisTap tp[3][3] = {{axis_tap(px, sc.gm1[0]), axis_tap(px + h.x, sc.gm1[0]), axis_tap(px - h.x, sc.gm1[0])},
-                                  {axis_tap(py, sc.gm1[1]), axis_tap(py + h.y, sc.gm1[1]), axis_tap(py - h.y, sc.gm1[1])},
-                                  {axis_tap(pz, sc.gm1[2]), axis_tap(pz + h.z, sc.gm1[2]), axis_tap(pz - h.z, sc.gm1[2])}};
-        // f = (a + b) + c per position, density_feature_kernel's order
-        float v[7];
-        vm_grad_term(sc.dplane[0], sc.dline[0], sc.grid[0], sc.grid[1], sc.grid[2], tp[0], tp[1], tp[2], sub, v);     // plane (x, y), line z
-        f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3]; f[4] = v[4]; f[5] = v[5]; f[6] = v[6];
-        vm_grad_term(sc.dplane[1], sc.dline[1], sc.grid[0], sc.grid[2], sc.grid[1], tp[0], tp[2], tp[1], sub, v);     // plane (x, z), line y
-        f[0] = f[0] + v[0]; f[1] = f[1] + v[1]; f[2] = f[2] + v[2]; f[3] = f[3] + v[5]; f[4] = f[4] + v[6]; f[5] = f[5] + v[3]; f[6] = f[6] + v[4];
-        vm_grad_term(sc.dplane[2], sc.dline[2], sc.grid[1], sc.grid[2], sc.grid[0], tp[1], tp[2], tp[0], sub, v);     // plane (y, z), line x
-        f[0] = f[0] + v[0]; f[1] = f[1] + v[5]; f[2] = f[2] + v[6]; f[3] = f[3] + v[1]; f[4] = f[4] + v[2]; f[5] = f[5] + v[3]; f[6] = f[6] + v[4];
-    }
+    if (s < m) vm_grad_point(sc, xyz[s * 3], xyz[s * 3 + 1], xyz[s * 3 + 2], h, sub, f);
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
         f[j] += __shfl_xor(f[j], 1);

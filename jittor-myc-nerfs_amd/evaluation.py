@@ -4,6 +4,7 @@
                              builds `all_rays [n_img, H*W, 6]`, loads ground-truth PNGs when they exist (alpha blended to white, :105-108)
   * evaluation             — tensorf-myc/renderer.py:29-91: per-image render (chunk 1024), clamp, PSNR / SSIM, `*_r_{idx}.png`, `rgbd/*.png`, `mean.txt`
   * evaluation_path        — tensorf-myc/renderer.py:93-148 without the mp4 writers (imageio is not available here)
+  * normal_map_to_rgb8     — (no reference counterpart) the picture of TensorBase.render_normals' output; `evaluation(..., normal_maps=True)` writes `normal/{idx:03d}.png`
   * rgb_ssim, visualize_depth_numpy — tensorf-myc/utils.py:73-119, :11-26 (the depth colour map is a numpy jet ramp standing in for cv2's LUT)
 Everything here is host-side plumbing around `renderer(rays, tensorf, …)`; the rendering itself is the HIP path.
 """
@@ -169,6 +170,20 @@ def visualize_depth_numpy(depth, minmax=None):
     return (np.stack([b, g, r], -1) * 255).astype(np.uint8), [mi, ma]
 
 
+def normal_map_to_rgb8(normal: torch.Tensor, acc: torch.Tensor, white_bg: bool = True) -> torch.Tensor:
+    """uint8 [..., 3] picture of a normal map (TensorBase.render_normals: normal [..., 3] = sum of weight x unit normal, acc [...] = sum of the weights):
+    round(255 * clamp(0.5 * normal + 0.5 * acc + (1 - acc) * bg, 0, 1)), bg = 1 (white) or 0.  The usual 0.5 n + 0.5 colouring of a unit normal, composited over the
+    background with the colour's own opacity: a ray that hits nothing shows the background, a silhouette pixel blends as the colour image does.  Pure; either device."""
+    a = acc.to(torch.float32).unsqueeze(-1)
+    x = 0.5 * normal.to(torch.float32) + 0.5 * a + (1.0 - a) * (1.0 if white_bg else 0.0)
+    return torch.round(255.0 * x.clamp(0.0, 1.0)).to(torch.uint8)
+
+
+def _normal_frame(tensorf, rays, N_samples, white_bg, H, W):
+    normal, acc, _ = tensorf.render_normals(rays, N_samples=N_samples)
+    return normal_map_to_rgb8(normal, acc, white_bg).reshape(H, W, 3)
+
+
 def _imwrite(path, arr):
     from PIL import Image
     # compress_level 1: the same pixels (PNG is lossless), files ~ 15 % larger, encoding 3 - 4 x faster than Pillow's default 6 — the encoder, not the renderer, sets the pace of
@@ -178,10 +193,15 @@ def _imwrite(path, arr):
 
 @torch.no_grad()
 def evaluation(test_dataset, tensorf, args, renderer, savePath=None, N_vis=5, prtx='', N_samples=-1, white_bg=False, ndc_ray=False,
-               compute_extra_metrics=True, device='cuda') -> List[float]:
+               compute_extra_metrics=True, device='cuda', normal_maps=False) -> List[float]:
+    """normal_maps (not a reference option): with savePath, also write normal/{idx:03d}.png per frame — tensorf.render_normals on the frame's rays (not `renderer`),
+    encoded by normal_map_to_rgb8."""
     PSNRs, ssims = [], []
+    normal_maps = bool(normal_maps) and savePath is not None
     if savePath is not None:
         os.makedirs(savePath + "/rgbd", exist_ok=True)
+    if normal_maps:
+        os.makedirs(savePath + "/normal", exist_ok=True)
     near_far = test_dataset.near_far
     n = test_dataset.all_rays.shape[0]
     interval = 1 if N_vis < 0 else max(n // N_vis, 1)
@@ -193,7 +213,7 @@ def evaluation(test_dataset, tensorf, args, renderer, savePath=None, N_vis=5, pr
 
     def finish(idx, handle, n_metrics):
         arrs = fetch.finish(handle)
-        rgb, depth, metrics = arrs[0], arrs[1], arrs[2:]
+        rgb, depth, metrics = arrs[0], arrs[1], arrs[2:2 + n_metrics]
         if n_metrics >= 1:
             PSNRs.append(-10.0 * np.log(float(metrics[0])) / np.log(10.0))
         if n_metrics >= 2:
@@ -203,6 +223,8 @@ def evaluation(test_dataset, tensorf, args, renderer, savePath=None, N_vis=5, pr
             depth_vis, _ = visualize_depth_numpy(depth, near_far)
             writer.write(f'{savePath}/{expname}_r_{idx}.png', img)
             writer.write(f'{savePath}/rgbd/{prtx}{idx:03d}.png', np.concatenate((img, depth_vis), axis=1))
+            if normal_maps:
+                writer.write(f'{savePath}/normal/{prtx}{idx:03d}.png', arrs[2 + n_metrics])
 
     pending = None                                                   # one frame of lookahead: frame k is post-processed on the host while frame k + 1 renders
     for idx, samples in enumerate(test_dataset.all_rays[0::interval]):
@@ -215,7 +237,8 @@ def evaluation(test_dataset, tensorf, args, renderer, savePath=None, N_vis=5, pr
             metrics.append(torch.mean((rgb_dev - gt) ** 2))
             if compute_extra_metrics:
                 metrics.append(_rgb_ssim_dev(rgb_dev, gt, 1))                # utils.py:73-119 on the device
-        handle = fetch.start(rgb_dev, depth_map.reshape(H, W), *metrics)
+        extra = [_normal_frame(tensorf, rays, N_samples, white_bg, H, W)] if normal_maps else []
+        handle = fetch.start(rgb_dev, depth_map.reshape(H, W), *metrics, *extra)
         if pending is not None:
             finish(*pending)
         pending = (idx, handle, len(metrics))
@@ -234,9 +257,13 @@ def evaluation(test_dataset, tensorf, args, renderer, savePath=None, N_vis=5, pr
 
 @torch.no_grad()
 def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath=None, N_vis=5, prtx='', N_samples=-1, white_bg=False, ndc_ray=False,
-                    compute_extra_metrics=True, device='cuda'):
+                    compute_extra_metrics=True, device='cuda', normal_maps=False):
+    """normal_maps: as in evaluation."""
+    normal_maps = bool(normal_maps) and savePath is not None
     if savePath is not None:
         os.makedirs(savePath + "/rgbd", exist_ok=True)
+    if normal_maps:
+        os.makedirs(savePath + "/normal", exist_ok=True)
     W, H = test_dataset.img_wh
     focal = test_dataset.focal
     dirs = R.get_ray_directions(H, W, [focal, focal])
@@ -246,20 +273,24 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath=None, N_vis=
     fetch = _FrameFetch(device)
 
     def finish(idx, handle):
-        rgb, depth = fetch.finish(handle)
+        arrs = fetch.finish(handle)
+        rgb, depth = arrs[0], arrs[1]
         img = (rgb * 255).astype('uint8')
         frames.append(img)
         if savePath is not None:
             depth_vis, _ = visualize_depth_numpy(depth, test_dataset.near_far)
             writer.write(f'{savePath}/{prtx}{idx:03d}.png', img)
             writer.write(f'{savePath}/rgbd/{prtx}{idx:03d}.png', np.concatenate((img, depth_vis), axis=1))
+            if normal_maps:
+                writer.write(f'{savePath}/normal/{prtx}{idx:03d}.png', arrs[2])
 
     pending = None
     for idx, c2w in enumerate(c2ws):
         o, d = R.get_rays(dirs, np.asarray(c2w, dtype=np.float32))
         rays = torch.from_numpy(np.ascontiguousarray(np.concatenate([o, d], 1), dtype=np.float32)).to(device)
         rgb_map, _, depth_map, _, _ = renderer(rays, tensorf, chunk=8192, N_samples=N_samples, ndc_ray=ndc_ray, white_bg=white_bg, device=device)
-        handle = fetch.start(rgb_map.clamp(0.0, 1.0).reshape(H, W, 3), depth_map.reshape(H, W))
+        extra = [_normal_frame(tensorf, rays, N_samples, white_bg, H, W)] if normal_maps else []
+        handle = fetch.start(rgb_map.clamp(0.0, 1.0).reshape(H, W, 3), depth_map.reshape(H, W), *extra)
         if pending is not None:
             finish(*pending)
         pending = (idx, handle)

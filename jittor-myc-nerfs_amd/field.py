@@ -789,16 +789,8 @@ class TensorBase(torch.nn.Module):
         half_width: one number or three (x, y, z), in normalised units; None = one cell of the field's own grid per axis, 2 / (gridSize_k - 1)."""
         x = self._device_points(xyz_sampled, "compute_density_gradient")
         sc = self._ensure_scene()
-        if half_width is None:
-            hw = [2.0 / (int(g) - 1) for g in self.gridSize]
-        elif hasattr(half_width, "__len__"):
-            hw = [float(v) for v in half_width]
-            if len(hw) != 3:
-                raise ValueError(f"half_width takes one number or three (x, y, z); got {len(hw)}")
-        else:
-            hw = [float(half_width)] * 3
-        h = (C.c_float * 3)(*hw)
-        sigma = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
+        h = (C.c_float * 3)(*self._half_widths(half_width))
+        sigma =torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
         grad = torch.empty((x.shape[0], 3), dtype=torch.float32, device=self.device)
         L.check(L.lib().tvr_density_gradient(sc, x.data_ptr(), x.shape[0], C.byref(h), sigma.data_ptr(), L.nbytes(sigma), grad.data_ptr(), L.nbytes(grad),
                                              _stream_ptr(self.device)), "tvr_density_gradient")
@@ -1030,6 +1022,56 @@ class TensorBase(torch.nn.Module):
                                None if dn is None else C.byref(dn), None if stats is None else stats.data_ptr(),
                                profile, _stream_ptr(self.device)), "tvr_render")
         return (rgb, depth, out) if dense else (rgb, depth)
+
+    NORMALS_SCRATCH_BOUND = 1 << 30            # render_normals(chunk=None): the rays per C call are chosen so that the scratch stays at or below 1 GiB
+
+    def _half_widths(self, half_width):
+        """compute_density_gradient's reading of half_width: None = one cell of the field's own grid per axis, one number, or three (x, y, z)."""
+        if half_width is None:
+            return [2.0 / (int(g) - 1) for g in self.gridSize]
+        if hasattr(half_width, "__len__"):
+            hw = [float(v) for v in half_width]
+            if len(hw) != 3:
+                raise ValueError(f"half_width takes one number or three (x, y, z); got {len(hw)}")
+            return hw
+        return [float(half_width)] * 3
+
+    @torch.no_grad()
+    def render_normals(self, rays, N_samples=-1, jitter=None, eps_T=None, half_width=None, chunk=None):
+        """(normal [N,3], acc [N], depth [N]) of a ray batch (tvr_render_normals): render_rays' march, then one kernel that sums, per ray, weight x unit normal over
+        the ray's appearance samples — normal = surface_normals' value at the sample (-grad / |grad| of the density feature for `half_width`, world space).  The sum
+        is NOT renormalised: |normal| <= acc, a ray that hits nothing gives 0 (evaluation.normal_map_to_rgb8 makes the picture).  acc and depth are render_rays' own.
+        chunk: rays per C call (None: as many as keep the scratch at or below NORMALS_SCRATCH_BOUND); the result is bit-identical whatever the chunk."""
+        sc = self._ensure_scene()
+        lib = L.lib()
+        r = _f32c(rays, self.device)
+        if r.dim() != 2 or r.shape[1] != 6:
+            raise ValueError(f"rays must be [N,6] (origin, direction); got {tuple(r.shape)}")
+        n = r.shape[0]
+        S = int(N_samples) if N_samples > 0 else self.nSamples
+        h = (C.c_float * 3)(*self._half_widths(half_width))
+        if eps_T is None:
+            eps_T = self.eps_T if self.eps_T is not None else float(self.rayMarch_weight_thres)
+        jit = None if jitter is None else _f32c(jitter, self.device).view(-1)
+        if jit is not None and jit.shape[0] != n:
+            raise ValueError("jitter must hold one value per ray")
+        normal = L.dev_empty((n, 3), torch.float32, self.device, "tvr_render_normals normal_out")
+        acc = L.dev_empty((n,), torch.float32, self.device, "tvr_render_normals acc_out")
+        depth = L.dev_empty((n,), torch.float32, self.device, "tvr_render_normals depth_out")
+        if n == 0:
+            return normal, acc, depth
+        if chunk is None:
+            per_ray = lib.tvr_render_normals_scratch_bytes(sc, 4096, S) / 4096.0
+            chunk = max(256, int(self.NORMALS_SCRATCH_BOUND / per_ray) // 256 * 256)
+        chunk = max(1, min(int(chunk), n, ((1 << 32) - 1) // S))
+        scratch = self._get_scratch(lib.tvr_render_normals_scratch_bytes(sc, chunk, S))
+        for a in range(0, n, chunk):
+            b = min(a + chunk, n)
+            L.check(lib.tvr_render_normals(sc, r[a:b].data_ptr(), b - a, S, None if jit is None else jit[a:b].data_ptr(), float(eps_T), C.byref(h),
+                                           normal[a:b].data_ptr(), L.nbytes(normal[a:b]), acc[a:b].data_ptr(), L.nbytes(acc[a:b]),
+                                           depth[a:b].data_ptr(), L.nbytes(depth[a:b]), scratch.data_ptr(), scratch.numel(), _stream_ptr(self.device)),
+                    "tvr_render_normals")
+        return normal, acc, depth
 
     def forward(self, rays_chunk, white_bg=True, is_train=False, ndc_ray=False, N_samples=-1, additional_output=False):
         """TensorBase.execute (tensorBase.py:476-536)."""

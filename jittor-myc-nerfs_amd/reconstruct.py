@@ -85,6 +85,8 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # (not reference options) per-vertex normals (nx ny nz) / colours (red green blue) in the exported PLY; 0 = the reference's bare geometry
     p.add_argument("--mesh_normals", type=int, default=0)
     p.add_argument("--mesh_colors", type=int, default=0)
+    # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
+    p.add_argument("--render_normals", type=int, default=0)
     for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int), ("mesh_grid", int)):
         p.add_argument("--" + name, type=typ, action="append")
     argv = sys.argv[1:] if cmd is None else list(cmd)
@@ -137,6 +139,15 @@ def _build_from_ckpt(args, ckpt, device):
     return tensorf, kwargs
 
 
+def _normal_maps_wanted(args) -> bool:
+    """--render_normals 1, refused where the model has no normal pass (NerfPlusPlus places its samples itself: TensorBase.render_normals)."""
+    if not getattr(args, "render_normals", 0):
+        return False
+    if args.model_name == "NerfPlusPlus":
+        raise NotImplementedError("--render_normals 1: normal maps are not built for NerfPlusPlus (its samples lie at explicit depths; the normal pass marches uniform steps)")
+    return True
+
+
 @torch.no_grad()
 def render_test(args, device="cuda"):
     """train.py:62-110."""
@@ -148,16 +159,17 @@ def render_test(args, device="cuda"):
         print("the ckpt path does not exists!!")
         return None
     tensorf, _ = _build_from_ckpt(args, load_checkpoint(args.ckpt), device)
+    normal_maps = _normal_maps_wanted(args)
     logfolder = os.path.dirname(args.ckpt)
     out = {}
     if args.render_test:
         out["test"] = evaluation(test_dataset, tensorf, args, OctreeRender_trilinear_fast, f"{logfolder}/imgs_test_all/", N_vis=-1, N_samples=-1,
-                                 white_bg=test_dataset.white_bg, ndc_ray=args.ndc_ray, device=device)
+                                 white_bg=test_dataset.white_bg, ndc_ray=args.ndc_ray, device=device, normal_maps=normal_maps)
         print(f"======> {args.expname} test all psnr: {np.mean(out['test'])} <========================")
     if args.render_path:
         out["path"] = evaluation_path(test_dataset, tensorf, [p.numpy() for p in test_dataset.poses], OctreeRender_trilinear_fast,
                                       f"{logfolder}/imgs_path_all/", N_vis=-1, N_samples=-1, white_bg=test_dataset.white_bg, ndc_ray=args.ndc_ray,
-                                      device=device)
+                                      device=device, normal_maps=normal_maps)
     return out
 
 
@@ -196,6 +208,7 @@ def reconstruction(args, device="cuda", log=print, train_dataset=None, val_datas
         raise NotImplementedError(f"model_name {args.model_name!r} is outside the accelerated path (TensorVMSplit, REFTensoRF, NerfPlusPlus)")
     if args.ndc_ray:
         raise NotImplementedError("ndc_ray datasets are not part of the reference's loaders")
+    normal_maps = _normal_maps_wanted(args)                              # (refused before any training, not after it)
     if train_dataset is None:
         train_dataset = BlenderRays(args.datadir, split="train", downsample=args.downsample_train, is_stack=False, bbox=_bbox(args), near=args.near,
                                     far=args.far, white_bg=args.white_bkgd)
@@ -341,7 +354,7 @@ def reconstruction(args, device="cuda", log=print, train_dataset=None, val_datas
         if len(test_dataset.all_rgbs):
             with torch.no_grad():
                 PSNRs_test = evaluation(test_dataset, tensorf, args, OctreeRender_trilinear_fast, f"{logfolder}/imgs_test_all/", N_vis=-1,
-                                        N_samples=-1, white_bg=white_bg, ndc_ray=False, device=device)
+                                        N_samples=-1, white_bg=white_bg, ndc_ray=False, device=device, normal_maps=normal_maps)
             log(f"======> {args.expname} test all psnr: {np.mean(PSNRs_test)} <========================")
     return tensorf, logfolder, PSNRs_test
 

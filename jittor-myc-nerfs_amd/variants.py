@@ -246,6 +246,10 @@ class NerfPlusPlus(TensorVMSplit):
         super().__init__(aabb, gridSize, device, **kargs)
         self.bg_net = None
 
+    def render_normals(self, rays, N_samples=-1, jitter=None, eps_T=None, half_width=None, chunk=None):
+        raise NotImplementedError("NerfPlusPlus.render_normals: the normal pass marches uniform steps from the box entry (tvr_render_normals); NerfPlusPlus places "
+                                  "its samples itself (explicit depths, tvr_render_z), and normal maps are not built for it")
+
     def set_nerfplusplus(self, bg_freq=4, bg_view_freq=2, bg_D=4, radii=20):                  # :147-163
         self.bg_freq, self.bg_view_freq, self.radii, self.bg_D = bg_freq, bg_view_freq, radii, bg_D
         self.bg_embedder_position = Embedder(input_dim=4, max_freq_log2=bg_freq - 1, N_freqs=bg_freq)
