@@ -132,13 +132,14 @@ size_t tvr_cp_scene_packed_bytes(const tvr_scene_desc *desc);
 int tvr_cp_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out);
 /* CONCURRENCY: a scene's packed images are shared by every call that names the scene.  Any number of tvr_render(_z) calls may be in flight on different streams at once as
  * long as each has its own scratch and output buffers (they only READ the scene; render.py::FrameStream keeps two frames in flight this way).  Whatever WRITES the scene's
- * device state — tvr_scene_update, tvr_scene_set_alpha, tvr_scene_validate_arith, the first TVR_ARITH_F16 render after an update (it converts the fp16 copies) — must be
+ * device state — tvr_scene_update, tvr_scene_set_alpha, tvr_scene_validate_arith, the first TVR_ARITH_F16 render after an update (it converts the fp16 copies), the first
+ * render after an update of a scene with a density volume (it bakes the volume), tvr_scene_set_density_volume — must be
  * ordered by the caller against every call still reading it (stream waits or events); the library inserts no cross-stream synchronisation. */
 /* tvr_scene_update captured into a hipGraph (a whole training step, tvr_train_forward's host does that): every REPLAY re-packs the fp32 images on the device and runs no
  * host code, so whatever the host derived from "the parameters as last packed" is stale afterwards — (a) a range proof that switched the fp16-range check off
  * (tvr_scene_set_range_check(scene, 0)): switch it back on, or prove again, before rendering; (b) the fp16 copies of the appearance factors that TVR_ARITH_F16 gathers
  * (converted by an un-captured update or by the first render in that mode): call tvr_scene_touch() before the next render, which then converts first.
- * tvr_scene_touch: "the packed fp32 images were rewritten behind the host's back" — marks every derived copy stale.  Host-only, no launch. */
+ * tvr_scene_touch: "the packed fp32 images were rewritten behind the host's back" — marks every derived copy (the fp16 copies, the density volume) stale.  Host-only, no launch. */
 int tvr_scene_touch(tvr_scene *scene);
 /* AlphaGridMask (tensorBase.py:39-59): volume (gz,gy,gx) fp32 (non-negative) in device memory, kept by reference; NULL clears.
  * bits (optional, tvr_alpha_bits_bytes() of device memory, kept by reference): the march then tests `sample_alpha(p) > 0` (:491-496) on a
@@ -146,6 +147,31 @@ int tvr_scene_touch(tvr_scene *scene);
 size_t tvr_alpha_bits_bytes(const int32_t agrid_xyz[3]);
 int tvr_scene_set_alpha(tvr_scene *scene, const float *alpha_volume_dev, const int32_t agrid_xyz[3],
                         const float alpha_aabb[6], const float alpha_inv_size[3], void *bits, size_t bits_bytes, void *stream);
+/* BAKED DENSITY VOLUME (inference).  The density feature  sum_i sum_c bilinear(plane_ic)(u,v) * linear(line_ic)(w)  is, inside a grid cell, exactly the trilinear
+ * interpolation of the eight corner values  D[z][y][x] = sum_i sum_c plane_ic * line_ic  (a bilinear function times a linear one of the third coordinate is trilinear;
+ * the march already uses one cell index and one weight per axis for all planes and lines).  D depends on the parameters alone, so a scene may carry it:
+ *   tvr_density_volume_bytes(desc)   (gx+1)(gy+1)(gz+1) fp32, x fastest; the +1 layer is padding (it only ever meets weight 0 and holds 0); 0 for a bad descriptor;
+ *   tvr_scene_set_density_volume(scene, buf, bytes, stream)   attaches `buf` (device memory, the CALLER's, kept by reference like tvr_scene_set_alpha's bits;
+ *                                    256-byte aligned); buf == NULL detaches.  TVR_ERR_INVALID for a NULL scene, TVR_ERR_SCRATCH for a buffer that is too small or
+ *                                    misaligned, TVR_ERR_UNSUPPORTED for a CP scene (tvr_last_error() says which).  If tvr_scene_update has run, the volume is baked
+ *                                    here on `stream`; otherwise by the first render.
+ * ONE EVALUATOR PER SCENE: while a volume is attached EVERY call that runs the render march — tvr_render (with and without `dense`), tvr_render_z,
+ * tvr_render_normals, tvr_scene_validate_arith's probes, the pieces of a call rendered piecewise — takes the density feature from the volume (four loads of two adjacent
+ * floats and seven lerps per sample instead of twelve 64-B texels, six line texels and a 48-term contraction), so whatever was bit-identical between those calls still is.
+ * With no volume attached the factored kernels run, unchanged.  The training forwards (tvr_march_forward(_z), tvr_train_forward), tvr_density_feature,
+ * tvr_density_gradient and tvr_alpha_* always evaluate the factored form.  The two forms differ by fp32 rounding only (against fp64 on a 128^3 scene, |feature| <= 41:
+ * factored 4.2e-6, volume 6.4e-6 max abs); a sample whose weight sits within that of weight_thres may enter or leave the appearance queue (about 1e-4 on its pixel).
+ * BAKE: one kernel, every value the fp64 sum of the 48 exact products in a fixed order, rounded once; it reads the packed images, i.e. what the factored march reads.
+ * STALENESS: tvr_scene_update and tvr_scene_touch only mark the volume stale (a training step that never renders pays nothing); the next call that runs the render
+ * march bakes first, on ITS stream (in a call rendered piecewise: before the fork), and records an event; a later call on a DIFFERENT stream waits on that event, so
+ * a second stream never reads a half-baked volume.  The bake WRITES the scene's device state: like the fp16 conversion below it must be ordered by the caller against
+ * calls on other streams still reading the volume (see CONCURRENCY).
+ * STREAM CAPTURE (as for the fp16 copies, tvr_scene_set_arith): a hipGraph that captured a render bakes in whether a volume was attached and whether a bake was due.
+ * A render captured while the volume is stale captures the bake in front of its march — every replay bakes again — and the volume STAYS marked stale (a capture runs
+ * nothing), so the next un-captured render bakes too.  Under capture no event is recorded or waited on: bring the volume up to date (one un-captured render, or the
+ * attach itself) and synchronise before capturing on another stream.  Capture again after attaching or detaching.  ADDITIVE exports: TVR_VERSION is unchanged. */
+size_t tvr_density_volume_bytes(const tvr_scene_desc *desc);
+int tvr_scene_set_density_volume(tvr_scene *scene, void *volume_dev, size_t volume_bytes, void *stream);
 /* fp16-range check of the inference entry points (tvr_render(_z), tvr_app_feature(_ref), tvr_mlp_render(_ref)); ON when a scene is created.
  * ON: every value that enters a matrix product through the fp16 hi / lo split is held against fp16's largest finite value on the way (one v_max3 per two
  * values, ~1.5 % of the shade kernel's time); an appearance sample with an operand at or beyond 65 504 gets NaN as its colour / features, so its pixel is NaN,

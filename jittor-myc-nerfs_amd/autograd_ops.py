@@ -383,7 +383,7 @@ class _MarchFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gw, gacc, _gx, _gr, _gd, glam):
         model, lib = ctx.model, L.lib()
-        sc = model._ensure_scene()
+        sc = model._ensure_scene(settle=False)
         grads = [torch.empty(sh, dtype=torch.float32, device=model.device) for sh in ctx.shapes]
         out = L.VmGrads()
         for i in range(3):
@@ -412,7 +412,7 @@ class _AppHFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, xyz, *app_params):
-        sc = model._ensure_scene()
+        sc = model._ensure_scene(settle=False)
         h = torch.empty((xyz.shape[0], 144), dtype=torch.float32, device=model.device)       # the kernels' layout: 3 planes x 48 channels (zero behind a plane's own components)
         L.check(L.lib().tvr_app_h_forward(sc, xyz.data_ptr(), xyz.shape[0], h.data_ptr(), L.nbytes(h), _stream_ptr(model.device)), "tvr_app_h_forward")
         ctx.model, ctx.xyz = model, xyz
@@ -422,7 +422,7 @@ class _AppHFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh):
         model = ctx.model
-        sc = model._ensure_scene()
+        sc = model._ensure_scene(settle=False)
         grads = [torch.empty(sh, dtype=torch.float32, device=model.device) for sh in ctx.shapes]
         out = L.VmGrads()
         for i in range(3):
@@ -442,7 +442,7 @@ class _MlpTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, h, viewdirs, basis_w, W1, b1, W2, b2, W3, b3):
         lib = L.lib()
-        sc = model._ensure_scene()                     # packed by _MarchFn.forward of this step
+        sc = model._ensure_scene(settle=False)                     # packed by _MarchFn.forward of this step
         dev = h.device
         m = h.shape[0]
         h = h.contiguous()
@@ -513,7 +513,7 @@ class _RefMlpTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, h, viewdirs, basis_w, nW, nb, dW, db, sW, sb, rW, rb_, W1, b1, W2, b2, W3, b3):
         lib = L.lib()
-        sc = model._ensure_scene()
+        sc = model._ensure_scene(settle=False)
         dev, m = h.device, h.shape[0]
         h = h.contiguous()
         vd = viewdirs.detach().contiguous().float()
@@ -640,7 +640,7 @@ class _FusedStepFn(torch.autograd.Function):
                                "batches, or two renders in one loss): its saved activations are gone.  Use model.static_training = False for such loops, or call "
                                "backward() before the next forward — render_rays_autograd() does the former by itself when it can see the outstanding forward")
         B["pending"] = None
-        sc = model._ensure_scene()
+        sc = model._ensure_scene(settle=False)
         net = [t.detach().contiguous().float() for t in ctx.saved_tensors]
         dev, n = model.device, ctx.rays.shape[0]
         grads = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes]

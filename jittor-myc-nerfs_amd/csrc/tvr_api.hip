@@ -131,6 +131,12 @@ struct tvr_scene {
     hipStream_t side[2];
     hipEvent_t ev_fork, ev_join[2];
     bool side_ready;
+    // the baked density volume (tvr_scene_set_density_volume): the caller's memory; `dvol_stale`: the packed density factors are newer than the volume — the next call
+    // that launches the render march bakes first, on ITS stream, and records ev_dvol; a later call on another stream waits on that event (ensure_dvol)
+    float *dvol;
+    bool dvol_stale, dvol_recorded;
+    hipStream_t dvol_stream;
+    hipEvent_t ev_dvol;
 };
 
 struct tvr_profile {
@@ -254,6 +260,11 @@ static int scene_create_impl(const tvr_scene_desc *desc, void *packed_dev, size_
     s->side[0] = s->side[1] = nullptr;
     s->ev_fork = s->ev_join[0] = s->ev_join[1] = nullptr;
     s->side_ready = false;
+    s->dvol = nullptr;
+    s->dvol_stale = true;
+    s->dvol_recorded = false;
+    s->dvol_stream = nullptr;
+    s->ev_dvol = nullptr;
     SceneDev &v = s->dev;
     memset(&v, 0, sizeof(v));
     for (int k = 0; k < 3; ++k) {
@@ -369,6 +380,7 @@ int tvr_scene_update(tvr_scene *s, const tvr_scene_params *p, void *stream_)
     }
     s->params_set = true;
     s->h16_stale = true;                  // (the first render in TVR_ARITH_F16 converts the fp16 copies: nothing is converted for steps that never read them)
+    s->dvol_stale = true;                 // (likewise the density volume: the next render bakes it — a training step that never renders pays nothing)
     s->arith_valid = 0;                   // new parameters: a reduced arithmetic has to be measured again before it runs (tvr_scene_validate_arith)
     s->dev.arith = TVR_ARITH_F32;
     return TVR_OK;
@@ -414,6 +426,7 @@ int tvr_scene_touch(tvr_scene *s)
 {
     if (!s) return fail(TVR_ERR_INVALID, "tvr_scene_touch: scene is NULL");
     s->h16_stale = true;         // the next TVR_ARITH_F16 render converts the fp32 images first
+    s->dvol_stale = true;        // and the next render of a scene with a density volume bakes it first
     s->arith_valid = 0;          // and a reduced arithmetic has to be validated again
     s->dev.arith = TVR_ARITH_F32;
     return TVR_OK;
@@ -468,7 +481,67 @@ int tvr_scene_destroy(tvr_scene *s)
         }
         if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     }
+    if (s && s->ev_dvol) (void)hipEventDestroy(s->ev_dvol);
     delete s;
+    return TVR_OK;
+}
+
+}  // extern "C"
+
+static size_t density_volume_values(const tvr_scene_desc &d)
+{
+    return ((size_t)d.grid[0] + 1) * ((size_t)d.grid[1] + 1) * ((size_t)d.grid[2] + 1);
+}
+
+// Called by every entry that launches the render march, on the caller's stream and in front of any fork: brings the attached density volume up to date and orders
+// this stream behind the bake.  Stale: bake here (a KERNEL, see tvr_scene_update's note on graph replays) and record ev_dvol.  Fresh, but baked on another stream:
+// wait on ev_dvol, so a second stream (render.FrameStream) never reads a half-baked volume.  Under stream capture (tvr.h): a stale volume's bake is captured in front of
+// the march — every replay bakes again — and the flag STAYS set, because nothing has run yet: the next un-captured render bakes too; no event is recorded or waited on.
+static int ensure_dvol(tvr_scene *s, hipStream_t stream)
+{
+    if (!s->dvol) return TVR_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    if (s->dvol_stale) {
+        HIP_TRY(launch_density_volume(s->dev, s->dvol, stream));
+        if (capturing) return TVR_OK;
+        if (!s->ev_dvol) HIP_TRY(hipEventCreateWithFlags(&s->ev_dvol, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(s->ev_dvol, stream));
+        s->dvol_recorded = true;
+        s->dvol_stream = stream;
+        s->dvol_stale = false;
+    } else if (!capturing && s->dvol_recorded && stream != s->dvol_stream) {
+        HIP_TRY(hipStreamWaitEvent(stream, s->ev_dvol, 0));
+    }
+    return TVR_OK;
+}
+
+extern "C" {
+
+size_t tvr_density_volume_bytes(const tvr_scene_desc *desc)
+{
+    if (check_desc(desc) != TVR_OK) return 0;
+    return density_volume_values(*desc) * sizeof(float);
+}
+
+int tvr_scene_set_density_volume(tvr_scene *s, void *buf, size_t bytes, void *stream)
+{
+    if (!s) return fail(TVR_ERR_INVALID, "tvr_scene_set_density_volume: scene is NULL");
+    if (!buf) {                            // detach: the shipped (factored) march runs from the next call on
+        s->dvol = nullptr;
+        s->dvol_stale = true;
+        s->dvol_recorded = false;
+        return TVR_OK;
+    }
+    NOT_CP(s);
+    const size_t need = density_volume_values(s->desc) * sizeof(float);
+    if (bytes < need) return fail(TVR_ERR_SCRATCH, "tvr_scene_set_density_volume: buffer %zu B < required %zu B", bytes, need);
+    if ((uintptr_t)buf % 256) return fail(TVR_ERR_SCRATCH, "tvr_scene_set_density_volume: buffer must be 256-byte aligned");
+    s->dvol = (float *)buf;
+    s->dvol_stale = true;
+    s->dvol_recorded = false;
+    if (s->params_set) return ensure_dvol(s, (hipStream_t)stream);       // parameters are packed: bake now, on the caller's stream
     return TVR_OK;
 }
 
@@ -583,7 +656,7 @@ static int render_one(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S
         if (ev) HIP_TRY(hipEventRecord(ev[3], stream));
         return TVR_OK;
     }
-    HIP_TRY(launch_march(s->dev, rays, (int)n_rays, S, sm, eps_T, mo, dense, stream));
+    HIP_TRY(launch_march(s->dev, rays, (int)n_rays, S, sm, eps_T, mo, dense, stream, s->dvol));
     if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
     ShadeArgs sa;
     memset(&sa, 0, sizeof(sa));
@@ -637,6 +710,10 @@ static int render_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     if (s->dev.arith == TVR_ARITH_F16 && !s->dev.gen && s->h16_stale) {        // the mode was set after the last tvr_scene_update
         int rc16 = refresh_h16(s, stream);
         if (rc16 != TVR_OK) return rc16;
+    }
+    if (!s->cp) {                          // the density volume, if one is attached: current, and this stream behind its bake, before anything forks
+        int rcv = ensure_dvol(s, stream);
+        if (rcv != TVR_OK) return rcv;
     }
     // the per-sample outputs of `dense` are a debugging / parity surface ([n,S,*] arrays): such calls stay one launch set
     const PiecePlan P = dense ? PiecePlan{1, n_rays} : piece_plan(s, n_rays);
@@ -1561,6 +1638,10 @@ int tvr_render_normals(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     if (!scratch || scratch_bytes < L.total) return fail(TVR_ERR_SCRATCH, "tvr_render_normals: scratch %zu B < required %zu B", scratch_bytes, L.total);
     if ((uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "tvr_render_normals: scratch must be 256-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
+    if (!s->cp) {                          // the same march as tvr_render's: the density volume, if one is attached
+        int rcv = ensure_dvol(s, stream);
+        if (rcv != TVR_OK) return rcv;
+    }
     char *b = (char *)scratch;
     MarchOut mo;
     mo.counter = (unsigned *)(b + L.counter);
@@ -1577,7 +1658,7 @@ int tvr_render_normals(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     const MarchSampling sm = {jitter, nullptr};
     HIP_TRY(launch_zero_header(mo.counter, stream));                   // [0] queue length, [1] the march's tile counter, [2] its fault flag, [16] the normal pass's ray tickets
     if (s->cp) HIP_TRY(launch_cp_march(s->dev, s->cpd, rays, (int)n_rays, S, sm, eps_T, mo, nullptr, stream));
-    else HIP_TRY(launch_march(s->dev, rays, (int)n_rays, S, sm, eps_T, mo, nullptr, stream));
+    else HIP_TRY(launch_march(s->dev, rays, (int)n_rays, S, sm, eps_T, mo, nullptr, stream, s->dvol));
     HIP_TRY(launch_normals(s->dev, s->cp ? &s->cpd : nullptr, mo, (int)n_rays, half_width, inv2h, normal_out, acc_out, depth_out, stream));
     return TVR_OK;
 }

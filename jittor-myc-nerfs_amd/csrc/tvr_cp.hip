@@ -17,7 +17,8 @@ template <bool DENSE>
 __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void cp_march_kernel(const SceneDev sc, const CpDev cp, const float *__restrict__ rays, const int n_rays, const int S,
                                                                         const int s_cap, const MarchSampling sm, const float eps_T, MarchOut mo, const tvr_dense_out dn)
 {
-    constexpr bool LDSL = false, CP = true;
+    constexpr bool LDSL = false, CP = true, VOL = false;
+    const float *const dvol = nullptr;
 #include "tvr_march_body.inc"
 }
 

@@ -64,8 +64,11 @@ struct ShadeArgs {
     unsigned long long *stats;
 };
 
+// dvol: the scene's baked density volume (tvr_scene_set_density_volume, baked by launch_density_volume) or nullptr — the render entries pass it, the training forward
+// keeps the factored evaluation
 hipError_t launch_march(const SceneDev &sc, const float *rays, int n_rays, int S, const MarchSampling &sm, float eps_T,
-                        const MarchOut &mo, const tvr_dense_out *dense, hipStream_t stream);
+                        const MarchOut &mo, const tvr_dense_out *dense, hipStream_t stream, const float *dvol = nullptr);
+hipError_t launch_density_volume(const SceneDev &sc, float *out, hipStream_t stream);
 hipError_t launch_composite(const MarchOut &mo, int n_rays, int white_bg, float *rgb, hipStream_t stream);
 hipError_t launch_scatter_rgb(const MarchOut &mo, int S, float *rgb_dense, hipStream_t stream);
 hipError_t launch_density_feature(const SceneDev &sc, const float *xyz, long long m, float *out, hipStream_t stream);

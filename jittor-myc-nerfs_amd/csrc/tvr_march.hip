@@ -36,9 +36,57 @@ __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const Scene
                                                                      const MarchSampling sm, const float eps_T,
                                                                      MarchOut mo, const tvr_dense_out dn)
 {
-    constexpr bool CP = false;                            // the body is shared with the CP march (tvr_cp.hip) as text
+    constexpr bool CP = false, VOL = false;               // the body is shared with the CP march (tvr_cp.hip) and the volume march (below) as text
+    const CpDev cp = {};
+    const float *const dvol = nullptr;
+#include "tvr_march_body.inc"
+}
+
+// The march of a scene with a baked density volume (tvr_scene_set_density_volume): the same body, the density feature from vol_density (tvr_march_body.h) — 32 B per
+// sample through L1 instead of 768 B and 384 B of LDS, seven lerps instead of three 16-channel bilinear / linear products and two quad reductions.  No line image in LDS:
+// a group needs its header and 6 B per sample and wave; the launch shape and why: tvr_march_body.h (MARCH_VOL_*), DESIGN.md 4.1.
+template <bool DENSE>
+__global__ __launch_bounds__(64 * MARCH_VOL_WAVES, DENSE ? MARCH_VOL_OCC - 1 : MARCH_VOL_OCC) void march_vol_kernel(const SceneDev sc, const float *__restrict__ dvol, const float *__restrict__ rays,
+                                                                         const int n_rays, const int S, const int s_cap, const MarchSampling sm, const float eps_T,
+                                                                         MarchOut mo, const tvr_dense_out dn)
+{
+    constexpr bool LDSL = false, CP = false, VOL = true;
     const CpDev cp = {};
 #include "tvr_march_body.inc"
+}
+
+// The bake: one thread per value of D, x fastest.  The 48 products plane_i[c] * line_i[c] (i = 0, 1, 2; c = 0 .. 15, in that order) are exact in fp64 and are summed in
+// fp64, one rounding to fp32 at the end.  It reads the PACKED planes and lines (zero pad texel at index grid, zero pad channels), i.e. what the factored march reads, so
+// the padding layer of D is 0.
+__global__ __launch_bounds__(256) void density_volume_kernel(const SceneDev sc, float *__restrict__ out)
+{
+    const long long gx1 = sc.grid[0] + 1, gy1 = sc.grid[1] + 1, gz1 = sc.grid[2] + 1;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= gx1 * gy1 * gz1) return;
+    const long long x = t % gx1, y = (t / gx1) % gy1, z = t / (gx1 * gy1);
+    // plane0 (x,y) . line0(z) ; plane1 (x,z) . line1(y) ; plane2 (y,z) . line2(x)   (matMode / vecMode); plane i is [H+1][W+1] texels of 4 float4
+    const float4 *P[3] = {sc.dplane[0] + (y * gx1 + x) * 4, sc.dplane[1] + (z * gx1 + x) * 4, sc.dplane[2] + (z * gy1 + y) * 4};
+    const float4 *Ln[3] = {sc.dline[0] + z * 4, sc.dline[1] + y * 4, sc.dline[2] + x * 4};
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 p = P[i][g], l = Ln[i][g];
+            acc = acc + (double)p.x * (double)l.x;
+            acc = acc + (double)p.y * (double)l.y;
+            acc = acc + (double)p.z * (double)l.z;
+            acc = acc + (double)p.w * (double)l.w;
+        }
+    }
+    out[t] = (float)acc;
+}
+
+hipError_t launch_density_volume(const SceneDev &sc, float *out, hipStream_t stream)
+{
+    const long long n = ((long long)sc.grid[0] + 1) * ((long long)sc.grid[1] + 1) * ((long long)sc.grid[2] + 1);      // <= 4097^3: fewer than 2^31 blocks
+    hipLaunchKernelGGL(density_volume_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sc, out);
+    return hipGetLastError();
 }
 
 // composite tail (tensorBase.py:520-527): rgb_map = sum_j w_j*rgb_j (+ 1-acc if white_bg), clamp(0,1).
@@ -213,9 +261,34 @@ static int device_cu_count()
 
 int march_cu_count() { return device_cu_count(); }
 
-hipError_t launch_march(const SceneDev &sc, const float *rays, int n_rays, int S, const MarchSampling &sm, float eps_T,
-                        const MarchOut &mo, const tvr_dense_out *dense, hipStream_t stream)
+// the volume march: groups of MARCH_VOL_WAVES waves, MARCH_VOL_GROUPS of them per CU (tvr_march_body.h says why), fewer waves per group (and proportionally more
+// groups) only where the appearance lists (6 B per sample and wave) do not leave room
+static hipError_t launch_march_vol(const SceneDev &sc, const float *dvol, const float *rays, int n_rays, int S, const MarchSampling &sm, float eps_T, const MarchOut &mo,
+                                   const tvr_dense_out *dense, hipStream_t stream)
 {
+    const int groups = MARCH_VOL_GROUPS;                     // per CU
+    const size_t kLds = 160 * 1024 / (size_t)groups, per_wave = (size_t)S * 6, fixed = MARCH_HDR + 64;
+    int waves = (int)((kLds - fixed) / per_wave);
+    waves = waves >= MARCH_VOL_WAVES ? MARCH_VOL_WAVES : (waves >= 8 ? 8 : (waves >= 4 ? 4 : (waves >= 2 ? 2 : 1)));
+    const size_t lds = fixed + (size_t)waves * per_wave;
+    const int n_tiles = (n_rays + MARCH_TILE - 1) / MARCH_TILE;
+    long long grid = (long long)device_cu_count() * groups * (MARCH_VOL_WAVES / waves);
+    if (grid > n_tiles) grid = n_tiles;
+    if (grid < 1) grid = 1;
+    tvr_dense_out none = {};
+    const tvr_dense_out &dn = dense ? *dense : none;
+    hipError_t rc = dense ? hipFuncSetAttribute((const void *)march_vol_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                          : hipFuncSetAttribute((const void *)march_vol_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (rc != hipSuccess) return rc;
+    if (dense) hipLaunchKernelGGL((march_vol_kernel<true>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
+    else hipLaunchKernelGGL((march_vol_kernel<false>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
+    return hipGetLastError();
+}
+
+hipError_t launch_march(const SceneDev &sc, const float *rays, int n_rays, int S, const MarchSampling &sm, float eps_T,
+                        const MarchOut &mo, const tvr_dense_out *dense, hipStream_t stream, const float *dvol)
+{
+    if (dvol) return launch_march_vol(sc, dvol, rays, n_rays, S, sm, eps_T, mo, dense, stream);
     // LDS budget: the density lines (if they fit next to at least 4 waves' lists) + 6 B per sample and wave for the appearance lists
     const size_t kLds = 160 * 1024, line_bytes = ((size_t)sc.grid[0] + sc.grid[1] + sc.grid[2] + 3) * 16 * MARCH_LSTRIDE, per_wave = (size_t)S * 6;
     bool ldsl = MARCH_HDR + line_bytes + 4 * per_wave + 64 <= kLds;

@@ -1,4 +1,4 @@
-// tvr_march_body.h — what the march kernels' shared body (tvr_march_body.inc) needs in front of it: the launch constants and the two density evaluations.  Included by
+// tvr_march_body.h — what the march kernels' shared body (tvr_march_body.inc) needs in front of it: the launch constants and the density evaluations.  Included by
 // tvr_march.hip (march_kernel: TensorVMSplit / REFTensoRF) and tvr_cp.hip (cp_march_kernel: TensorCP).
 #pragma once
 #include "tvr_device.h"
@@ -19,6 +19,22 @@
 #endif
 #ifndef MARCH_TAIL
 #define MARCH_TAIL 4u                     // rays per handout at the end of a launch (16u = off)
+#endif
+// The volume march (march_vol_kernel, tvr_march.hip).  Its launch shape, measured on the 800x800 x 512 bench frame (profiles/density_volume.txt):
+// alone, the kernel takes 5.15 - 5.20 ms whether a CU holds 16, 24 or 32 of its waves (5.50 with 8), so the shape was chosen on the frame rendered in pieces, where the
+// other piece's shade kernel competes for the CUs: 32 / 24 / 16 waves per CU in groups of 8 gave 17.0 / 16.5 / 15.3 - 15.5 ms per frame, one group of 16 waves 15.1, two
+// 16.5, and one group of 16 waves at 65 registers (the 72-register step) 16.4.  Hence ONE group of 16 waves per CU — the factored kernel's shape: a tile's 16 rays march
+// concurrently and share their lines in L1 — compiled for 64 registers (the launch bound asks for 8 waves per SIMD to get that cap, not to run them); why the frame
+// prefers it is not established.  LDS is the header and 6 B per sample and wave (49 KB at 512 samples, where the factored kernel holds 107 KB).  The
+// DENSE form (debugging surface, 70 registers) is compiled for one wave fewer rather than spill to scratch.
+#ifndef MARCH_VOL_WAVES
+#define MARCH_VOL_WAVES 16                // waves per group
+#endif
+#ifndef MARCH_VOL_GROUPS
+#define MARCH_VOL_GROUPS 1                // groups per CU
+#endif
+#ifndef MARCH_VOL_OCC
+#define MARCH_VOL_OCC 8                   // waves per SIMD the kernel's registers are capped for (512 / 8 = 64)
 #endif
 #define MARCH_HDR 560                     // LDS header: ray cursor (16 B) + 64 slots of {local tile number + 1 | tail bit, first ray} (dynamic queue) + 3 u64 statistics sums + pad
 #ifndef MARCH_LSTRIDE
@@ -68,4 +84,22 @@ __device__ __forceinline__ float cp_density_quad(const SceneDev &sc, const CpDev
         part = part + ((tx + ty) + (tz + tw));
     }
     return part;
+}
+
+// The baked density volume (tvr_scene_set_density_volume): D[z][y][x] = sum_i sum_c plane_i[c] * line_i[c] at the grid points, (gx+1)(gy+1)(gz+1) fp32 with x fastest.
+// Inside a cell a bilinear function of two coordinates times a linear one of the third is trilinear, so the factored feature IS the trilinear interpolation of the cell's
+// eight corner values — an identity in exact arithmetic; in fp32 the two forms differ by rounding.  Lane per sample: four row loads of two adjacent
+// floats (4-byte aligned: the pair may start at an odd index), then seven lerps a + w (b - a) in this fixed order — x on the four rows, y on the two z layers, z last.
+// A tap at index grid (the padding layer, finite) only ever meets weight 0: fmaf(0, pad - a, a) == a.
+struct __attribute__((packed, aligned(4))) vol_pair { float a, b; };
+__device__ __forceinline__ float vol_density(const float *__restrict__ D, int gx1, int gy1, int ix, int iy, int iz, float wx, float wy, float wz)
+{
+    const size_t sy = (size_t)gx1, sz = (size_t)gx1 * (size_t)gy1;        // a volume of the largest grid the ABI admits has 4097^3 values: 64-bit indices
+    const float *r = D + ((size_t)iz * sz + (size_t)iy * sy + (size_t)ix);
+    const vol_pair p00 = *(const vol_pair *)r, p01 = *(const vol_pair *)(r + sy);
+    const vol_pair p10 = *(const vol_pair *)(r + sz), p11 = *(const vol_pair *)(r + sz + sy);
+    const float c00 = __builtin_fmaf(wx, p00.b - p00.a, p00.a), c01 = __builtin_fmaf(wx, p01.b - p01.a, p01.a);
+    const float c10 = __builtin_fmaf(wx, p10.b - p10.a, p10.a), c11 = __builtin_fmaf(wx, p11.b - p11.a, p11.a);
+    const float c0 = __builtin_fmaf(wy, c01 - c00, c00), c1 = __builtin_fmaf(wy, c11 - c10, c10);
+    return __builtin_fmaf(wz, c1 - c0, c0);
 }

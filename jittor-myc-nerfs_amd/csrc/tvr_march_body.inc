@@ -2,8 +2,10 @@
 // description.  Everything but the density evaluation — ray entry, sampling, in-box / alpha mask, cell indices, the transmittance scan, the queue, the dense outputs, the
 // counters — is this one text, so both kernels produce the same bits for the same rays, box and grid.  (As text and not as an inlined function: the instruction stream of
 // march_kernel is then what it was when the body stood in the kernel itself — a forceinline function taking the kernel's arguments compiled to 20 - 100 more instructions.)
-// Expects in scope: constexpr bool DENSE, LDSL, CP; sc, rays, n_rays, S, s_cap, sm, eps_T, mo, dn (the kernel's arguments) and `cp` (CpDev; unused unless CP).
+// Expects in scope: constexpr bool DENSE, LDSL, CP, VOL; sc, rays, n_rays, S, s_cap, sm, eps_T, mo, dn (the kernel's arguments), `cp` (CpDev; unused unless CP) and
+// `dvol` (the baked density volume, tvr_scene_set_density_volume; unused unless VOL).
     static_assert(!(CP && LDSL), "the CP lines (up to 96 channels) do not go through LDS");
+    static_assert(!(VOL && (CP || LDSL)), "the baked volume replaces the factored evaluation: no lines in LDS, no CP lines");
     // LDS: [cursor 16 B][lines: 3 x (L+1) x 4 float4, LDSL only][per-wave weight lists f32 s_cap][per-wave sample lists u16 s_cap]
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int lane = threadIdx.x & 63;
@@ -184,33 +186,39 @@
             tl_chunks++;
 #endif
 
-            // ---- density feature: 4 sub-steps, quad-per-sample gather ----
+            // ---- density feature ----
             float sf = 0.0f;
+            if constexpr (VOL) {
+                // baked volume (tvr_march_body.h: vol_density): lane per sample, the trilinear interpolation of the cell's eight corner values
+                if (valid) sf = vol_density(dvol, sc.grid[0] + 1, sc.grid[1] + 1, i0[0], i0[1], i0[2], w[0], w[1], w[2]);
+            } else {
+                // factored form: 4 sub-steps, quad-per-sample gather
 #pragma unroll
-            for (int k4 = 0; k4 < 4; ++k4) {
-                const bool v = quad_bcast_i((int)valid, k4) != 0;
-                if (__ballot(v) == 0ull) continue;
-                const int ix = quad_bcast_i(i0[0], k4), iy = quad_bcast_i(i0[1], k4), iz = quad_bcast_i(i0[2], k4);
-                const float wx = quad_bcast_f(w[0], k4), wy = quad_bcast_f(w[1], k4), wz = quad_bcast_f(w[2], k4);
-                float part = 0.0f;
-                if constexpr (CP) {
-                    if (v) part = cp_density_quad(sc, cp, ix, iy, iz, wx, wy, wz, sub);
-                } else
-                if (v && LDSL) {
-                    const float4 a = vm_term_lds(sc.dplane[0], ls0, sc.grid[0], ix, iy, iz, wx, wy, wz, sub);
-                    const float4 b = vm_term_lds(sc.dplane[1], ls1, sc.grid[0], ix, iz, iy, wx, wz, wy, sub);
-                    const float4 cc = vm_term_lds(sc.dplane[2], ls2, sc.grid[1], iy, iz, ix, wy, wz, wx, sub);
-                    part = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((cc.x + cc.y) + (cc.z + cc.w));
-                } else if (v) {
-                    // plane0 (x,y)·line0(z) ; plane1 (x,z)·line1(y) ; plane2 (y,z)·line2(x)   (matMode / vecMode)
-                    const float4 a = vm_term<4, false>(sc.dplane[0], sc.dline[0], sc.grid[0], sc.grid[1], sc.grid[2], ix, iy, iz, wx, wy, wz, sub);
-                    const float4 b = vm_term<4, false>(sc.dplane[1], sc.dline[1], sc.grid[0], sc.grid[2], sc.grid[1], ix, iz, iy, wx, wz, wy, sub);
-                    const float4 cc = vm_term<4, false>(sc.dplane[2], sc.dline[2], sc.grid[1], sc.grid[2], sc.grid[0], iy, iz, ix, wy, wz, wx, sub);
-                    part = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((cc.x + cc.y) + (cc.z + cc.w));
+                for (int k4 = 0; k4 < 4; ++k4) {
+                    const bool v = quad_bcast_i((int)valid, k4) != 0;
+                    if (__ballot(v) == 0ull) continue;
+                    const int ix = quad_bcast_i(i0[0], k4), iy = quad_bcast_i(i0[1], k4), iz = quad_bcast_i(i0[2], k4);
+                    const float wx = quad_bcast_f(w[0], k4), wy = quad_bcast_f(w[1], k4), wz = quad_bcast_f(w[2], k4);
+                    float part = 0.0f;
+                    if constexpr (CP) {
+                        if (v) part = cp_density_quad(sc, cp, ix, iy, iz, wx, wy, wz, sub);
+                    } else
+                    if (v && LDSL) {
+                        const float4 a = vm_term_lds(sc.dplane[0], ls0, sc.grid[0], ix, iy, iz, wx, wy, wz, sub);
+                        const float4 b = vm_term_lds(sc.dplane[1], ls1, sc.grid[0], ix, iz, iy, wx, wz, wy, sub);
+                        const float4 cc = vm_term_lds(sc.dplane[2], ls2, sc.grid[1], iy, iz, ix, wy, wz, wx, sub);
+                        part = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((cc.x + cc.y) + (cc.z + cc.w));
+                    } else if (v) {
+                        // plane0 (x,y)·line0(z) ; plane1 (x,z)·line1(y) ; plane2 (y,z)·line2(x)   (matMode / vecMode)
+                        const float4 a = vm_term<4, false>(sc.dplane[0], sc.dline[0], sc.grid[0], sc.grid[1], sc.grid[2], ix, iy, iz, wx, wy, wz, sub);
+                        const float4 b = vm_term<4, false>(sc.dplane[1], sc.dline[1], sc.grid[0], sc.grid[2], sc.grid[1], ix, iz, iy, wx, wz, wy, sub);
+                        const float4 cc = vm_term<4, false>(sc.dplane[2], sc.dline[2], sc.grid[1], sc.grid[2], sc.grid[0], iy, iz, ix, wy, wz, wx, sub);
+                        part = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((cc.x + cc.y) + (cc.z + cc.w));
+                    }
+                    part += quad_perm_f<QUAD_XOR1>(part);
+                    part += quad_perm_f<QUAD_XOR2>(part);
+                    if (sub == k4) sf = part;
                 }
-                part += quad_perm_f<QUAD_XOR1>(part);
-                part += quad_perm_f<QUAD_XOR2>(part);
-                if (sub == k4) sf = part;
             }
 
             float sigma = 0.0f;

@@ -255,6 +255,7 @@ class TensorBase(torch.nn.Module):
         if getattr(self, "_scene", None):
             L.lib().tvr_scene_destroy(self._scene)
         self._scene, self._packed, self._sig = None, None, None
+        self._dvol, self._dvol_refused = None, False      # the scene's baked density volume (_settle_density_volume) goes with the scene
         self._grad_scratch = None
         self._alpha_dirty = True
 
@@ -278,10 +279,15 @@ class TensorBase(torch.nn.Module):
             ps += [lin.weight, lin.bias]
         return ps
 
-    def _ensure_scene(self, force=False):
+    def _ensure_scene(self, force=False, settle=True):
         """Create the tvr_scene on first use and re-pack whenever a parameter tensor was replaced or written in place (detected by
         storage pointer + version counter).  force=True re-packs regardless: the training forward does so every step, because a fused
-        optimizer kernel (torch.optim.Adam(fused=True)) updates the parameters without bumping their version counters."""
+        optimizer kernel (torch.optim.Adam(fused=True)) updates the parameters without bumping their version counters.
+        settle: bring the scene's density volume in line with `density_volume` (_settle_density_volume) before the handle is returned.  The render entry points
+        (render_rays, render_normals) and a caller that takes the handle to the C ABI itself get that — the handle then renders with ONE evaluator whoever calls
+        through it.  Every caller that never runs the render march passes settle=False (and force implies it): the training step, the field queries
+        (compute_densityfeature / _appfeature / _density_gradient, the network call), filtering_rays and with them updateAlphaMask and the mesh helpers — a training
+        run that refreshes its alpha mask allocates and bakes nothing."""
         lib = L.lib()
         if self.device.type != "cuda":
             raise L.TvrError(f"the render path runs on an MI355X (HIP) device only; model device is {self.device}. "
@@ -324,6 +330,7 @@ class TensorBase(torch.nn.Module):
             h = C.c_void_p()
             L.check(create(C.byref(d), self._packed.data_ptr(), nbytes, C.byref(h)), "tvr_cp_scene_create" if self._cp else "tvr_scene_create")
             self._scene = h
+            self._scene_desc = d
             self._sig = None
             self._alpha_dirty = True
             self._arith_set = None
@@ -374,6 +381,8 @@ class TensorBase(torch.nn.Module):
                 raise ValueError(f"mlp_arith must be one of {sorted(self._ARITH)}, got {self.mlp_arith!r}")
             L.check(lib.tvr_scene_set_arith(self._scene, self._ARITH[self.mlp_arith]), "tvr_scene_set_arith")      # a REQUEST: see _settle_arith
             self._arith_set = self.mlp_arith
+        if settle and not force:
+            self._settle_density_volume()
         return self._scene
 
     # ---- the gate of the reduced arithmetics (include/tvr.h, tvr_scene_validate_arith) -----------------------------------------------------
@@ -438,6 +447,43 @@ class TensorBase(torch.nn.Module):
     arith_in_effect = "f32"
     arith_max_diff = None
 
+    # ---- the baked density volume (include/tvr.h, BAKED DENSITY VOLUME) ----------------------------------------------------------------------------------
+    # The inference march of a TensorVMSplit / REFTensoRF scene reads the density feature from a volume of (gx+1)(gy+1)(gz+1) fp32 baked from the density factors
+    # (109 MB at 300^3) instead of contracting 48 plane x line terms per sample: the same function up to fp32 rounding.  `density_volume = False` (class or instance)
+    # turns it off: the factored kernels then run, as before.  The volume is allocated by the first inference render (render_rays / render_normals) and dropped with the scene; the library re-bakes
+    # it after every parameter update, on the first render that follows (the training step pays nothing).
+    density_volume = True
+    DENSITY_VOLUME_MEMORY_SHARE = 4            # the volume may take at most 1/4 of the device memory that is free when it is allocated
+
+    def _settle_density_volume(self):
+        """Called at the end of _ensure_scene() for the render entry points (settle=True): attach / detach the density volume as `density_volume` says.  A host that rendered before keeps
+        rendering: the volume is only allocated if it takes no more than a quarter of what torch.cuda.mem_get_info reports free (plus what torch's allocator holds
+        cached) — the scratch of a full frame (1.3 GB in pieces) and the caller's own buffers are allocated later and must still fit — and an allocation that fails
+        anyway falls back to the factored march, silently, until the scene is re-created."""
+        if self._cp:
+            return
+        lib = L.lib()
+        if not self.density_volume:
+            if self._dvol is not None:
+                L.check(lib.tvr_scene_set_density_volume(self._scene, None, 0, None), "tvr_scene_set_density_volume")
+                self._dvol = None
+            return
+        if self._dvol is not None or self._dvol_refused or torch.cuda.is_current_stream_capturing():
+            return                                                # (nothing is allocated inside a capture: such a model keeps the evaluator it was captured with)
+        need = int(lib.tvr_density_volume_bytes(C.byref(self._scene_desc)))
+        free, _ = torch.cuda.mem_get_info(self.device)
+        cached = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        if need == 0 or need * self.DENSITY_VOLUME_MEMORY_SHARE > free + cached:
+            self._dvol_refused = True
+            return
+        try:
+            vol = L.dev_bytes(need, self.device, what="density volume")
+        except torch.OutOfMemoryError:
+            self._dvol_refused = True
+            return
+        L.check(lib.tvr_scene_set_density_volume(self._scene, vol.data_ptr(), vol.numel(), _stream_ptr(self.device)), "tvr_scene_set_density_volume")
+        self._dvol = vol
+
     render_rays_is_the_frame = True           # render_rays(rays) IS forward(rays, is_train=False) for this class and REFTensoRF (render.FrameStream relies on it)
 
     def scene_settled(self) -> bool:
@@ -448,6 +494,8 @@ class TensorBase(torch.nn.Module):
             return False
         if getattr(self, "_arith_set", None) != self.mlp_arith:
             return False
+        if not self._cp and bool(self.density_volume) != (self._dvol is not None) and not (self.density_volume and self._dvol_refused):
+            return False                                                            # the next call attaches (and bakes) or detaches the density volume
         if tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in self._param_list()) != self._sig:
             return False
         if self.mlp_arith != "f32" and self.view_pe <= 2 and self.fea_pe <= 2:
@@ -567,7 +615,7 @@ class TensorBase(torch.nn.Module):
         L.check(L.lib().tvr_scene_set_range_check(self._scene, 0 if self._range_proven else 1), "tvr_scene_set_range_check")
 
     def _get_grad_scratch(self) -> torch.Tensor:
-        nbytes = L.lib().tvr_grad_scratch_bytes(self._ensure_scene())
+        nbytes = L.lib().tvr_grad_scratch_bytes(self._ensure_scene(settle=False))
         if getattr(self, "_grad_scratch", None) is None or self._grad_scratch.numel() < nbytes:
             self._grad_scratch = L.dev_bytes(nbytes, self.device, what="tvr_grad_scratch")
         return self._grad_scratch
@@ -661,7 +709,7 @@ class TensorBase(torch.nn.Module):
         b = getattr(self, "_train_buf", None)
         if b is None or b["key"] != key:
             lib = L.lib()
-            sc = self._ensure_scene()
+            sc = self._ensure_scene(settle=False)
             self._train_buf = None
             b = dict(key=key, cap=cap,
                      scratch=L.dev_bytes(lib.tvr_render_scratch_bytes(sc, n, S), self.device, zero=True, what="tvr_train_forward scratch"),
@@ -761,7 +809,7 @@ class TensorBase(torch.nn.Module):
 
     # ---- compute entry points ----------------------------------------------------------------------------
     def compute_densityfeature(self, xyz_sampled):                                            # tensoRF.py:209-225
-        sc = self._ensure_scene()
+        sc = self._ensure_scene(settle=False)
         x = _f32c(xyz_sampled, self.device).view(-1, 3)
         out = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
         L.check(L.lib().tvr_density_feature(sc, x.data_ptr(), x.shape[0], out.data_ptr(), L.nbytes(out), _stream_ptr(self.device)),
@@ -769,7 +817,7 @@ class TensorBase(torch.nn.Module):
         return out
 
     def compute_appfeature(self, xyz_sampled):                                                # tensoRF.py:228-244
-        sc = self._ensure_scene()
+        sc = self._ensure_scene(settle=False)
         self._settle_range_check()
         x = _f32c(xyz_sampled, self.device).view(-1, 3)
         out = torch.empty((x.shape[0], self.app_dim), dtype=torch.float32, device=self.device)
@@ -788,7 +836,7 @@ class TensorBase(torch.nn.Module):
         compute_densityfeature's value bit for bit, grad[:, k] = (f(p + h_k e_k) - f(p - h_k e_k)) * (0.5 / h_k), a symmetric difference of that value.
         half_width: one number or three (x, y, z), in normalised units; None = one cell of the field's own grid per axis, 2 / (gridSize_k - 1)."""
         x = self._device_points(xyz_sampled, "compute_density_gradient")
-        sc = self._ensure_scene()
+        sc = self._ensure_scene(settle=False)
         h = (C.c_float * 3)(*self._half_widths(half_width))
         sigma =torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
         grad = torch.empty((x.shape[0], 3), dtype=torch.float32, device=self.device)
@@ -829,7 +877,7 @@ class TensorBase(torch.nn.Module):
         return torch.round(255.0 * rgb.clamp(0, 1)).to(torch.uint8)
 
     def _mlp_render(self, viewdirs, features):
-        sc = self._ensure_scene()
+        sc = self._ensure_scene(settle=False)
         self._settle_range_check()
         v = _f32c(viewdirs, self.device).view(-1, 3)
         f = _f32c(features, self.device).view(-1, self.app_dim)
@@ -955,7 +1003,7 @@ class TensorBase(torch.nn.Module):
         N = int(np.prod(all_rays.shape[:-1]))
         flat = all_rays.reshape(N, all_rays.shape[-1])
         if self.device.type == "cuda" and flat.shape[-1] == 6 and (bbox_only or self.alphaMask is not None):
-            sc = self._ensure_scene()
+            sc = self._ensure_scene(settle=False)
             mask = torch.empty(N, dtype=torch.uint8, device=self.device)
             big = 8 << 20
             for i0 in range(0, N, big):

@@ -87,7 +87,7 @@ class REFTensoRF(TensorVMSplit):
 
     def compute_appfeature(self, xyz_sampled):                                                # :107-133
         """-> (appfeatures [M,27], rgb_d [M,3], specular_tint [M,1], normal_vector [M,3], rho [M,1])"""
-        sc = self._ensure_scene()
+        sc = self._ensure_scene(settle=False)
         x = _f32c(xyz_sampled, self.device).view(-1, 3)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return self._heads(_AppHFn.apply(self, x, *self.app_plane, *self.app_line))
@@ -106,7 +106,7 @@ class REFTensoRF(TensorVMSplit):
                                   "mesh vertex colours are not built for REFTensoRF; normals are (mesh_vertex_attributes(verts, colors=False))")
 
     def _mlp_render_ref(self, viewdirs, features, dot_product):
-        sc = self._ensure_scene()
+        sc = self._ensure_scene(settle=False)
         v = _f32c(viewdirs, self.device).view(-1, 3)
         f = _f32c(features, self.device).view(-1, self.app_dim)
         d = _f32c(dot_product, self.device).view(-1)
@@ -235,6 +235,10 @@ class NerfPlusPlus(TensorVMSplit):
     max_render_chunk = 655360     # rays per merged inference call (renderer): the background holds [rays, 512, ~20] fp32 temporaries — 24 GB for a whole 800x800 frame of the 288 GB
                                   # this card has (round 6: 103.3 -> 98.7 ms per frame against 65 536-ray calls, which also stayed below tvr_render's pieces; lower it on smaller cards)
 
+    # The baked density volume is OFF by default for this model: the host default covers TensorVMSplit / REFTensoRF frames, where it is measured.  This
+    # model's frame is its background network (98.7 ms); what a volume gains on the foreground's explicit-depth march (tvr_render_z) is NOT measured.  The
+    # library serves tvr_render_z from an attached volume like every other render entry (include/tvr.h), so `model.density_volume = True` opts a model in.
+    density_volume = False
     render_rays_is_the_frame = False          # forward() adds the background; render_rays alone is the foreground field (render.FrameStream refuses this model)
 
     def scene_settled(self) -> bool:
