@@ -620,6 +620,39 @@ int tvr_mesh_emit(const float *volume, const int32_t dims[3], float level, const
                   float *verts, size_t verts_bytes, int64_t n_vertices, int32_t *faces, size_t faces_bytes, int64_t n_triangles, int32_t flip,
                   uint32_t *fault_flag_dev, void *stream);
 
+/* Connected components of an indexed triangle mesh and a filter that keeps whole components (csrc/tvr_mesh_cc.hip; the reference writes whatever skimage returns,
+ * utils.py:146-207, so an exported field carries its floaters).  ADDITIVE exports: TVR_VERSION is unchanged.  faces [n_triangles][3] int32 indexes n_vertices vertices.
+ *   Component: two vertices are connected iff a chain of triangles links them (a triangle connects its three vertices); a vertex no triangle uses is a component of
+ *   its own with zero triangles.  Label of a component = its SMALLEST vertex index (a function of the mesh alone).  Size = the triangles whose FIRST vertex carries the label.
+ * tvr_mesh_components: vertex_label [n_vertices] int32 = the label of each vertex's component; component_faces [n_vertices] int32 = at a label (vertex_label[v] == v) the
+ *   component's triangle count, 0 elsewhere; *n_components_dev (int64) = the number of labels.  Union-find over the vertices driven by the triangles: a root is only ever
+ *   hooked under a smaller index, so the root of a finished tree is the component's minimum whatever the order the atomics land in; a flatten pass then writes every
+ *   vertex's root.  scratch: tvr_mesh_components_scratch_bytes (256-byte aligned); its second uint32 holds, after the call, the most steps any one walk took (diagnostic).
+ *   A triangle index outside 0 .. n_vertices-1 sets *fault_flag_dev = 1 and NOTHING else is written (a pass over the triangles precedes every other store); no load or
+ *   store leaves the caller's buffers whatever `faces` holds.  Every walk is bounded (2 n_vertices + 64 steps; indices strictly decrease along a walk, so the bound is
+ *   out of reach unless vertex_label is overwritten during the call) and gives up by setting the flag.  The flag is only ever set; the caller zeroes it.
+ * Filter, in the two steps of tvr_mesh_count / tvr_mesh_emit because the output sizes are results.  keep_root [n_vertices] uint8 is read at labels only: a vertex
+ *   survives iff keep_root[vertex_label[v]] != 0, a triangle iff its first vertex does.
+ *   tvr_mesh_filter_count fills `scratch` (tvr_mesh_filter_scratch_bytes, 256-byte aligned: 9 B per element of max(n_vertices, n_triangles) rounded up to TVR_MESH_TILE)
+ *   with the keep flags and their exclusive scans (the reduce / scan / add scheme above) and leaves {surviving vertices, surviving triangles} in counts_dev[2].
+ *   A triangle index or a label outside 0 .. n_vertices-1 sets the flag, is neither followed nor kept, and makes the following emit write nothing.
+ *   tvr_mesh_filter_emit with the SAME faces, counts and scratch: verts_out [n_vertices_out][3] fp32 = the surviving rows of verts, bit for bit and in their order (verts
+ *   and verts_out may both be NULL: indices only); faces_out [n_triangles_out][3] int32 = the surviving triangles in their order, re-indexed; kept_vertex [n_vertices_out]
+ *   int32 = the old index of each new vertex (ascending).  The declared counts are the capacities: no store happens at or beyond them, and if they are not the counted
+ *   totals the flag is set and nothing is written.  A surviving triangle whose corner did not survive (labels that do not belong to these faces) sets the flag.
+ * n_triangles == 0 or n_vertices == 0 is valid (the arrays of that length may be NULL).  Errors, all before any launch: TVR_ERR_INVALID for a NULL pointer, a negative
+ *   count, an undersized buffer, a misaligned scratch, declared output counts above n_vertices / n_triangles; TVR_ERR_UNSUPPORTED for a count above 2^31 - 1 (int32
+ *   indices).  The two *_scratch_bytes functions return 0 for such counts. */
+size_t tvr_mesh_components_scratch_bytes(int64_t n_vertices, int64_t n_triangles);
+int tvr_mesh_components(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, int32_t *vertex_label, size_t vertex_label_bytes, int32_t *component_faces,
+                        size_t component_faces_bytes, int64_t *n_components_dev, void *scratch, size_t scratch_bytes, uint32_t *fault_flag_dev, void *stream);
+size_t tvr_mesh_filter_scratch_bytes(int64_t n_vertices, int64_t n_triangles);
+int tvr_mesh_filter_count(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, const int32_t *vertex_label, const uint8_t *keep_root, void *scratch,
+                          size_t scratch_bytes, int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_filter_emit(const float *verts, const int32_t *faces, int64_t n_triangles, int64_t n_vertices, const void *scratch, size_t scratch_bytes, float *verts_out,
+                         size_t verts_out_bytes, int64_t n_vertices_out, int32_t *faces_out, size_t faces_out_bytes, int64_t n_triangles_out, int32_t *kept_vertex,
+                         size_t kept_vertex_bytes, uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

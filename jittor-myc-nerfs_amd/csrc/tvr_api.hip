@@ -1885,3 +1885,91 @@ int tvr_mesh_emit(const float *volume, const int32_t dims[3], float level, const
                              (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- connected components of a mesh and the component filter (tvr_mesh_cc.hip) ---------------------------------------------------------------------------------
+static int cc_counts(const char *fn, int64_t n_vertices, int64_t n_triangles)
+{
+    if (n_vertices < 0 || n_triangles < 0)
+        return fail(TVR_ERR_INVALID, "%s: n_vertices %lld / n_triangles %lld is negative", fn, (long long)n_vertices, (long long)n_triangles);
+    if (n_vertices > INT32_MAX || n_triangles > INT32_MAX)
+        return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices %lld / n_triangles %lld: indices are int32 and both counts must stay below 2^31", fn, (long long)n_vertices,
+                    (long long)n_triangles);
+    return TVR_OK;
+}
+
+size_t tvr_mesh_components_scratch_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (cc_counts(__func__, n_vertices, n_triangles) != TVR_OK) return 0;
+    return MESH_CC_SCRATCH_BYTES;
+}
+
+int tvr_mesh_components(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, int32_t *vertex_label, size_t vertex_label_bytes, int32_t *component_faces,
+                        size_t component_faces_bytes, int64_t *n_components_dev, void *scratch, size_t scratch_bytes, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = cc_counts(__func__, n_vertices, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!n_components_dev || !fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: n_components_dev / fault_flag_dev is NULL", __func__);
+    if ((n_triangles && !faces) || (n_vertices && (!vertex_label || !component_faces)))
+        return fail(TVR_ERR_INVALID, "%s: faces / vertex_label / component_faces is NULL", __func__);
+    if (vertex_label_bytes < (size_t)n_vertices * sizeof(int32_t) || component_faces_bytes < (size_t)n_vertices * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: vertex_label holds %zu B and component_faces %zu B, %lld vertices x int32 need %zu B each", __func__, vertex_label_bytes,
+                    component_faces_bytes, (long long)n_vertices, (size_t)n_vertices * 4);
+    if (!scratch) return fail(TVR_ERR_INVALID, "%s: scratch is NULL", __func__);
+    if ((uintptr_t)scratch % 256) return fail(TVR_ERR_INVALID, "%s: scratch is not 256-byte aligned", __func__);
+    if (scratch_bytes < MESH_CC_SCRATCH_BYTES)
+        return fail(TVR_ERR_INVALID, "%s: scratch holds %zu B, tvr_mesh_components_scratch_bytes asks for %d B", __func__, scratch_bytes, MESH_CC_SCRATCH_BYTES);
+    HIP_TRY(launch_mesh_components(faces, n_triangles, n_vertices, vertex_label, component_faces, (long long *)n_components_dev, scratch, fault_flag_dev,
+                                   (hipStream_t)stream));
+    return TVR_OK;
+}
+
+static long long cc_elements(int64_t n_vertices, int64_t n_triangles) { return n_vertices > n_triangles ? n_vertices : n_triangles; }
+
+size_t tvr_mesh_filter_scratch_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (cc_counts(__func__, n_vertices, n_triangles) != TVR_OK) return 0;
+    return mesh_scratch_bytes(cc_elements(n_vertices, n_triangles));
+}
+
+int tvr_mesh_filter_count(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, const int32_t *vertex_label, const uint8_t *keep_root, void *scratch,
+                          size_t scratch_bytes, int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = cc_counts(__func__, n_vertices, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!counts_dev || !fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: counts_dev / fault_flag_dev is NULL", __func__);
+    if ((n_triangles && !faces) || (n_vertices && (!vertex_label || !keep_root))) return fail(TVR_ERR_INVALID, "%s: faces / vertex_label / keep_root is NULL", __func__);
+    const long long n = cc_elements(n_vertices, n_triangles);
+    if ((rc = mesh_scratch_check(__func__, scratch, scratch_bytes, n)) != TVR_OK) return rc;
+    HIP_TRY(launch_mesh_filter_count(faces, n_triangles, n_vertices, vertex_label, keep_root, mesh_carve(n, scratch), (long long *)counts_dev, fault_flag_dev,
+                                     (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_filter_emit(const float *verts, const int32_t *faces, int64_t n_triangles, int64_t n_vertices, const void *scratch, size_t scratch_bytes, float *verts_out,
+                         size_t verts_out_bytes, int64_t n_vertices_out, int32_t *faces_out, size_t faces_out_bytes, int64_t n_triangles_out, int32_t *kept_vertex,
+                         size_t kept_vertex_bytes, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = cc_counts(__func__, n_vertices, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_triangles && !faces) return fail(TVR_ERR_INVALID, "%s: faces is NULL", __func__);
+    const long long n = cc_elements(n_vertices, n_triangles);
+    if ((rc = mesh_scratch_check(__func__, scratch, scratch_bytes, n)) != TVR_OK) return rc;
+    if (n_vertices_out < 0 || n_vertices_out > n_vertices || n_triangles_out < 0 || n_triangles_out > n_triangles)
+        return fail(TVR_ERR_INVALID, "%s: n_vertices_out %lld / n_triangles_out %lld outside 0 .. %lld vertices / %lld triangles", __func__, (long long)n_vertices_out,
+                    (long long)n_triangles_out, (long long)n_vertices, (long long)n_triangles);
+    if ((n_vertices_out && (!kept_vertex || (verts && !verts_out))) || (n_triangles_out && !faces_out))
+        return fail(TVR_ERR_INVALID, "%s: verts_out / faces_out / kept_vertex is NULL", __func__);
+    if (verts && verts_out_bytes < (size_t)n_vertices_out * 3 * sizeof(float))
+        return fail(TVR_ERR_INVALID, "%s: verts_out holds %zu B, %lld vertices x 3 fp32 need %zu B", __func__, verts_out_bytes, (long long)n_vertices_out,
+                    (size_t)n_vertices_out * 12);
+    if (faces_out_bytes < (size_t)n_triangles_out * 3 * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: faces_out holds %zu B, %lld triangles x 3 int32 need %zu B", __func__, faces_out_bytes, (long long)n_triangles_out,
+                    (size_t)n_triangles_out * 12);
+    if (kept_vertex_bytes < (size_t)n_vertices_out * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: kept_vertex holds %zu B, %lld vertices x int32 need %zu B", __func__, kept_vertex_bytes, (long long)n_vertices_out,
+                    (size_t)n_vertices_out * 4);
+    HIP_TRY(launch_mesh_filter_emit(verts, faces, n_triangles, n_vertices, mesh_carve(n, const_cast<void *>(scratch)), verts_out, n_vertices_out, faces_out, n_triangles_out,
+                                    kept_vertex, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

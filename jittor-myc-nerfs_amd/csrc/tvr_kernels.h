@@ -193,6 +193,20 @@ MeshScratch mesh_carve(long long points, void *scratch);
 size_t mesh_scratch_bytes(long long points);
 // count + scan: fills the scratch, leaves {vertices, triangles} in counts_dev[2]
 hipError_t launch_mesh_count(const float *vol, const int dims[3], float level, const MeshScratch &s, long long *counts_dev, hipStream_t stream);
+// the scan half of launch_mesh_count over a scratch whose cnt8 / tile_base are filled (also the component filter's, tvr_mesh_cc.hip): tile bases, totals -> counts_dev[2]
+// and the scratch header, per-element bases
+hipError_t launch_mesh_scan(const MeshScratch &s, long long *counts_dev, hipStream_t stream);
 // emit from a filled scratch; n_vertices / n_triangles are the capacities of verts / faces AND must equal the counted totals, else *fault = 1 and nothing is written
 hipError_t launch_mesh_emit(const float *vol, const int dims[3], float level, const float origin[3], const float spacing[3], const MeshScratch &s, float *verts,
                             long long n_vertices, int *faces, long long n_triangles, int flip, unsigned *fault, hipStream_t stream);
+
+// tvr_mesh_cc.hip: connected components of an indexed triangle mesh (union-find over the vertices, the label array is the parent array) and the component filter.
+// The components' scratch is one header of MESH_CC_SCRATCH_BYTES: {uint32 bad index seen, uint32 most steps of any walk}.  The filter's scratch is a MeshScratch over
+// max(V, F) elements: count byte bit 0 = vertex kept, bit 3 = triangle kept (what the scan kernels read as one vertex / one triangle); totals[1] != 0 = bad input seen.
+#define MESH_CC_SCRATCH_BYTES 256
+hipError_t launch_mesh_components(const int *faces, long long n_triangles, long long n_vertices, int *vertex_label, int *component_faces, long long *n_components,
+                                  void *scratch, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_filter_count(const int *faces, long long n_triangles, long long n_vertices, const int *vertex_label, const unsigned char *keep_root,
+                                    const MeshScratch &s, long long *counts_dev, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_filter_emit(const float *verts, const int *faces, long long n_triangles, long long n_vertices, const MeshScratch &s, float *verts_out,
+                                   long long n_vertices_out, int *faces_out, long long n_triangles_out, int *kept_vertex, unsigned *fault, hipStream_t stream);

@@ -247,8 +247,14 @@ hipError_t launch_mesh_count(const float *vol, const int dims[3], float level, c
 {
     const MeshDims d = {dims[0], dims[1], dims[2], (unsigned)((long long)dims[0] * dims[1] * dims[2])};
     hipLaunchKernelGGL(mesh_count_kernel, dim3(s.n_tiles), dim3(MESH_THREADS), 0, stream, vol, d, level, s.cnt8, s.tile_base);
+    return launch_mesh_scan(s, counts_dev, stream);
+}
+
+hipError_t launch_mesh_scan(const MeshScratch &s, long long *counts_dev, hipStream_t stream)
+{
     hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(1), dim3(MESH_THREADS), 0, stream, s.tile_base, s.n_tiles, s.totals, counts_dev);
-    hipLaunchKernelGGL(mesh_scan_points_kernel, dim3(s.n_tiles), dim3(MESH_THREADS), 0, stream, s.cnt8, s.tile_base, s.vbase, s.tbase);
+    if (s.n_tiles)              // (a volume has tiles; the component filter of an empty mesh has none)
+        hipLaunchKernelGGL(mesh_scan_points_kernel, dim3(s.n_tiles), dim3(MESH_THREADS), 0, stream, s.cnt8, s.tile_base, s.vbase, s.tbase);
     return hipGetLastError();
 }
 

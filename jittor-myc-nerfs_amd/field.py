@@ -935,7 +935,7 @@ class TensorBase(torch.nn.Module):
         return alpha, dense_xyz
 
     @torch.no_grad()
-    def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False):
+    def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False, min_component_faces=0, keep_largest=0):
         """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
         (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
 
@@ -946,8 +946,13 @@ class TensorBase(torch.nn.Module):
         flip: reverse every triangle.  Normals point out of the dense region (mesh.py); the reference reverses skimage's order, which cannot be compared here.
         normals / colors: add per-vertex `nx ny nz` / `red green blue` (mesh_vertex_attributes) to the file; with both off the file is the reference's bare geometry.
         The attributes are evaluated where the field was SAMPLED: with spacing="reference" the written (shrunken) vertices are mapped back by N / (N - 1) about aabb[0]
-        for the query only.  flip does not touch the normals: they follow the field."""
+        for the query only.  flip does not touch the normals: they follow the field.
+        min_component_faces / keep_largest: drop floaters — keep the connected components with at least that many triangles, then the `keep_largest` biggest of them
+        (mesh.filter_components; 0 = off, the default: the file is then what it was without these options).  The filter runs before the attributes are evaluated, so
+        they are computed for the survivors only; self.mesh_export_stats then says how many components and triangles were dropped."""
         from . import mesh
+        if min_component_faces < 0 or keep_largest < 0:
+            raise ValueError(f"min_component_faces = {min_component_faces} / keep_largest = {keep_largest}: negative values mean nothing (0 switches an option off)")
         alpha, _ = self.getDenseAlpha(gridSize)
         aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
         n = torch.tensor([float(s) for s in alpha.shape], dtype=torch.float32, device=alpha.device)
@@ -958,6 +963,8 @@ class TensorBase(torch.nn.Module):
         else:
             raise ValueError(f"spacing {spacing!r}: 'reference' or 'samples'")
         verts, faces = mesh.marching_cubes(alpha, level, spacing=voxel.tolist(), origin=aabb[0].tolist(), flip=flip)
+        self.mesh_export_stats = {}
+        verts, faces, _ = mesh.filter_components(verts, faces, min_faces=min_component_faces, keep_largest=keep_largest, stats=self.mesh_export_stats)
         if not (normals or colors):
             mesh.write_ply(path, verts, faces)
             return verts, faces

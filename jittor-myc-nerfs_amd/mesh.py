@@ -72,6 +72,130 @@ def marching_cubes(volume: torch.Tensor, level: float, spacing=(1, 1, 1), origin
     return verts, faces
 
 
+# ---- connected components and the component filter (csrc/tvr_mesh_cc.hip, include/tvr.h tvr_mesh_components / tvr_mesh_filter_*) -------------------------------------------
+def _faces_on_device(faces, what: str) -> torch.Tensor:
+    if not torch.is_tensor(faces) or faces.device.type != "cuda":
+        where = faces.device if torch.is_tensor(faces) else type(faces).__name__
+        raise L.TvrError(f"{what} runs on an MI355X (HIP) device only; the faces are on {where}. There is no CPU fallback.")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise L.TvrError(f"{what} takes faces [F, 3]; got shape {tuple(faces.shape)}")
+    return faces.detach().to(torch.int32).contiguous()
+
+
+def _ptr(t: torch.Tensor):
+    return t.data_ptr() if t.numel() else None
+
+
+def _policy(min_faces, keep_largest):
+    min_faces, keep_largest = int(min_faces), int(keep_largest)
+    if min_faces < 0 or keep_largest < 0:
+        raise ValueError(f"min_faces = {min_faces} / keep_largest = {keep_largest}: negative values mean nothing (0 switches an option off)")
+    return min_faces, keep_largest
+
+
+def mesh_components(faces: torch.Tensor, n_vertices: int, stats: dict = None):
+    """Connected components of an indexed triangle mesh on the device -> (vertex_label [V] int32, component_faces [V] int32, n_components).
+
+    Two vertices are connected iff a chain of triangles links them; a vertex no triangle uses is a component of its own.  vertex_label[v] is the SMALLEST vertex
+    index of v's component; component_faces holds, at each label, the number of triangles whose first vertex carries it (0 elsewhere).  All three are functions of the
+    mesh alone: the same on every run.  A face index outside 0 .. V-1 raises TvrError.  `stats` (a dict) receives max_walk_steps / walk_step_bound."""
+    f = _faces_on_device(faces, "mesh_components")
+    V, F = int(n_vertices), int(f.shape[0])
+    lib, dev = L.lib(), f.device
+    nbytes = lib.tvr_mesh_components_scratch_bytes(V, F)
+    if nbytes == 0:
+        raise L.TvrError("mesh_components: " + lib.tvr_last_error().decode(errors="replace"))
+    scratch = L.dev_bytes(nbytes, dev, what="mesh components scratch")
+    label = L.dev_empty((V,), torch.int32, dev, what="mesh vertex labels")
+    sizes = L.dev_empty((V,), torch.int32, dev, what="mesh component sizes")
+    n_comp = L.dev_empty((1,), torch.int64, dev, what="mesh component count")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh components fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_components(_ptr(f), F, V, _ptr(label), L.nbytes(label), _ptr(sizes), L.nbytes(sizes), n_comp.data_ptr(), scratch.data_ptr(), L.nbytes(scratch),
+                                    flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_components")
+    if int(flag.item()) != 0:
+        raise L.TvrError(f"tvr_mesh_components raised its fault flag: a face index lies outside 0 .. {V - 1} (or a walk gave up; include/tvr.h)")
+    if stats is not None:
+        stats["max_walk_steps"] = int(scratch[4:8].view(torch.int32).item())
+        stats["walk_step_bound"] = min(2 * V + 64, 2 ** 32 - 1)
+    return label, sizes, int(n_comp.item())
+
+
+def component_keep_mask(vertex_label: torch.Tensor, component_faces: torch.Tensor, min_faces: int = 0, keep_largest: int = 0) -> torch.Tensor:
+    """The size policy as keep_root [V] uint8 (1 at the labels of the components to keep, read at labels only), on the tensors' device — CPU tensors work too.
+
+    In this order: min_faces = m keeps the components with at least m triangles; keep_largest = K then keeps, among those, the K with the most triangles, ties going to
+    the SMALLER label.  0 switches an option off; with either option on, components without triangles (unused vertices) are never kept; with both off every component is."""
+    min_faces, keep_largest = _policy(min_faces, keep_largest)
+    V = int(vertex_label.shape[0])
+    sizes = component_faces.to(torch.int64)
+    keep = vertex_label.to(torch.int64) == torch.arange(V, dtype=torch.int64, device=vertex_label.device)
+    if min_faces or keep_largest:
+        keep &= sizes >= max(min_faces, 1)
+    if keep_largest:
+        roots = keep.nonzero().view(-1)                              # ascending labels
+        if roots.numel() > keep_largest:
+            key = (sizes.max() - sizes[roots]) * max(V, 1) + roots   # (size descending, label ascending) in one int64: both factors are below 2^31
+            keep = torch.zeros_like(keep)
+            keep[roots[torch.argsort(key)[:keep_largest]]] = True
+    return keep.to(torch.uint8)
+
+
+def filter_count(faces: torch.Tensor, n_vertices: int, vertex_label: torch.Tensor, keep_root: torch.Tensor):
+    """First step (tvr_mesh_filter_count): (filled scratch buffer, surviving vertices, surviving triangles, fault flag [1] int32 on the device)."""
+    lib, dev = L.lib(), faces.device
+    V, F = int(n_vertices), int(faces.shape[0])
+    nbytes = lib.tvr_mesh_filter_scratch_bytes(V, F)
+    if nbytes == 0:
+        raise L.TvrError("filter_components: " + lib.tvr_last_error().decode(errors="replace"))
+    scratch = L.dev_bytes(nbytes, dev, what="mesh filter scratch")
+    counts = L.dev_empty((2,), torch.int64, dev, what="mesh filter counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh filter fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_filter_count(_ptr(faces), F, V, _ptr(vertex_label), _ptr(keep_root), scratch.data_ptr(), L.nbytes(scratch), counts.data_ptr(), flag.data_ptr(),
+                                      _stream_ptr(dev)), "tvr_mesh_filter_count")
+    n_v, n_f = (int(x) for x in counts.cpu().tolist())
+    return scratch, n_v, n_f, flag
+
+
+def filter_emit(verts, faces: torch.Tensor, n_vertices: int, scratch: torch.Tensor, n_vertices_out: int, n_triangles_out: int, flag: torch.Tensor):
+    """Second step (tvr_mesh_filter_emit) into buffers of exactly the declared counts: (verts_out [V',3] or None when verts is None, faces_out [F',3], kept_vertex [V'])."""
+    lib, dev = L.lib(), faces.device
+    verts_out = None if verts is None else L.dev_empty((int(n_vertices_out), 3), torch.float32, dev, what="filtered verts")
+    faces_out = L.dev_empty((int(n_triangles_out), 3), torch.int32, dev, what="filtered faces")
+    kept = L.dev_empty((int(n_vertices_out),), torch.int32, dev, what="kept vertices")
+    L.check(lib.tvr_mesh_filter_emit(None if verts is None else _ptr(verts), _ptr(faces), int(faces.shape[0]), int(n_vertices), scratch.data_ptr(), L.nbytes(scratch),
+                                     None if verts_out is None else _ptr(verts_out), 0 if verts_out is None else L.nbytes(verts_out), int(n_vertices_out), _ptr(faces_out),
+                                     L.nbytes(faces_out), int(n_triangles_out), _ptr(kept), L.nbytes(kept), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_filter_emit")
+    return verts_out, faces_out, kept
+
+
+def filter_components(verts: torch.Tensor, faces: torch.Tensor, min_faces: int = 0, keep_largest: int = 0, stats: dict = None):
+    """Drop whole connected components of an indexed mesh by size -> (verts [V',3] float32, faces [F',3] int32, kept_vertex [V'] int32), on the device.
+
+    The policy is component_keep_mask's (min_faces first, then keep_largest, ties to the smaller label).  Surviving vertices and faces keep their order; the
+    coordinates are the input's bit for bit, the faces are re-indexed and nothing else; kept_vertex[i] is the old index of new vertex i (use it to carry per-vertex
+    attributes over).  With both options 0 the inputs are returned as they are with kept_vertex = None and the library is not called.  No CPU fallback.
+    `stats` (a dict) receives components / components_kept / triangles_dropped."""
+    min_faces, keep_largest = _policy(min_faces, keep_largest)
+    if not (min_faces or keep_largest):
+        return verts, faces, None
+    f = _faces_on_device(faces, "filter_components")
+    if not torch.is_tensor(verts) or verts.device != f.device or verts.dim() != 2 or verts.shape[1] != 3:
+        raise L.TvrError(f"filter_components takes verts [V, 3] on the faces' device ({f.device})")
+    v = verts.detach().to(torch.float32).contiguous()
+    V = int(v.shape[0])
+    label, sizes, n_components = mesh_components(f, V)
+    keep_root = component_keep_mask(label, sizes, min_faces, keep_largest)
+    scratch, n_v, n_f, flag = filter_count(f, V, label, keep_root)
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_filter_count raised its fault flag: a face index or a label lies outside the mesh (include/tvr.h)")
+    verts_out, faces_out, kept = filter_emit(v, f, V, scratch, n_v, n_f, flag)
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_filter_emit raised its fault flag: the counted totals and the declared capacities disagree (include/tvr.h)")
+    if stats is not None:
+        stats.update(components=n_components, components_kept=int(keep_root.sum().item()), triangles_dropped=int(f.shape[0]) - n_f)
+    return verts_out, faces_out, kept
+
+
 # ---- PLY: the subset plyfile writes for the reference (utils.py:192-207) -----------------------------------------------------------------------------------
 _VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 _FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])

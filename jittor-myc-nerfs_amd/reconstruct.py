@@ -9,7 +9,7 @@ What differs from the reference, on purpose:
   * no TensorBoard writer, no `ndc_ray` datasets (the reference ships only the Blender loader); `set_nerfplusplus` is called for NerfPlusPlus only
     (train.py:172 calls it unconditionally and fails for the others);
   * `--export_mesh 1` (train.py:41-59) extracts the surface with the HIP marching cubes (mesh.py) instead of skimage and writes the PLY without plyfile; the
-    level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
+    level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_min_faces N` / `--mesh_keep_largest K` drop connected components (floaters), `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
     geometry), and the command ends after the export instead of falling through into a training run;
   * progress is a plain print every `progress_refresh_rate` iterations.
 Host-side plumbing only: every pixel comes from the HIP kernels through `OctreeRender_trilinear_fast`.
@@ -85,6 +85,9 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # (not reference options) per-vertex normals (nx ny nz) / colours (red green blue) in the exported PLY; 0 = the reference's bare geometry
     p.add_argument("--mesh_normals", type=int, default=0)
     p.add_argument("--mesh_colors", type=int, default=0)
+    # drop floaters from the mesh (mesh.filter_components): components below N triangles, then all but the K largest; 0 = off
+    p.add_argument("--mesh_min_faces", type=int, default=0)
+    p.add_argument("--mesh_keep_largest", type=int, default=0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int), ("mesh_grid", int)):
@@ -187,8 +190,11 @@ def export_mesh(args, device="cuda"):
     tensorf, _ = _build_from_ckpt(args, load_checkpoint(args.ckpt), device)
     path = f"{args.ckpt[:-3]}.ply"
     verts, faces = tensorf.export_mesh(path, level=getattr(args, "mesh_level", 0.0005), gridSize=grid, normals=bool(getattr(args, "mesh_normals", 0)),
-                                       colors=bool(getattr(args, "mesh_colors", 0)))
-    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles)")
+                                       colors=bool(getattr(args, "mesh_colors", 0)), min_component_faces=int(getattr(args, "mesh_min_faces", 0)),
+                                       keep_largest=int(getattr(args, "mesh_keep_largest", 0)))
+    st = getattr(tensorf, "mesh_export_stats", None) or {}
+    dropped = f"; dropped {st['components'] - st['components_kept']} of {st['components']} components, {st['triangles_dropped']} triangles" if st else ""
+    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles{dropped})")
     return path
 
 
