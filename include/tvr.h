@@ -653,6 +653,48 @@ int tvr_mesh_filter_emit(const float *verts, const int32_t *faces, int64_t n_tri
                          size_t verts_out_bytes, int64_t n_vertices_out, int32_t *faces_out, size_t faces_out_bytes, int64_t n_triangles_out, int32_t *kept_vertex,
                          size_t kept_vertex_bytes, uint32_t *fault_flag_dev, void *stream);
 
+/* Mesh simplification by vertex clustering (Rossignac-Borrel; csrc/tvr_mesh_simplify.hip): vertices are snapped to a regular lattice of cells, each cell's vertices
+ * merge into their mean, triangles are re-indexed, collapsed ones and exact duplicates go.  ADDITIVE exports: TVR_VERSION is unchanged.
+ *   verts [n_vertices][3] fp32, faces [n_triangles][3] int32; origin / cell / inv_cell: three HOST floats each, inv_cell = 1 / cell computed by the caller (the kernels
+ *   never divide by cell).  All arithmetic below is fp32 with every operation rounded on its own, except where stated.
+ * Cell of a vertex, per axis: g = (v - origin) * inv_cell, c = floorf(g).  A coordinate exactly on a cell boundary belongs to the UPPER cell.  (Marching-cubes vertices
+ *   lie on grid edges: with cell a whole number of voxels and origin the volume's, most vertices have two coordinates exactly on a boundary — the common case.)  A vertex
+ *   with !(0 <= c && c < 2^21) on any axis (NaN, infinity, anything outside the lattice) sets *fault_flag_dev and no output is written.  key = cx | cy << 21 | cz << 42.
+ * Cluster = the vertices with the same key.  Its representative is its SMALLEST old vertex index; new vertices are numbered in ascending order of representative, so
+ *   vertex_map [n_vertices] (old -> new) and the vertex order are functions of the mesh alone.
+ * Position of a new vertex, per axis: f = g - (float)c (exact), q = (uint32_t)(f * 1048576.0f) (truncates; q < 2^20); sum = the 64-bit INTEGER sum of q over the
+ *   cluster, n = its member count; frac = (float)((double)sum / ((double)n * 1048576.0)); pos = (origin + (float)c * cell) + frac * cell, with c the cell of the
+ *   cluster.  Integer sums make the mean independent of the order the atomics land in; no float is added atomically anywhere.
+ * Triangles: corners are mapped through vertex_map.  A triangle with two equal new corners is dropped.  Of the triangles whose new corner triples are equal up to
+ *   ROTATION (the same orientation) only the one with the smallest old index survives; the reverse orientation is a different triangle and stays.  Survivors keep their
+ *   relative order and their own corner order.
+ * NOT promised: manifoldness, closedness.  Unused vertices DO occur: every cluster gets a vertex whether or not a surviving triangle uses it (an input vertex no
+ *   triangle uses is clustered like any other).
+ * Two steps, because the output sizes are results (as tvr_mesh_count / tvr_mesh_emit):
+ *   tvr_mesh_simplify_count fills `scratch` (tvr_mesh_simplify_scratch_bytes, 256-byte aligned) and leaves {n_vertices', n_triangles'} in counts_dev[2];
+ *   tvr_mesh_simplify_emit with the SAME inputs and scratch writes verts_out [n_vertices_out][3], faces_out [n_triangles_out][3] and vertex_map [n_vertices].  The
+ *   declared counts are the capacities: no store happens at or beyond them, and if they are not the counted totals the flag is set and nothing is written.
+ * Mechanism: two insert-only open-addressing hash tables in scratch (linear probing, capacity a power of two >= max(256, 2 x elements)).  Cells: 64-bit atomicCAS on the
+ *   key, 32-bit atomicMin on the representative.  Triangles: a slot holds a triangle index, claimed by atomicCAS from empty; an occupant whose mapped triple equals one's
+ *   own is joined by atomicMin, another is probed past; nothing is deleted, so equal keys meet in one slot.  Every probe sequence is bounded by the capacity and gives up
+ *   by setting the flag (which is only ever set; the caller zeroes it).  No loop waits for another workgroup.  The survivor flags are scanned by the reduce / scan / add
+ *   scheme above.  After the count the scratch's second uint32 holds the longest probe sequence seen, in slots (diagnostic: it
+ *   depends on the order insertions land in; no output does).
+ * Scratch, linear in the counts: 256 B + 9 B per element of max(n_vertices, n_triangles) rounded up to TVR_MESH_TILE (flags and scans, + 8 B per tile) + per vertex 4 B
+ *   (representative) + 32 B (member count and three sums) + 12 B per cell slot (2 to 4 slots a vertex) + per triangle 4 B (slot) + 4 B per triangle slot (2 to 4 a
+ *   triangle): at most 84 B per vertex + 20 B per triangle + the 9 B per element, each array rounded up to 256 B.
+ * A face index outside 0 .. n_vertices-1 sets the flag and nothing else is written; no load or store leaves the caller's buffers whatever faces and verts hold.
+ * n_vertices == 0 or n_triangles == 0 is valid input and a valid result (arrays of that length may be NULL).  Errors, all before any launch: TVR_ERR_INVALID for a NULL
+ *   pointer, a negative count, an undersized buffer, a misaligned scratch, a non-positive or non-finite cell / inv_cell, declared output counts above the inputs';
+ *   TVR_ERR_UNSUPPORTED for a count above 2^31 - 1; tvr_mesh_simplify_scratch_bytes then returns 0. */
+size_t tvr_mesh_simplify_scratch_bytes(int64_t n_vertices, int64_t n_triangles);
+int tvr_mesh_simplify_count(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const float origin[3], const float cell[3],
+                            const float inv_cell[3], void *scratch, size_t scratch_bytes, int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_simplify_emit(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const float origin[3], const float cell[3],
+                           const float inv_cell[3], void *scratch, size_t scratch_bytes, float *verts_out, size_t verts_out_bytes, int64_t n_vertices_out,
+                           int32_t *faces_out, size_t faces_out_bytes, int64_t n_triangles_out, int32_t *vertex_map, size_t vertex_map_bytes,
+                           uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

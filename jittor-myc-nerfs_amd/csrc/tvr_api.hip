@@ -3,6 +3,7 @@
 #include "tvr_device.h"
 #include "tvr_kernels.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1971,5 +1972,73 @@ int tvr_mesh_filter_emit(const float *verts, const int32_t *faces, int64_t n_tri
                     (size_t)n_vertices_out * 4);
     HIP_TRY(launch_mesh_filter_emit(verts, faces, n_triangles, n_vertices, mesh_carve(n, const_cast<void *>(scratch)), verts_out, n_vertices_out, faces_out, n_triangles_out,
                                     kept_vertex, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+// ---- vertex-clustering simplification of a mesh (tvr_mesh_simplify.hip) ----------------------------------------------------------------------------------------
+size_t tvr_mesh_simplify_scratch_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (cc_counts(__func__, n_vertices, n_triangles) != TVR_OK) return 0;
+    return simplify_carve(n_vertices, n_triangles, nullptr).total;
+}
+
+// everything tvr_mesh_simplify_count and _emit share: counts, inputs, lattice, scratch
+static int simplify_inputs(const char *fn, const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const float origin[3], const float cell[3],
+                           const float inv_cell[3], const void *scratch, size_t scratch_bytes, const uint32_t *fault_flag_dev, SimplifyLattice *lat)
+{
+    int rc = cc_counts(fn, n_vertices, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!origin || !cell || !inv_cell || !fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: origin / cell / inv_cell / fault_flag_dev is NULL", fn);
+    if ((n_vertices && !verts) || (n_triangles && !faces)) return fail(TVR_ERR_INVALID, "%s: verts / faces is NULL", fn);
+    for (int a = 0; a < 3; ++a) {
+        if (!(cell[a] > 0.0f) || !std::isfinite(cell[a]) || !(inv_cell[a] > 0.0f) || !std::isfinite(inv_cell[a]))
+            return fail(TVR_ERR_INVALID, "%s: cell[%d] = %g / inv_cell[%d] = %g: both must be positive and finite", fn, a, (double)cell[a], a, (double)inv_cell[a]);
+        lat->origin[a] = origin[a];
+        lat->cell[a] = cell[a];
+        lat->inv_cell[a] = inv_cell[a];
+    }
+    if (!scratch) return fail(TVR_ERR_INVALID, "%s: scratch is NULL", fn);
+    if ((uintptr_t)scratch % 256) return fail(TVR_ERR_INVALID, "%s: scratch is not 256-byte aligned", fn);
+    const size_t need = simplify_carve(n_vertices, n_triangles, nullptr).total;
+    if (scratch_bytes < need) return fail(TVR_ERR_INVALID, "%s: scratch holds %zu B, tvr_mesh_simplify_scratch_bytes asks for %zu B", fn, scratch_bytes, need);
+    return TVR_OK;
+}
+
+int tvr_mesh_simplify_count(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const float origin[3], const float cell[3],
+                            const float inv_cell[3], void *scratch, size_t scratch_bytes, int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    SimplifyLattice lat;
+    const int rc = simplify_inputs(__func__, verts, n_vertices, faces, n_triangles, origin, cell, inv_cell, scratch, scratch_bytes, fault_flag_dev, &lat);
+    if (rc != TVR_OK) return rc;
+    if (!counts_dev) return fail(TVR_ERR_INVALID, "%s: counts_dev is NULL", __func__);
+    HIP_TRY(launch_mesh_simplify_count(verts, n_vertices, faces, n_triangles, lat, simplify_carve(n_vertices, n_triangles, scratch), (long long *)counts_dev,
+                                       fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_simplify_emit(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const float origin[3], const float cell[3],
+                           const float inv_cell[3], void *scratch, size_t scratch_bytes, float *verts_out, size_t verts_out_bytes, int64_t n_vertices_out,
+                           int32_t *faces_out, size_t faces_out_bytes, int64_t n_triangles_out, int32_t *vertex_map, size_t vertex_map_bytes, uint32_t *fault_flag_dev,
+                           void *stream)
+{
+    SimplifyLattice lat;
+    const int rc = simplify_inputs(__func__, verts, n_vertices, faces, n_triangles, origin, cell, inv_cell, scratch, scratch_bytes, fault_flag_dev, &lat);
+    if (rc != TVR_OK) return rc;
+    if (n_vertices_out < 0 || n_vertices_out > n_vertices || n_triangles_out < 0 || n_triangles_out > n_triangles)
+        return fail(TVR_ERR_INVALID, "%s: n_vertices_out %lld / n_triangles_out %lld outside 0 .. %lld vertices / %lld triangles", __func__, (long long)n_vertices_out,
+                    (long long)n_triangles_out, (long long)n_vertices, (long long)n_triangles);
+    if ((n_vertices_out && !verts_out) || (n_triangles_out && !faces_out) || (n_vertices && !vertex_map))
+        return fail(TVR_ERR_INVALID, "%s: verts_out / faces_out / vertex_map is NULL", __func__);
+    if (verts_out_bytes < (size_t)n_vertices_out * 3 * sizeof(float))
+        return fail(TVR_ERR_INVALID, "%s: verts_out holds %zu B, %lld vertices x 3 fp32 need %zu B", __func__, verts_out_bytes, (long long)n_vertices_out,
+                    (size_t)n_vertices_out * 12);
+    if (faces_out_bytes < (size_t)n_triangles_out * 3 * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: faces_out holds %zu B, %lld triangles x 3 int32 need %zu B", __func__, faces_out_bytes, (long long)n_triangles_out,
+                    (size_t)n_triangles_out * 12);
+    if (vertex_map_bytes < (size_t)n_vertices * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: vertex_map holds %zu B, %lld vertices x int32 need %zu B", __func__, vertex_map_bytes, (long long)n_vertices,
+                    (size_t)n_vertices * 4);
+    HIP_TRY(launch_mesh_simplify_emit(verts, n_vertices, faces, n_triangles, lat, simplify_carve(n_vertices, n_triangles, scratch), verts_out, n_vertices_out, faces_out,
+                                      n_triangles_out, vertex_map, fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }

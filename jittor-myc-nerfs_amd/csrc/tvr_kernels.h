@@ -210,3 +210,31 @@ hipError_t launch_mesh_filter_count(const int *faces, long long n_triangles, lon
                                     const MeshScratch &s, long long *counts_dev, unsigned *fault, hipStream_t stream);
 hipError_t launch_mesh_filter_emit(const float *verts, const int *faces, long long n_triangles, long long n_vertices, const MeshScratch &s, float *verts_out,
                                    long long n_vertices_out, int *faces_out, long long n_triangles_out, int *kept_vertex, unsigned *fault, hipStream_t stream);
+
+// tvr_mesh_simplify.hip: vertex-clustering simplification of an indexed triangle mesh (include/tvr.h tvr_mesh_simplify_*).  The scratch carved for V vertices and
+// F triangles: a header {uint32 bad input seen, uint32 longest probe sequence}, a MeshScratch over max(V, F) elements (count byte bit 0 = vertex e is its cluster's
+// representative, bit 3 = triangle e survives: tvr_mesh.hip's scan reads them as one vertex / one triangle), per vertex its cluster's representative, per triangle its
+// slot, the two hash tables (cells: 64-bit key + representative per slot; triangles: one triangle index per slot) and per vertex {members, sum qx, sum qy, sum qz}.
+struct SimplifyScratch {
+    unsigned *header;
+    MeshScratch flags;
+    unsigned *vrep;                    // [V] after the cell pass: the vertex's slot; after the resolve pass: its cluster's representative
+    unsigned *tslot;                   // [F] the triangle's slot (0 for a collapsed triangle, which sits in no slot)
+    unsigned long long *cell_key;      // [cap_v], empty = all ones
+    unsigned *cell_rep;                // [cap_v], the smallest vertex index that reached the slot
+    unsigned *tri_slot;                // [cap_t], the smallest triangle index of the slot's triple, empty = all ones
+    unsigned long long *sums;          // [V][4], read at representatives
+    unsigned long long cap_v, cap_t;   // powers of two, >= 2 V / 2 F
+    size_t fill_off, fill_bytes;       // the tables: one 0xff fill before the count
+    size_t sums_off, sums_bytes;       // zeroed before the emit
+    size_t total;
+};
+struct SimplifyLattice {
+    float origin[3], cell[3], inv_cell[3];
+};
+SimplifyScratch simplify_carve(long long n_vertices, long long n_triangles, void *scratch);
+hipError_t launch_mesh_simplify_count(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const SimplifyLattice &lat,
+                                      const SimplifyScratch &s, long long *counts_dev, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_simplify_emit(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const SimplifyLattice &lat,
+                                     const SimplifyScratch &s, float *verts_out, long long n_vertices_out, int *faces_out, long long n_triangles_out, int *vertex_map,
+                                     unsigned *fault, hipStream_t stream);

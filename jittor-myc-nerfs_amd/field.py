@@ -935,7 +935,8 @@ class TensorBase(torch.nn.Module):
         return alpha, dense_xyz
 
     @torch.no_grad()
-    def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False, min_component_faces=0, keep_largest=0):
+    def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False, min_component_faces=0, keep_largest=0,
+                    simplify=0.0):
         """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
         (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
 
@@ -949,10 +950,16 @@ class TensorBase(torch.nn.Module):
         for the query only.  flip does not touch the normals: they follow the field.
         min_component_faces / keep_largest: drop floaters — keep the connected components with at least that many triangles, then the `keep_largest` biggest of them
         (mesh.filter_components; 0 = off, the default: the file is then what it was without these options).  The filter runs before the attributes are evaluated, so
-        they are computed for the survivors only; self.mesh_export_stats then says how many components and triangles were dropped."""
+        they are computed for the survivors only; self.mesh_export_stats then says how many components and triangles were dropped.
+        simplify: shrink the mesh by vertex clustering (mesh.simplify_clustering) — the edge of a cluster cell in units of THIS export's marching-cubes voxel, on a
+        lattice whose corner is aabb[0] (mesh_simplify_lattice).  0 = off, the default: the file is then what it was without the option.  2.0 merges about 2 x 2 x 2
+        voxels, roughly a quarter of the triangles.  Values in (0, 1), negative and non-finite ones are a ValueError.  It runs AFTER the component filter (floaters are gone
+        before they could be welded to the object) and BEFORE the attributes, which are therefore evaluated at the new vertices; self.mesh_export_stats gains
+        vertices_in / vertices_out / triangles_in / triangles_out / max_probe / table_capacity."""
         from . import mesh
         if min_component_faces < 0 or keep_largest < 0:
             raise ValueError(f"min_component_faces = {min_component_faces} / keep_largest = {keep_largest}: negative values mean nothing (0 switches an option off)")
+        simplify = self._mesh_simplify_factor(simplify)
         alpha, _ = self.getDenseAlpha(gridSize)
         aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
         n = torch.tensor([float(s) for s in alpha.shape], dtype=torch.float32, device=alpha.device)
@@ -965,6 +972,9 @@ class TensorBase(torch.nn.Module):
         verts, faces = mesh.marching_cubes(alpha, level, spacing=voxel.tolist(), origin=aabb[0].tolist(), flip=flip)
         self.mesh_export_stats = {}
         verts, faces, _ = mesh.filter_components(verts, faces, min_faces=min_component_faces, keep_largest=keep_largest, stats=self.mesh_export_stats)
+        if simplify:
+            cell, corner = self.mesh_simplify_lattice(alpha.shape, spacing, simplify)
+            verts, faces, _ = mesh.simplify_clustering(verts, faces, cell, origin=corner, stats=self.mesh_export_stats)
         if not (normals or colors):
             mesh.write_ply(path, verts, faces)
             return verts, faces
@@ -972,6 +982,27 @@ class TensorBase(torch.nn.Module):
         attrs = self.mesh_vertex_attributes(at, normals=normals, colors=colors)
         mesh.write_ply(path, verts, faces, normals=attrs.get("normals"), colors=attrs.get("colors"))
         return verts, faces
+
+    @staticmethod
+    def _mesh_simplify_factor(simplify):
+        simplify = float(simplify)
+        if not np.isfinite(simplify) or simplify < 0 or 0 < simplify < 1:
+            raise ValueError(f"simplify = {simplify}: the cluster cell's edge in marching-cubes voxels, 0 (off) or a finite value >= 1")
+        return simplify
+
+    def mesh_simplify_lattice(self, gridSize, spacing, simplify):
+        """(cell [3], origin [3]) as Python floats: the lattice export_mesh(gridSize=, spacing=, simplify=) hands to mesh.simplify_clustering — cell = simplify x the
+        export's voxel (computed in fp32 exactly as export_mesh computes it), origin = aabb[0]."""
+        simplify = self._mesh_simplify_factor(simplify)
+        aabb = self.aabb.to(device=self.device, dtype=torch.float32)
+        n = torch.tensor([float(s) for s in gridSize], dtype=torch.float32, device=aabb.device)
+        if spacing == "reference":
+            voxel = (aabb[1] - aabb[0]) / n
+        elif spacing == "samples":
+            voxel = (aabb[1] - aabb[0]) / (n - 1)
+        else:
+            raise ValueError(f"spacing {spacing!r}: 'reference' or 'samples'")
+        return [simplify * x for x in voxel.tolist()], aabb[0].tolist()
 
     def mesh_sample_positions(self, verts, gridSize, spacing):
         """Where the field was sampled for the vertices export_mesh writes: the vertices themselves for spacing="samples"; for "reference" (voxel = extent / N)

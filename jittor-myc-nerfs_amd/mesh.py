@@ -196,6 +196,99 @@ def filter_components(verts: torch.Tensor, faces: torch.Tensor, min_faces: int =
     return verts_out, faces_out, kept
 
 
+# ---- vertex-clustering simplification (csrc/tvr_mesh_simplify.hip, include/tvr.h tvr_mesh_simplify_*) -------------------------------------------------------------------
+def _lattice(cell, origin):
+    """(origin, cell, inv_cell) as three fp32 triples; inv_cell = float32(1) / float32(cell), the value include/tvr.h's definition is stated with."""
+    c = np.asarray(cell, dtype=np.float64).reshape(-1)
+    if c.size == 1:
+        c = np.repeat(c, 3)
+    if c.size != 3 or not (np.isfinite(c).all() and (c > 0).all()):
+        raise ValueError(f"cell = {cell!r}: one positive finite edge length, or three")
+    o = np.asarray(origin, dtype=np.float32).reshape(-1)
+    if o.size != 3:
+        raise ValueError(f"origin = {origin!r}: three coordinates")
+    with np.errstate(all="ignore"):
+        c = c.astype(np.float32)
+        inv = np.float32(1) / c
+    if not (np.isfinite(inv).all() and (inv > 0).all() and (c > 0).all()):
+        raise ValueError(f"cell = {cell!r}: the edge length or its inverse is not a positive finite fp32 number")
+    return o, c, inv
+
+
+def _c3(a):
+    return (C.c_float * 3)(*[float(x) for x in a])
+
+
+def simplify_count(verts: torch.Tensor, faces: torch.Tensor, origin, cell, inv_cell):
+    """First step (tvr_mesh_simplify_count): (filled scratch buffer, vertices out, triangles out, fault flag [1] int32 on the device)."""
+    lib, dev = L.lib(), faces.device
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    nbytes = lib.tvr_mesh_simplify_scratch_bytes(V, F)
+    if nbytes == 0:
+        raise L.TvrError("simplify_clustering: " + lib.tvr_last_error().decode(errors="replace"))
+    scratch = L.dev_bytes(nbytes, dev, what="mesh simplify scratch")
+    counts = L.dev_empty((2,), torch.int64, dev, what="mesh simplify counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh simplify fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_simplify_count(_ptr(verts), V, _ptr(faces), F, _c3(origin), _c3(cell), _c3(inv_cell), scratch.data_ptr(), L.nbytes(scratch), counts.data_ptr(),
+                                        flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_simplify_count")
+    n_v, n_f = (int(x) for x in counts.cpu().tolist())
+    return scratch, n_v, n_f, flag
+
+
+def simplify_emit(verts: torch.Tensor, faces: torch.Tensor, origin, cell, inv_cell, scratch: torch.Tensor, n_vertices_out: int, n_triangles_out: int, flag: torch.Tensor):
+    """Second step (tvr_mesh_simplify_emit) into buffers of exactly the declared counts: (verts_out [V',3], faces_out [F',3], vertex_map [V] old -> new)."""
+    lib, dev = L.lib(), faces.device
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    verts_out = L.dev_empty((int(n_vertices_out), 3), torch.float32, dev, what="simplified verts")
+    faces_out = L.dev_empty((int(n_triangles_out), 3), torch.int32, dev, what="simplified faces")
+    vmap = L.dev_empty((V,), torch.int32, dev, what="simplify vertex map")
+    L.check(lib.tvr_mesh_simplify_emit(_ptr(verts), V, _ptr(faces), F, _c3(origin), _c3(cell), _c3(inv_cell), scratch.data_ptr(), L.nbytes(scratch), _ptr(verts_out),
+                                       L.nbytes(verts_out), int(n_vertices_out), _ptr(faces_out), L.nbytes(faces_out), int(n_triangles_out), _ptr(vmap), L.nbytes(vmap),
+                                       flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_simplify_emit")
+    return verts_out, faces_out, vmap
+
+
+def simplify_table_capacities(n_vertices: int, n_triangles: int):
+    """(cell table slots, triangle table slots): the power of two >= max(256, 2 x elements) include/tvr.h states."""
+    def cap(n):
+        c = 256
+        while c < 2 * int(n):
+            c *= 2
+        return c
+    return cap(n_vertices), cap(n_triangles)
+
+
+def simplify_clustering(verts: torch.Tensor, faces: torch.Tensor, cell, origin=(0, 0, 0), stats: dict = None):
+    """Vertex-clustering simplification on the device -> (verts [V',3] float32, faces [F',3] int32, vertex_map [V] int32 old -> new).
+
+    Vertices fall into the cells of a lattice (edge `cell`, a float or three, world units; corner `origin`; a coordinate on a boundary belongs to the upper cell); each
+    cell's vertices merge into their mean (an exact integer mean of the in-cell fractions quantised to 2^-20 of a cell), numbered by their smallest old index; faces are
+    re-indexed, the ones with two equal corners go, and of the faces equal up to rotation the one with the smallest old index stays, in its own corner order.  A reversed
+    face is another face.  Every cell keeps its vertex whether a face still uses it or not.  The result is a function of the arguments alone: the same bit for bit on
+    every run (include/tvr.h tvr_mesh_simplify_* has the arithmetic).  ValueError for a cell that is not positive and finite; TvrError when the library raises its fault
+    flag: a vertex outside the lattice (below `origin`, beyond 2^21 cells, NaN) or a face index outside the vertices.  No CPU fallback.
+    `stats` (a dict) receives vertices_in / vertices_out / triangles_in / triangles_out / max_probe (longest probe sequence of either hash table, in slots) /
+    table_capacity (slots of the larger table; also cell_table_capacity / triangle_table_capacity)."""
+    o, c, inv = _lattice(cell, origin)
+    f = _faces_on_device(faces, "simplify_clustering")
+    if not torch.is_tensor(verts) or verts.device != f.device or verts.dim() != 2 or verts.shape[1] != 3:
+        raise L.TvrError(f"simplify_clustering takes verts [V, 3] on the faces' device ({f.device})")
+    v = verts.detach().to(torch.float32).contiguous()
+    V, F = int(v.shape[0]), int(f.shape[0])
+    scratch, n_v, n_f, flag = simplify_count(v, f, o, c, inv)
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_simplify_count raised its fault flag: a vertex lies outside the lattice (below origin, beyond 2^21 cells, or not a number) or a face "
+                         f"index lies outside 0 .. {V - 1} (include/tvr.h)")
+    verts_out, faces_out, vmap = simplify_emit(v, f, o, c, inv, scratch, n_v, n_f, flag)
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_simplify_emit raised its fault flag: the counted totals and the declared capacities disagree (include/tvr.h)")
+    if stats is not None:
+        cap_v, cap_t = simplify_table_capacities(V, F)
+        stats.update(vertices_in=V, vertices_out=n_v, triangles_in=F, triangles_out=n_f, max_probe=int(scratch[4:8].view(torch.int32).item()),
+                     table_capacity=max(cap_v, cap_t), cell_table_capacity=cap_v, triangle_table_capacity=cap_t)
+    return verts_out, faces_out, vmap
+
+
 # ---- PLY: the subset plyfile writes for the reference (utils.py:192-207) -----------------------------------------------------------------------------------
 _VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 _FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
