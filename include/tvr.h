@@ -695,6 +695,67 @@ int tvr_mesh_simplify_emit(const float *verts, int64_t n_vertices, const int32_t
                            int32_t *faces_out, size_t faces_out_bytes, int64_t n_triangles_out, int32_t *vertex_map, size_t vertex_map_bytes,
                            uint32_t *fault_flag_dev, void *stream);
 
+/* Vertex adjacency of an indexed triangle mesh, with the number of face sides on every edge (csrc/tvr_mesh_smooth.hip): the structure that says whether a mesh is closed
+ * and the one smoothing gathers over.  ADDITIVE exports: TVR_VERSION is unchanged.  faces [n_triangles][3] int32 indexes n_vertices vertices.
+ *   Sides: a face (a, b, c) has the three sides {a,b}, {b,c}, {c,a}; a side with two equal ends is ignored (a face (a, a, b) still gives the side {a,b}, twice;
+ *   a face (a, a, a) gives none).  Orientation is ignored: {a,b} and {b,a} are the same side.
+ *   Neighbours: u is a neighbour of v iff some side is {u, v}.  The row of v holds its DISTINCT neighbours in ASCENDING order; a vertex no side uses has an empty row.
+ *   offsets [n_vertices + 1] int32: offsets[0] = 0, row v = neighbours[offsets[v] .. offsets[v+1] - 1], offsets[n_vertices] = H, the number of half-edges (every
+ *   undirected edge appears twice, once in each end's row).  neighbours [H] int32.
+ *   edge_faces [H] int32, parallel to neighbours: the number of sides equal to that edge, counted over all faces — a face listed twice counts twice, a reversed face
+ *   counts like any other.  1 = a boundary edge, 2 = the edge of a closed 2-manifold, above 2 = a non-manifold edge.
+ *   A mesh is closed iff no edge_faces is 1.  The output is a function of (faces, n_vertices) alone: the same on every run.
+ * Two steps, because H is a result (as tvr_mesh_count / tvr_mesh_emit):
+ *   tvr_mesh_adjacency_count fills `scratch` (tvr_mesh_adjacency_scratch_bytes, 256-byte aligned) and leaves counts_dev[4] int64 = {H, boundary_edges, nonmanifold_edges,
+ *   max_degree}: boundary_edges = UNDIRECTED edges with edge_faces == 1, nonmanifold_edges = those with edge_faces > 2, max_degree = the longest row.
+ *   tvr_mesh_adjacency_emit with the SAME faces, counts and scratch writes offsets, neighbours and edge_faces.  n_half_edges is the capacity of the two arrays AND must
+ *   be the counted H: no store happens at or beyond it, and if it is not the counted H *fault_flag_dev becomes 1 and NOTHING is written (offsets included).
+ *   A face index outside 0 .. n_vertices-1 sets the flag at count time (the four counts are then 0) and makes the following emit set it again and write nothing; no load
+ *   or store leaves the caller's buffers whatever `faces` holds.  The flag is only ever set; the caller zeroes it.
+ * Mechanism: every side adds 1 to the RAW degree of both ends (32-bit atomicAdd); a 32-bit reduce / scan / add over tiles of TVR_MESH_TILE entries gives the raw row
+ *   starts; every side writes each end into the other's raw row through a per-row cursor (atomicAdd; the order inside a raw row is the only thing that depends on the order
+ *   atomics land in); every raw row is sorted and run-length encoded, which yields the distinct neighbours, edge_faces and the degree: a raw row of at most
+ *   TVR_MESH_ADJ_SHORT_ROW entries by ONE THREAD (insertion sort), a longer one by ONE WORKGROUP (a bitonic network for any length, log2(n)(log2(n)+1)/2 passes of n/2
+ *   comparators over 256 lanes, then two block scans); a scan of the degrees gives offsets; the emit copies row fronts.  No float is involved, no loop waits for another
+ *   workgroup, every loop is bounded by a count below 2^31.
+ * Scratch, linear in the counts: 256 B + per vertex 16 B (degree, long-row slot, raw row start, offset) + 4 B per TVR_MESH_TILE vertices + per triangle 48 B (6 raw
+ *   entries and their 6 counts), each array rounded up to 256 B.
+ * n_vertices == 0 or n_triangles == 0 is valid (offsets always has its n_vertices + 1 entries; arrays of length 0 may be NULL).  Errors, all before any launch:
+ *   TVR_ERR_INVALID for a NULL pointer, a negative count, an undersized buffer, a misaligned scratch; TVR_ERR_UNSUPPORTED for n_vertices or 6 * n_triangles above
+ *   2^31 - 1 (H <= 6 * n_triangles and indices are int32); tvr_mesh_adjacency_scratch_bytes then returns 0. */
+#define TVR_MESH_ADJ_SHORT_ROW 64
+size_t tvr_mesh_adjacency_scratch_bytes(int64_t n_vertices, int64_t n_triangles);
+int tvr_mesh_adjacency_count(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, void *scratch, size_t scratch_bytes, int64_t *counts_dev,
+                             uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_adjacency_emit(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, const void *scratch, size_t scratch_bytes, int32_t *offsets,
+                            size_t offsets_bytes, int32_t *neighbours, size_t neighbours_bytes, int32_t *edge_faces, size_t edge_faces_bytes, int64_t n_half_edges,
+                            uint32_t *fault_flag_dev, void *stream);
+
+/* Taubin lambda|mu smoothing of vertex positions over that adjacency (csrc/tvr_mesh_smooth.hip).  ADDITIVE export.  verts / verts_out [n_vertices][3] fp32; offsets,
+ * neighbours, edge_faces as above (any CSR with offsets non-decreasing from 0 to n_half_edges and neighbours in 0 .. n_vertices-1 is taken; the sums follow ITS order).
+ *   All arithmetic is fp32 and every operation is rounded on its own (no fused multiply-add); the division is IEEE correctly rounded.
+ *   One iteration = two half steps, the first with weight w = lambda, the second with w = mu.  In a half step every vertex v, per axis, with deg = its row's length:
+ *     deg == 0, or v pinned:  p'[v] = p[v]
+ *     else  s = p[n_0]; s = s + p[n_k] for k = 1 .. deg-1 in the row's stored order (the sum STARTS from the first neighbour, not from zero: -0.0 survives);
+ *           m = s / (float)deg;  d = m - p[v];  t = w * d;  p'[v] = p[v] + t
+ *   Every vertex of a half step reads the positions the previous half step left (Jacobi, not Gauss-Seidel): one launch per half step over two buffers of the scratch,
+ *   the last one into verts_out; no atomics, no grid-wide barrier, so the result is a function of the arguments alone: bit-identical from run to run.
+ *   pin_boundary != 0: v is pinned iff one of its edges has edge_faces == 1.  pin_boundary == 0: nothing is pinned and edge_faces may be NULL.
+ *   iterations == 0 copies verts to verts_out bit for bit.  Non-finite coordinates are not an error: they spread to neighbours as the arithmetic dictates.
+ * A first kernel checks the adjacency: offsets[0] == 0, offsets non-decreasing, offsets[n_vertices] == n_half_edges, every neighbour in 0 .. n_vertices-1.  A violation
+ *   sets *fault_flag_dev (only ever set; the caller zeroes it), every later kernel returns at once and verts_out stays unwritten.  The gather re-checks every index it
+ *   uses, so no load leaves the caller's buffers whatever they hold.
+ * scratch: tvr_mesh_smooth_scratch_bytes, 256-byte aligned: 256 B + 2 x 16 B per vertex (positions are kept as 16-byte rows {x, y, z, pinned}).
+ * Errors, all before any launch: TVR_ERR_INVALID for a NULL pointer where data is due, a negative count, iterations outside 0 .. TVR_MESH_SMOOTH_MAX_ITERATIONS, a
+ *   non-finite lambda or mu, verts_out_bytes != 12 * n_vertices, too little or misaligned scratch; TVR_ERR_UNSUPPORTED for a count above 2^31 - 1;
+ *   tvr_mesh_smooth_scratch_bytes then returns 0.
+ * NOT promised: that vertices stay on the iso-surface (they leave it), that self-intersections go, that the volume is kept (Taubin keeps it approximately). */
+#define TVR_MESH_SMOOTH_MAX_ITERATIONS 1000
+size_t tvr_mesh_smooth_scratch_bytes(int64_t n_vertices, int64_t n_half_edges);
+int tvr_mesh_smooth(const float *verts, int64_t n_vertices, const int32_t *offsets, const int32_t *neighbours, const int32_t *edge_faces, int64_t n_half_edges,
+                    int32_t iterations, float lambda, float mu, int32_t pin_boundary, void *scratch, size_t scratch_bytes, float *verts_out, size_t verts_out_bytes,
+                    uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,6 @@ from .variants import Embedder, MLPNet, MLPRender_Fea_Ref, NerfPlusPlus, REFTens
 from .render import OctreeRender_trilinear_fast, N_to_reso, cal_n_samples, render_sharded, ShardedFramePipeline, FrameStream, shard_indices, shard_capacity, shard_gather_index, shard_send_views, shard_unpermute  # noqa: F401
 from .evaluation import BlenderRays, evaluation, evaluation_path, normal_map_to_rgb8, rgb_ssim, rgb_ssim_torch  # noqa: F401
 from .losses import TVLoss  # noqa: F401
-from .mesh import marching_cubes, read_ply, read_ply_attributes, simplify_clustering, write_ply  # noqa: F401
+from .mesh import marching_cubes, mesh_adjacency, read_ply, read_ply_attributes, simplify_clustering, smooth_taubin, write_ply  # noqa: F401
 from .training import GradBucket, make_graphed_step, shard_batch  # noqa: F401
 from . import mesh, ngp, rays, synthetic  # noqa: F401

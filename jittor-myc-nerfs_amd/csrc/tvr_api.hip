@@ -2042,3 +2042,109 @@ int tvr_mesh_simplify_emit(const float *verts, int64_t n_vertices, const int32_t
                                       n_triangles_out, vertex_map, fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- vertex adjacency and Taubin smoothing of a mesh (tvr_mesh_smooth.hip) -------------------------------------------------------------------------------------------
+static int adj_counts(const char *fn, int64_t n_vertices, int64_t n_triangles)
+{
+    if (n_vertices < 0 || n_triangles < 0)
+        return fail(TVR_ERR_INVALID, "%s: n_vertices %lld / n_triangles %lld is negative", fn, (long long)n_vertices, (long long)n_triangles);
+    if (n_vertices > INT32_MAX || n_triangles > INT32_MAX / 6)
+        return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices %lld / n_triangles %lld: indices are int32, n_vertices and 6 x n_triangles must stay below 2^31", fn,
+                    (long long)n_vertices, (long long)n_triangles);
+    return TVR_OK;
+}
+
+size_t tvr_mesh_adjacency_scratch_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (adj_counts(__func__, n_vertices, n_triangles) != TVR_OK) return 0;
+    return adj_carve(n_vertices, n_triangles, nullptr).total;
+}
+
+// everything tvr_mesh_adjacency_count and _emit share
+static int adj_inputs(const char *fn, const int32_t *faces, int64_t n_triangles, int64_t n_vertices, const void *scratch, size_t scratch_bytes,
+                      const uint32_t *fault_flag_dev)
+{
+    int rc = adj_counts(fn, n_vertices, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", fn);
+    if (n_triangles && !faces) return fail(TVR_ERR_INVALID, "%s: faces is NULL", fn);
+    if (!scratch) return fail(TVR_ERR_INVALID, "%s: scratch is NULL", fn);
+    if ((uintptr_t)scratch % 256) return fail(TVR_ERR_INVALID, "%s: scratch is not 256-byte aligned", fn);
+    const size_t need = adj_carve(n_vertices, n_triangles, nullptr).total;
+    if (scratch_bytes < need) return fail(TVR_ERR_INVALID, "%s: scratch holds %zu B, tvr_mesh_adjacency_scratch_bytes asks for %zu B", fn, scratch_bytes, need);
+    return TVR_OK;
+}
+
+int tvr_mesh_adjacency_count(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, void *scratch, size_t scratch_bytes, int64_t *counts_dev,
+                             uint32_t *fault_flag_dev, void *stream)
+{
+    const int rc = adj_inputs(__func__, faces, n_triangles, n_vertices, scratch, scratch_bytes, fault_flag_dev);
+    if (rc != TVR_OK) return rc;
+    if (!counts_dev) return fail(TVR_ERR_INVALID, "%s: counts_dev is NULL", __func__);
+    HIP_TRY(launch_mesh_adjacency_count(faces, n_triangles, n_vertices, adj_carve(n_vertices, n_triangles, scratch), (long long *)counts_dev, fault_flag_dev,
+                                        (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_adjacency_emit(const int32_t *faces, int64_t n_triangles, int64_t n_vertices, const void *scratch, size_t scratch_bytes, int32_t *offsets,
+                            size_t offsets_bytes, int32_t *neighbours, size_t neighbours_bytes, int32_t *edge_faces, size_t edge_faces_bytes, int64_t n_half_edges,
+                            uint32_t *fault_flag_dev, void *stream)
+{
+    const int rc = adj_inputs(__func__, faces, n_triangles, n_vertices, scratch, scratch_bytes, fault_flag_dev);
+    if (rc != TVR_OK) return rc;
+    if (n_half_edges < 0 || n_half_edges > 6 * n_triangles)
+        return fail(TVR_ERR_INVALID, "%s: n_half_edges %lld outside 0 .. 6 x %lld triangles", __func__, (long long)n_half_edges, (long long)n_triangles);
+    if (!offsets || (n_half_edges && (!neighbours || !edge_faces))) return fail(TVR_ERR_INVALID, "%s: offsets / neighbours / edge_faces is NULL", __func__);
+    if (offsets_bytes < ((size_t)n_vertices + 1) * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: offsets holds %zu B, %lld vertices + 1 x int32 need %zu B", __func__, offsets_bytes, (long long)n_vertices,
+                    ((size_t)n_vertices + 1) * 4);
+    if (neighbours_bytes < (size_t)n_half_edges * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: neighbours holds %zu B, %lld half-edges x int32 need %zu B", __func__, neighbours_bytes, (long long)n_half_edges,
+                    (size_t)n_half_edges * 4);
+    if (edge_faces_bytes < (size_t)n_half_edges * sizeof(int32_t))
+        return fail(TVR_ERR_INVALID, "%s: edge_faces holds %zu B, %lld half-edges x int32 need %zu B", __func__, edge_faces_bytes, (long long)n_half_edges,
+                    (size_t)n_half_edges * 4);
+    HIP_TRY(launch_mesh_adjacency_emit(n_vertices, adj_carve(n_vertices, n_triangles, const_cast<void *>(scratch)), offsets, neighbours, edge_faces, n_half_edges,
+                                       fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+static int smooth_counts(const char *fn, int64_t n_vertices, int64_t n_half_edges)
+{
+    if (n_vertices < 0 || n_half_edges < 0)
+        return fail(TVR_ERR_INVALID, "%s: n_vertices %lld / n_half_edges %lld is negative", fn, (long long)n_vertices, (long long)n_half_edges);
+    if (n_vertices > INT32_MAX || n_half_edges > INT32_MAX)
+        return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices %lld / n_half_edges %lld: indices are int32 and both counts must stay below 2^31", fn, (long long)n_vertices,
+                    (long long)n_half_edges);
+    return TVR_OK;
+}
+
+size_t tvr_mesh_smooth_scratch_bytes(int64_t n_vertices, int64_t n_half_edges)
+{
+    if (smooth_counts(__func__, n_vertices, n_half_edges) != TVR_OK) return 0;
+    return smooth_carve(n_vertices, nullptr).total;
+}
+
+int tvr_mesh_smooth(const float *verts, int64_t n_vertices, const int32_t *offsets, const int32_t *neighbours, const int32_t *edge_faces, int64_t n_half_edges,
+                    int32_t iterations, float lambda, float mu, int32_t pin_boundary, void *scratch, size_t scratch_bytes, float *verts_out, size_t verts_out_bytes,
+                    uint32_t *fault_flag_dev, void *stream)
+{
+    const int rc = smooth_counts(__func__, n_vertices, n_half_edges);
+    if (rc != TVR_OK) return rc;
+    if (iterations < 0 || iterations > TVR_MESH_SMOOTH_MAX_ITERATIONS)
+        return fail(TVR_ERR_INVALID, "%s: iterations %d outside 0 .. %d", __func__, (int)iterations, TVR_MESH_SMOOTH_MAX_ITERATIONS);
+    if (!std::isfinite(lambda) || !std::isfinite(mu)) return fail(TVR_ERR_INVALID, "%s: lambda = %g / mu = %g: both must be finite", __func__, (double)lambda, (double)mu);
+    if (!fault_flag_dev || !offsets) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev / offsets is NULL", __func__);
+    if ((n_vertices && (!verts || !verts_out)) || (n_half_edges && !neighbours)) return fail(TVR_ERR_INVALID, "%s: verts / verts_out / neighbours is NULL", __func__);
+    if (pin_boundary && n_half_edges && !edge_faces) return fail(TVR_ERR_INVALID, "%s: edge_faces is NULL and pin_boundary is set", __func__);
+    if (verts_out_bytes != (size_t)n_vertices * 3 * sizeof(float))
+        return fail(TVR_ERR_INVALID, "%s: verts_out holds %zu B, %lld vertices x 3 fp32 are %zu B", __func__, verts_out_bytes, (long long)n_vertices,
+                    (size_t)n_vertices * 12);
+    if (!scratch) return fail(TVR_ERR_INVALID, "%s: scratch is NULL", __func__);
+    if ((uintptr_t)scratch % 256) return fail(TVR_ERR_INVALID, "%s: scratch is not 256-byte aligned", __func__);
+    const size_t need = smooth_carve(n_vertices, nullptr).total;
+    if (scratch_bytes < need) return fail(TVR_ERR_INVALID, "%s: scratch holds %zu B, tvr_mesh_smooth_scratch_bytes asks for %zu B", __func__, scratch_bytes, need);
+    HIP_TRY(launch_mesh_smooth(verts, n_vertices, offsets, neighbours, pin_boundary && n_half_edges ? edge_faces : nullptr, n_half_edges, iterations, lambda, mu,
+                               smooth_carve(n_vertices, scratch), verts_out, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

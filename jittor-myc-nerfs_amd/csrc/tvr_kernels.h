@@ -238,3 +238,28 @@ hipError_t launch_mesh_simplify_count(const float *verts, long long n_vertices, 
 hipError_t launch_mesh_simplify_emit(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const SimplifyLattice &lat,
                                      const SimplifyScratch &s, float *verts_out, long long n_vertices_out, int *faces_out, long long n_triangles_out, int *vertex_map,
                                      unsigned *fault, hipStream_t stream);
+
+// tvr_mesh_smooth.hip: vertex adjacency of an indexed triangle mesh and Taubin smoothing over it (include/tvr.h tvr_mesh_adjacency_* / tvr_mesh_smooth).  The adjacency's
+// scratch carved for V vertices and F triangles: a header {bad input seen, long rows, boundary edges, non-manifold edges, largest degree, H, raw entries}, the scan's
+// tile sums, per vertex its degree (first the raw degree, then the fill's cursor, then the distinct neighbours) and a slot in the list of long rows, the raw row starts
+// and the offsets (V + 1 each), and two arrays of 6 F entries: the raw rows (after the sort: each row's distinct neighbours at its front) and, parallel, edge_faces.
+#define ADJ_SHORT TVR_MESH_ADJ_SHORT_ROW
+struct AdjScratch {
+    unsigned *header, *tile, *deg, *long_rows, *raw_off, *off, *raw, *cnt;
+    unsigned raw_cap, n_tiles;
+    size_t total;
+};
+AdjScratch adj_carve(long long n_vertices, long long n_triangles, void *scratch);
+hipError_t launch_mesh_adjacency_count(const int *faces, long long n_triangles, long long n_vertices, const AdjScratch &s, long long *counts_dev, unsigned *fault,
+                                       hipStream_t stream);
+hipError_t launch_mesh_adjacency_emit(long long n_vertices, const AdjScratch &s, int *offsets, int *neighbours, int *edge_faces, long long n_half_edges, unsigned *fault,
+                                      hipStream_t stream);
+// the smoothing's scratch: a header {bad adjacency seen} and the two ping-pong buffers of 16-byte rows {x, y, z, pinned}
+struct SmoothScratch {
+    unsigned *header;
+    float4 *rows[2];
+    size_t total;
+};
+SmoothScratch smooth_carve(long long n_vertices, void *scratch);
+hipError_t launch_mesh_smooth(const float *verts, long long n_vertices, const int *offsets, const int *neighbours, const int *edge_faces, long long n_half_edges,
+                              int iterations, float lambda, float mu, const SmoothScratch &s, float *verts_out, unsigned *fault, hipStream_t stream);

@@ -936,7 +936,7 @@ class TensorBase(torch.nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False, min_component_faces=0, keep_largest=0,
-                    simplify=0.0):
+                    simplify=0.0, smooth=0):
         """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
         (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
 
@@ -955,11 +955,18 @@ class TensorBase(torch.nn.Module):
         lattice whose corner is aabb[0] (mesh_simplify_lattice).  0 = off, the default: the file is then what it was without the option.  2.0 merges about 2 x 2 x 2
         voxels, roughly a quarter of the triangles.  Values in (0, 1), negative and non-finite ones are a ValueError.  It runs AFTER the component filter (floaters are gone
         before they could be welded to the object) and BEFORE the attributes, which are therefore evaluated at the new vertices; self.mesh_export_stats gains
-        vertices_in / vertices_out / triangles_in / triangles_out / max_probe / table_capacity."""
+        vertices_in / vertices_out / triangles_in / triangles_out / max_probe / table_capacity.
+        smooth: N iterations of Taubin smoothing (mesh.smooth_taubin with lam 0.5, mu -0.53, boundary vertices pinned) against the voxel staircase.  0 = off, the
+        default: nothing new is called and the file is what it was without the option.  It runs AFTER the clustering (whose cell means are the blockiest input) and
+        BEFORE the attributes, so normals and colours are evaluated at the smoothed vertices — which no longer lie on the iso-surface.  An integer in 0 .. 1000, else
+        ValueError; self.mesh_export_stats gains half_edges / boundary_edges / nonmanifold_edges / max_degree (boundary_edges == 0: the mesh is closed) and
+        smooth_iterations."""
         from . import mesh
         if min_component_faces < 0 or keep_largest < 0:
             raise ValueError(f"min_component_faces = {min_component_faces} / keep_largest = {keep_largest}: negative values mean nothing (0 switches an option off)")
         simplify = self._mesh_simplify_factor(simplify)
+        if isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or not 0 <= int(smooth) <= mesh.SMOOTH_MAX_ITERATIONS:
+            raise ValueError(f"smooth = {smooth!r}: Taubin iterations, an integer in 0 .. {mesh.SMOOTH_MAX_ITERATIONS} (0 = off)")
         alpha, _ = self.getDenseAlpha(gridSize)
         aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
         n = torch.tensor([float(s) for s in alpha.shape], dtype=torch.float32, device=alpha.device)
@@ -975,6 +982,8 @@ class TensorBase(torch.nn.Module):
         if simplify:
             cell, corner = self.mesh_simplify_lattice(alpha.shape, spacing, simplify)
             verts, faces, _ = mesh.simplify_clustering(verts, faces, cell, origin=corner, stats=self.mesh_export_stats)
+        if smooth:
+            verts = mesh.smooth_taubin(verts, faces, int(smooth), lam=mesh.SMOOTH_LAMBDA, mu=mesh.SMOOTH_MU, pin_boundary=True, stats=self.mesh_export_stats)
         if not (normals or colors):
             mesh.write_ply(path, verts, faces)
             return verts, faces

@@ -289,6 +289,114 @@ def simplify_clustering(verts: torch.Tensor, faces: torch.Tensor, cell, origin=(
     return verts_out, faces_out, vmap
 
 
+# ---- vertex adjacency and Taubin smoothing (csrc/tvr_mesh_smooth.hip, include/tvr.h tvr_mesh_adjacency_* / tvr_mesh_smooth) --------------------------------------------------
+ADJ_SHORT_ROW = 64          # include/tvr.h TVR_MESH_ADJ_SHORT_ROW: raw rows up to this length are sorted by one thread, longer ones by one workgroup
+SMOOTH_MAX_ITERATIONS = 1000        # include/tvr.h TVR_MESH_SMOOTH_MAX_ITERATIONS
+SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53       # Taubin's pair as export_mesh(smooth=) uses it: the pass band ends at 1/lambda + 1/mu ~ 0.113
+
+
+def adjacency_count(faces: torch.Tensor, n_vertices: int):
+    """First step (tvr_mesh_adjacency_count): (filled scratch buffer, (half_edges, boundary_edges, nonmanifold_edges, max_degree), fault flag [1] int32 on the device)."""
+    lib, dev = L.lib(), faces.device
+    V, F = int(n_vertices), int(faces.shape[0])
+    nbytes = lib.tvr_mesh_adjacency_scratch_bytes(V, F)
+    if nbytes == 0:
+        raise L.TvrError("mesh_adjacency: " + lib.tvr_last_error().decode(errors="replace"))
+    scratch = L.dev_bytes(nbytes, dev, what="mesh adjacency scratch")
+    counts = L.dev_empty((4,), torch.int64, dev, what="mesh adjacency counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh adjacency fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_adjacency_count(_ptr(faces), F, V, scratch.data_ptr(), L.nbytes(scratch), counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)),
+            "tvr_mesh_adjacency_count")
+    return scratch, tuple(int(x) for x in counts.cpu().tolist()), flag
+
+
+def adjacency_emit(faces: torch.Tensor, n_vertices: int, scratch: torch.Tensor, n_half_edges: int, flag: torch.Tensor):
+    """Second step (tvr_mesh_adjacency_emit) into buffers of exactly the declared size: (offsets [V+1], neighbours [H], edge_faces [H]), int32."""
+    lib, dev = L.lib(), faces.device
+    V, F, H = int(n_vertices), int(faces.shape[0]), int(n_half_edges)
+    offsets = L.dev_empty((V + 1,), torch.int32, dev, what="adjacency offsets")
+    nbrs = L.dev_empty((H,), torch.int32, dev, what="adjacency neighbours")
+    edge_faces = L.dev_empty((H,), torch.int32, dev, what="adjacency edge_faces")
+    L.check(lib.tvr_mesh_adjacency_emit(_ptr(faces), F, V, scratch.data_ptr(), L.nbytes(scratch), offsets.data_ptr(), L.nbytes(offsets), _ptr(nbrs), L.nbytes(nbrs),
+                                        _ptr(edge_faces), L.nbytes(edge_faces), H, flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_adjacency_emit")
+    return offsets, nbrs, edge_faces
+
+
+def mesh_adjacency(faces: torch.Tensor, n_vertices: int, stats: dict = None):
+    """Vertex adjacency of an indexed triangle mesh on the device -> (offsets [V+1], neighbours [H], edge_faces [H]), all int32.
+
+    A face (a, b, c) has the sides {a,b}, {b,c}, {c,a}; a side with two equal ends is ignored.  Row v = neighbours[offsets[v]:offsets[v+1]] holds the DISTINCT vertices
+    that share a side with v, ascending (empty for a vertex no side uses); edge_faces, parallel to it, is the number of sides on that edge over all faces (a face listed
+    twice counts twice, orientation is ignored): 1 = boundary edge, 2 = closed manifold edge, more = non-manifold.  Every undirected edge appears in both ends' rows.
+    The result is a function of the arguments alone.  A face index outside 0 .. V-1 raises TvrError.  No CPU fallback.
+    `stats` (a dict) receives half_edges / boundary_edges (undirected edges with one side) / nonmanifold_edges (more than two) / max_degree: a mesh is closed iff
+    boundary_edges == 0."""
+    f = _faces_on_device(faces, "mesh_adjacency")
+    V = int(n_vertices)
+    if V < 0:
+        raise ValueError(f"n_vertices = {n_vertices}: negative")
+    scratch, (H, boundary, nonmanifold, max_degree), flag = adjacency_count(f, V)
+    if int(flag.item()) != 0:
+        raise L.TvrError(f"tvr_mesh_adjacency_count raised its fault flag: a face index lies outside 0 .. {V - 1} (include/tvr.h)")
+    out = adjacency_emit(f, V, scratch, H, flag)
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_adjacency_emit raised its fault flag: the counted half-edges and the declared capacity disagree (include/tvr.h)")
+    if stats is not None:
+        stats.update(half_edges=H, boundary_edges=boundary, nonmanifold_edges=nonmanifold, max_degree=max_degree)
+    return out
+
+
+def _smooth_arguments(iterations, lam, mu):
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= SMOOTH_MAX_ITERATIONS:
+        raise ValueError(f"iterations = {iterations!r}: an integer in 0 .. {SMOOTH_MAX_ITERATIONS}")
+    lam, mu = float(lam), float(mu)
+    if not 0 < lam <= 1:
+        raise ValueError(f"lam = {lam}: the shrinking step's weight, 0 < lam <= 1")
+    if not -1 <= mu <= 1:
+        raise ValueError(f"mu = {mu}: the inflating step's weight, -1 <= mu <= 1 (Taubin: mu < -lam; mu = lam is plain Laplacian smoothing)")
+    return int(iterations), lam, mu
+
+
+def smooth_taubin(verts: torch.Tensor, faces: torch.Tensor, iterations: int, lam: float = SMOOTH_LAMBDA, mu: float = SMOOTH_MU, pin_boundary: bool = True,
+                  adjacency=None, stats: dict = None) -> torch.Tensor:
+    """Taubin lambda|mu smoothing on the device -> verts' [V,3] float32; the faces are unchanged.
+
+    One iteration is two half steps, weight lam then weight mu; in a half step every vertex with neighbours moves by weight x (mean of its neighbours - itself), all
+    vertices reading the previous half step's positions.  The mean sums the neighbours in mesh_adjacency's ascending order in fp32, one rounded operation at a time, and
+    no atomics are involved: the result is the same bit for bit on every run (include/tvr.h tvr_mesh_smooth has the arithmetic).  pin_boundary keeps every vertex on an
+    edge with a single face side where it is.  iterations = 0 returns a copy.  Non-finite coordinates spread, they are not an error.
+    adjacency: the (offsets, neighbours, edge_faces) of mesh_adjacency(faces, V) when the caller has them already.
+    ValueError unless iterations is an integer in 0 .. 1000, 0 < lam <= 1 and -1 <= mu <= 1; TvrError for CPU tensors (no CPU fallback) and when the library raises its
+    fault flag (an adjacency that does not belong to V vertices).  `stats` (a dict) receives mesh_adjacency's counts (when it is computed here) and smooth_iterations."""
+    iterations, lam, mu = _smooth_arguments(iterations, lam, mu)
+    f = _faces_on_device(faces, "smooth_taubin")
+    if not torch.is_tensor(verts) or verts.device != f.device or verts.dim() != 2 or verts.shape[1] != 3:
+        raise L.TvrError(f"smooth_taubin takes verts [V, 3] on the faces' device ({f.device})")
+    v = verts.detach().to(torch.float32).contiguous()
+    V = int(v.shape[0])
+    if adjacency is None:
+        adjacency = mesh_adjacency(f, V, stats=stats)
+    offsets, nbrs, edge_faces = (a.detach().to(device=f.device, dtype=torch.int32).contiguous() for a in adjacency)
+    if offsets.numel() != V + 1 or nbrs.numel() != edge_faces.numel():
+        raise L.TvrError(f"smooth_taubin: adjacency of {offsets.numel() - 1} vertices / {nbrs.numel()} and {edge_faces.numel()} half-edges for {V} vertices")
+    H = int(nbrs.numel())
+    lib, dev = L.lib(), f.device
+    nbytes = lib.tvr_mesh_smooth_scratch_bytes(V, H)
+    if nbytes == 0:
+        raise L.TvrError("smooth_taubin: " + lib.tvr_last_error().decode(errors="replace"))
+    scratch = L.dev_bytes(nbytes, dev, what="mesh smooth scratch")
+    out = L.dev_empty((V, 3), torch.float32, dev, what="smoothed verts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh smooth fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_smooth(_ptr(v), V, offsets.data_ptr(), _ptr(nbrs), _ptr(edge_faces), H, iterations, lam, mu, 1 if pin_boundary else 0, scratch.data_ptr(),
+                                L.nbytes(scratch), _ptr(out), L.nbytes(out), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_smooth")
+    if int(flag.item()) != 0:
+        raise L.TvrError(f"tvr_mesh_smooth raised its fault flag: offsets do not run from 0 to {H} without decreasing, or a neighbour lies outside 0 .. {V - 1} "
+                         "(include/tvr.h)")
+    if stats is not None:
+        stats["smooth_iterations"] = iterations
+    return out
+
+
 # ---- PLY: the subset plyfile writes for the reference (utils.py:192-207) -----------------------------------------------------------------------------------
 _VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 _FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
