@@ -756,6 +756,48 @@ int tvr_mesh_smooth(const float *verts, int64_t n_vertices, const int32_t *offse
                     int32_t iterations, float lambda, float mu, int32_t pin_boundary, void *scratch, size_t scratch_bytes, float *verts_out, size_t verts_out_bytes,
                     uint32_t *fault_flag_dev, void *stream);
 
+/* Newton projection of mesh vertices onto the iso-surface of the density field (csrc/tvr_mesh_project.hip).  ADDITIVE export: TVR_VERSION is unchanged.
+ * THE SURFACE.  alpha(p) = 1 - exp(-feature2density(f(p)) * length) = level is the set f(p) = f*, where f is tvr_density_feature's value at normalize_coord(p) and
+ *   f* = feature2density^-1(sigma*), sigma* = -log1p(-level) / length;  softplus: f* = log(expm1(sigma*)) - density_shift;  relu: f* = sigma* (> 0).
+ *   `length` is what getDenseAlpha passes to compute_alpha, the scene's step_size.  The HOST computes f* in fp64 and passes it rounded to one float, target_feature.
+ *   LIMITATION: the alpha mask is NOT consulted.  Where a mask cuts alpha to zero inside the f >= f* region, the exported surface follows the mask's boundary while this
+ *   call pulls vertices towards f = f*, up to max_move away.
+ * INPUTS.  verts [n_vertices][3] fp32: WORLD positions where the field was sampled.  pinned [n_vertices] uint8 or NULL: non-zero = copy the vertex through.
+ *   iterations N in 0 .. TVR_MESH_PROJECT_MAX_ITERATIONS.  half_width[3]: tvr_density_gradient's, normalised units.  max_move[3]: world units, the half edges of the
+ *   trust box about the input vertex.  tol >= 0: feature units.
+ * PER VERTEX, with p_0 the input, lo / hi / inv the scene's aabb[0], aabb[1] and inv_aabb_size; every operation below is fp32 and rounded on its own (no fused
+ *   multiply-add), in exactly this order; the division is IEEE correctly rounded:
+ *     n_k = (p_k - lo) * inv - 1                                       (normalize_coord's three operations, per axis)
+ *     (f_k, g_k) = tvr_density_gradient's (sigma_feature, grad) at n_k for half_width, bit for bit (the same per-point code, csrc/tvr_gradient.h)
+ *     r_k = f_k - f*
+ *   step (k < N):
+ *     gw = g_k * inv                                                   (the world-space gradient, per axis)
+ *     s  = r_k / max((gw.x * gw.x + gw.y * gw.y) + gw.z * gw.z, 1e-30)
+ *     q  = p_k - s * gw                                                (per axis: one product, one difference)
+ *     p_{k+1} = min(max(min(max(q, p_0 - max_move), p_0 + max_move), lo), hi)      (the trust box first, then the aabb; p_0 -+ max_move are rounded fp32 sums)
+ *   result: the first p_k, k = 0 .. N, with |r_k| <= tol — the vertex is CONVERGED and iterates no further; otherwise the p_k with the smallest |r_k|, the smaller k on
+ *     a tie.  Hence |residual_out| <= |r_0| always, with equality only where the result is p_0.
+ *   exceptions: a pinned vertex, and every vertex when N = 0, is copied through bit for bit (r_0 is still evaluated; it is converged iff |r_0| <= tol).  A non-finite
+ *     p_0, a non-finite r_k or a non-finite q (before the clamps) at any k FREEZES the vertex at its best iterate so far (p_0 if there is none) and counts it as
+ *     non-finite; no load leaves the scene's buffers whatever the coordinates are.  A zero gradient gives s * gw = 0: q = p_k, which only the clamps can move.
+ *     A vertex outside the aabb is clamped INTO it by its first step, even beyond max_move.
+ * OUTPUTS.  verts_out [n_vertices][3] (may alias verts).  residual_in [n_vertices] or NULL = r_0.  residual_out [n_vertices] = r at the result, bit-equal to
+ *   tvr_density_feature(normalize_coord(result)) - f* (for a vertex frozen with no finite residual: r_0 as evaluated).  counts_dev [4] int64 on the device, ZEROED BY THE
+ *   CALL on `stream`: {converged, moved (result != p_0 in some bit), clamped (a clamp changed q at least once), non-finite}.
+ *   No position depends on an atomic or on another vertex: the outputs are the same bit for bit on every run, for every batch split and vertex order.
+ * Mechanism: VM scenes a quad of lanes per vertex, CP scenes a lane per vertex (tvr_density_gradient's mappings); N + 1 gradient evaluations in registers, a finished
+ *   vertex is held, not retired (wave-uniform trip count); no scratch, no LDS; the counters are one ballot + one 64-bit atomic add per wave and counter.
+ * VM scenes of every variant and CP scenes are taken; an attached density volume is not used (the factored form, as tvr_density_gradient).
+ * Errors, all before any launch: TVR_ERR_INVALID for a NULL scene / counts_dev / half_width / max_move, a scene without parameters, n_vertices < 0, NULL verts /
+ *   verts_out / residual_out with n_vertices > 0, iterations outside the range, a non-finite or non-positive half_width or max_move, a non-finite target_feature, tol < 0
+ *   or NaN; TVR_ERR_UNSUPPORTED for n_vertices above 2^31 - 1; TVR_ERR_SCRATCH for an output buffer that is too short (tvr_last_error() names it).
+ *   n_vertices == 0 succeeds and launches no kernel.  No host read happens inside the call.
+ * NOT promised: that triangles keep their orientation or do not fold over (the only guard is the trust box); anything about surfaces an alpha mask cut. */
+#define TVR_MESH_PROJECT_MAX_ITERATIONS 64
+int tvr_mesh_project(tvr_scene *scene, const float *verts, int64_t n_vertices, const uint8_t *pinned /* or NULL */, float target_feature, int32_t iterations,
+                     const float half_width[3], const float max_move[3], float tol, float *verts_out, size_t verts_out_bytes, float *residual_in /* or NULL */,
+                     size_t residual_in_bytes, float *residual_out, size_t residual_out_bytes, int64_t *counts_dev /* [4], zeroed by the call */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2148,3 +2148,37 @@ int tvr_mesh_smooth(const float *verts, int64_t n_vertices, const int32_t *offse
                                smooth_carve(n_vertices, scratch), verts_out, fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- projection of mesh vertices onto the iso-surface (tvr_mesh_project.hip) -------------------------------------------------------------------------------------------
+int tvr_mesh_project(tvr_scene *s, const float *verts, int64_t n_vertices, const uint8_t *pinned, float target_feature, int32_t iterations, const float half_width[3],
+                     const float max_move[3], float tol, float *verts_out, size_t verts_out_bytes, float *residual_in, size_t residual_in_bytes, float *residual_out,
+                     size_t residual_out_bytes, int64_t *counts_dev, void *stream)
+{
+    if (!s || !s->params_set) return fail(TVR_ERR_INVALID, "%s: scene is NULL or tvr_scene_update has not run", __func__);
+    if (n_vertices < 0) return fail(TVR_ERR_INVALID, "%s: n_vertices = %lld is negative", __func__, (long long)n_vertices);
+    if (n_vertices > 0x7fffffffll) return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices = %lld: at most 2^31 - 1 vertices per call", __func__, (long long)n_vertices);
+    if (iterations < 0 || iterations > TVR_MESH_PROJECT_MAX_ITERATIONS)
+        return fail(TVR_ERR_INVALID, "%s: iterations %d outside 0 .. %d", __func__, (int)iterations, TVR_MESH_PROJECT_MAX_ITERATIONS);
+    if (!half_width || !max_move) return fail(TVR_ERR_INVALID, "%s: half_width / max_move is NULL", __func__);
+    float inv2h[3];
+    for (int k = 0; k < 3; ++k) {
+        if (!(half_width[k] > 0.0f) || !std::isfinite(half_width[k]))
+            return fail(TVR_ERR_INVALID, "%s: half_width[%d] = %g must be finite and > 0", __func__, k, (double)half_width[k]);
+        if (!(max_move[k] > 0.0f) || !std::isfinite(max_move[k])) return fail(TVR_ERR_INVALID, "%s: max_move[%d] = %g must be finite and > 0", __func__, k, (double)max_move[k]);
+        inv2h[k] = 0.5f / half_width[k];
+    }
+    if (!std::isfinite(target_feature)) return fail(TVR_ERR_INVALID, "%s: target_feature = %g must be finite", __func__, (double)target_feature);
+    if (!(tol >= 0.0f)) return fail(TVR_ERR_INVALID, "%s: tol = %g must be >= 0", __func__, (double)tol);
+    if (!counts_dev) return fail(TVR_ERR_INVALID, "%s: counts_dev is NULL", __func__);
+    if (n_vertices > 0) {
+        if (!verts || !verts_out || !residual_out) return fail(TVR_ERR_INVALID, "%s: verts / verts_out / residual_out is NULL", __func__);
+        NEED("verts_out [n_vertices,3]", verts_out_bytes, n_vertices, 3);
+        NEED("residual_out [n_vertices]", residual_out_bytes, n_vertices, 1);
+        if (residual_in) NEED("residual_in [n_vertices]", residual_in_bytes, n_vertices, 1);
+    }
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, 4 * sizeof(int64_t), (hipStream_t)stream));
+    if (n_vertices == 0) return TVR_OK;
+    HIP_TRY(launch_mesh_project(s->dev, s->cp ? &s->cpd : nullptr, verts, n_vertices, pinned, target_feature, iterations, half_width, inv2h, max_move, tol, verts_out,
+                                residual_in, residual_out, (unsigned long long *)counts_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

@@ -263,3 +263,9 @@ struct SmoothScratch {
 SmoothScratch smooth_carve(long long n_vertices, void *scratch);
 hipError_t launch_mesh_smooth(const float *verts, long long n_vertices, const int *offsets, const int *neighbours, const int *edge_faces, long long n_half_edges,
                               int iterations, float lambda, float mu, const SmoothScratch &s, float *verts_out, unsigned *fault, hipStream_t stream);
+
+// tvr_mesh_project.hip: Newton projection of vertices onto the iso-surface density feature == target_feature (include/tvr.h tvr_mesh_project).  cp: the scene's CpDev
+// or nullptr (VM); h / inv2h: tvr_density_gradient's half width and 0.5 / h; pinned / residual_in may be nullptr; counts [4] must have been zeroed on `stream`.
+hipError_t launch_mesh_project(const SceneDev &sc, const CpDev *cp, const float *verts, long long n_vertices, const unsigned char *pinned, float target_feature,
+                               int iterations, const float h[3], const float inv2h[3], const float max_move[3], float tol, float *verts_out, float *residual_in,
+                               float *residual_out, unsigned long long *counts, hipStream_t stream);

@@ -854,6 +854,79 @@ class TensorBase(torch.nn.Module):
         g = -(g * self.invaabbSize.to(device=g.device, dtype=torch.float32))
         return g / torch.sqrt(torch.clamp((g * g).sum(-1, keepdim=True), min=1e-30))
 
+    PROJECT_MAX_ITERATIONS = 64             # include/tvr.h TVR_MESH_PROJECT_MAX_ITERATIONS
+
+    def iso_feature_target(self, level, length=None) -> float:
+        """The density feature f* on the surface compute_alpha(., length) == level, in fp64: feature2density^-1(-log1p(-level) / length).  length: None = stepSize,
+        what getDenseAlpha (and so export_mesh) passes.  softplus: log(expm1(sigma*)) - density_shift; relu: sigma*.  ValueError unless 0 < level < 1 (outside it no
+        density gives that alpha) and for a relu target that is not positive (relu has no inverse there)."""
+        import math
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError(f"level = {level}: an alpha strictly between 0 and 1")
+        length = float(self.stepSize) if length is None else float(length)
+        if not (math.isfinite(length) and length > 0.0):
+            raise ValueError(f"length = {length}: finite and > 0")
+        sigma = -math.log1p(-level) / length
+        if self.fea2denseAct == "softplus":
+            return sigma + math.log(-math.expm1(-sigma)) - float(self.density_shift)          # log(expm1(sigma)) without the overflow
+        if self.fea2denseAct == "relu":
+            if not sigma > 0.0:
+                raise ValueError(f"level = {level}: the density {sigma} it needs is not positive, and relu has no inverse there")
+            return sigma
+        raise ValueError(f"fea2denseAct {self.fea2denseAct!r}: 'softplus' or 'relu'")
+
+    @staticmethod
+    def _three_positive(value, name):
+        v = [float(x) for x in value] if hasattr(value, "__len__") else [float(value)] * 3
+        if len(v) != 3 or not all(np.isfinite(x) and x > 0.0 for x in v):
+            raise ValueError(f"{name} = {value!r}: one number or three (x, y, z), finite and > 0")
+        return v
+
+    @torch.no_grad()
+    def project_to_isosurface(self, verts, level, iterations=8, half_width=None, max_move=None, tol=None, pinned=None, stats=None):
+        """(verts' [V,3], residual_out [V]): the world positions `verts` moved onto the surface compute_alpha == level by Newton steps along the density feature's
+        gradient (tvr_mesh_project; include/tvr.h has the arithmetic) — per vertex r = f - iso_feature_target(level), p <- p - r * gw / |gw|^2, clamped into a trust box
+        of +-max_move about the input vertex and into the aabb; the first iterate with |r| <= tol is the result, else the one with the smallest |r|.
+        iterations: 0 .. 64 (0 copies through).  half_width: the gradient's symmetric difference, normalised units, one number or three; None = a QUARTER cell of the
+        field's grid per axis, 0.25 * 2 / (gridSize - 1).  max_move: world units, one number or three; None = one cell of the field's grid (`units`).
+        tol: feature units; None = 1e-3 * max(1, |f*|).  pinned: [V] bool / uint8, non-zero = leave the vertex where it is.
+        residual_out = density feature - f* at the returned positions.  The alpha mask is not consulted.  stats (a dict) receives refine_iterations,
+        refine_target_feature, refine_converged, refine_moved, refine_clamped, refine_nonfinite, refine_residual_median_before / _after (medians of |r|; reading them
+        waits for the device).  Bad arguments are a ValueError; points on the host a TvrError: there is no CPU fallback."""
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= self.PROJECT_MAX_ITERATIONS:
+            raise ValueError(f"iterations = {iterations!r}: an integer in 0 .. {self.PROJECT_MAX_ITERATIONS}")
+        target = self.iso_feature_target(level)
+        hw = [0.25 * 2.0 / (int(g) - 1) for g in self.gridSize] if half_width is None else self._three_positive(half_width, "half_width")
+        mm = [float(u) for u in self.units] if max_move is None else self._three_positive(max_move, "max_move")
+        tol = 1e-3 * max(1.0, abs(target)) if tol is None else float(tol)
+        if not tol >= 0.0:
+            raise ValueError(f"tol = {tol}: >= 0")
+        if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3:
+            raise ValueError(f"verts must be a [V,3] tensor; got {tuple(verts.shape) if torch.is_tensor(verts) else type(verts).__name__}")
+        V = verts.shape[0]
+        if pinned is not None and (not torch.is_tensor(pinned) or pinned.shape != (V,) or pinned.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError(f"pinned must be a [V] bool or uint8 tensor for V = {V} vertices")
+        v = self._device_points(verts, "project_to_isosurface")
+        if pinned is not None and pinned.device.type != "cuda":
+            raise L.TvrError(f"project_to_isosurface runs on an MI355X (HIP) device only; pinned is on {pinned.device}. There is no CPU fallback.")
+        pin = None if pinned is None else pinned.to(device=self.device, dtype=torch.uint8).contiguous()
+        sc = self._ensure_scene(settle=False)
+        out = L.dev_empty((V, 3), torch.float32, self.device, "tvr_mesh_project verts_out")
+        r_in = L.dev_empty((V,), torch.float32, self.device, "tvr_mesh_project residual_in")
+        r_out = L.dev_empty((V,), torch.float32, self.device, "tvr_mesh_project residual_out")
+        counts = torch.empty(4, dtype=torch.int64, device=self.device)
+        h3, m3 = (C.c_float * 3)(*hw), (C.c_float * 3)(*mm)
+        L.check(L.lib().tvr_mesh_project(sc, v.data_ptr(), V, None if pin is None else pin.data_ptr(), float(target), int(iterations), C.byref(h3), C.byref(m3),
+                                         float(tol), out.data_ptr(), L.nbytes(out), r_in.data_ptr(), L.nbytes(r_in), r_out.data_ptr(), L.nbytes(r_out),
+                                         counts.data_ptr(), _stream_ptr(self.device)), "tvr_mesh_project")
+        if stats is not None:
+            c = counts.tolist()
+            med = (lambda r: float(r.abs().median())) if V else (lambda r: 0.0)
+            stats.update(refine_iterations=int(iterations), refine_target_feature=float(np.float32(target)), refine_converged=c[0], refine_moved=c[1],
+                         refine_clamped=c[2], refine_nonfinite=c[3], refine_residual_median_before=med(r_in), refine_residual_median_after=med(r_out))
+        return out, r_out
+
     @torch.no_grad()
     def mesh_vertex_attributes(self, verts, normals=True, colors=True, half_width=None):
         """Per-vertex attributes of a mesh whose vertices [V,3] lie in world coordinates where the field was sampled: a dict with "normals" [V,3] float32
@@ -936,7 +1009,7 @@ class TensorBase(torch.nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False, min_component_faces=0, keep_largest=0,
-                    simplify=0.0, smooth=0):
+                    simplify=0.0, smooth=0, refine=0):
         """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
         (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
 
@@ -960,13 +1033,21 @@ class TensorBase(torch.nn.Module):
         default: nothing new is called and the file is what it was without the option.  It runs AFTER the clustering (whose cell means are the blockiest input) and
         BEFORE the attributes, so normals and colours are evaluated at the smoothed vertices — which no longer lie on the iso-surface.  An integer in 0 .. 1000, else
         ValueError; self.mesh_export_stats gains half_edges / boundary_edges / nonmanifold_edges / max_degree (boundary_edges == 0: the mesh is closed) and
-        smooth_iterations."""
+        smooth_iterations.
+        refine: N Newton iterations that put every vertex back on the surface alpha == level (project_to_isosurface with its default half width and tolerance, a trust
+        box of ONE VOXEL OF THIS EXPORT per axis).  0 = off, the default: nothing new is called and the file is what it was without the option.  It runs AFTER the
+        smoothing and BEFORE the attributes, on mesh_sample_positions(verts) — where the field was sampled; with spacing="reference" the result is mapped back by
+        (N - 1) / N about aabb[0].  Faces are untouched; normals and colours are evaluated at the projected positions.  The alpha mask is not consulted: where the
+        mask, not the level, bounds the surface, vertices move towards the level set, at most one voxel.  An integer in 0 .. 64, else ValueError;
+        self.mesh_export_stats gains the refine_* entries of project_to_isosurface."""
         from . import mesh
         if min_component_faces < 0 or keep_largest < 0:
             raise ValueError(f"min_component_faces = {min_component_faces} / keep_largest = {keep_largest}: negative values mean nothing (0 switches an option off)")
         simplify = self._mesh_simplify_factor(simplify)
         if isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or not 0 <= int(smooth) <= mesh.SMOOTH_MAX_ITERATIONS:
             raise ValueError(f"smooth = {smooth!r}: Taubin iterations, an integer in 0 .. {mesh.SMOOTH_MAX_ITERATIONS} (0 = off)")
+        if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= self.PROJECT_MAX_ITERATIONS:
+            raise ValueError(f"refine = {refine!r}: Newton iterations onto the iso-surface, an integer in 0 .. {self.PROJECT_MAX_ITERATIONS} (0 = off)")
         alpha, _ = self.getDenseAlpha(gridSize)
         aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
         n = torch.tensor([float(s) for s in alpha.shape], dtype=torch.float32, device=alpha.device)
@@ -984,10 +1065,17 @@ class TensorBase(torch.nn.Module):
             verts, faces, _ = mesh.simplify_clustering(verts, faces, cell, origin=corner, stats=self.mesh_export_stats)
         if smooth:
             verts = mesh.smooth_taubin(verts, faces, int(smooth), lam=mesh.SMOOTH_LAMBDA, mu=mesh.SMOOTH_MU, pin_boundary=True, stats=self.mesh_export_stats)
+        at = None
+        if refine:
+            # one voxel of this export, measured where the field was sampled: extent / (N - 1) whatever the spacing convention of the written vertices
+            at, _ = self.project_to_isosurface(self.mesh_sample_positions(verts, alpha.shape, spacing), level, iterations=int(refine),
+                                               max_move=((aabb[1] - aabb[0]) / (n - 1)).tolist(), stats=self.mesh_export_stats)
+            verts = at if spacing == "samples" else aabb[0] + (at - aabb[0]) * ((n - 1) / n)
         if not (normals or colors):
             mesh.write_ply(path, verts, faces)
             return verts, faces
-        at = self.mesh_sample_positions(verts, alpha.shape, spacing)
+        if at is None:
+            at = self.mesh_sample_positions(verts, alpha.shape, spacing)
         attrs = self.mesh_vertex_attributes(at, normals=normals, colors=colors)
         mesh.write_ply(path, verts, faces, normals=attrs.get("normals"), colors=attrs.get("colors"))
         return verts, faces

@@ -9,7 +9,7 @@ What differs from the reference, on purpose:
   * no TensorBoard writer, no `ndc_ray` datasets (the reference ships only the Blender loader); `set_nerfplusplus` is called for NerfPlusPlus only
     (train.py:172 calls it unconditionally and fails for the others);
   * `--export_mesh 1` (train.py:41-59) extracts the surface with the HIP marching cubes (mesh.py) instead of skimage and writes the PLY without plyfile; the
-    level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_min_faces N` / `--mesh_keep_largest K` drop connected components (floaters), `--mesh_simplify S` merges the vertices of every cell of S voxels (vertex clustering), `--mesh_smooth N` runs N Taubin smoothing iterations, `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
+    level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_min_faces N` / `--mesh_keep_largest K` drop connected components (floaters), `--mesh_simplify S` merges the vertices of every cell of S voxels (vertex clustering), `--mesh_smooth N` runs N Taubin smoothing iterations, `--mesh_refine N` projects the vertices back onto the iso-surface with N Newton iterations, `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
     geometry), and the command ends after the export instead of falling through into a training run;
   * progress is a plain print every `progress_refresh_rate` iterations.
 Host-side plumbing only: every pixel comes from the HIP kernels through `OctreeRender_trilinear_fast`.
@@ -92,6 +92,8 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--mesh_simplify", type=float, default=0.0)
     # smooth the mesh (mesh.smooth_taubin, lam 0.5 / mu -0.53, boundaries pinned): Taubin iterations, after the clustering and before the attributes; 0 = off
     p.add_argument("--mesh_smooth", type=int, default=0)
+    # put the vertices back on the iso-surface (TensorBase.project_to_isosurface): Newton iterations, after the smoothing and before the attributes; 0 = off
+    p.add_argument("--mesh_refine", type=int, default=0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int), ("mesh_grid", int)):
@@ -196,13 +198,15 @@ def export_mesh(args, device="cuda"):
     verts, faces = tensorf.export_mesh(path, level=getattr(args, "mesh_level", 0.0005), gridSize=grid, normals=bool(getattr(args, "mesh_normals", 0)),
                                        colors=bool(getattr(args, "mesh_colors", 0)), min_component_faces=int(getattr(args, "mesh_min_faces", 0)),
                                        keep_largest=int(getattr(args, "mesh_keep_largest", 0)), simplify=float(getattr(args, "mesh_simplify", 0.0)),
-                                       smooth=int(getattr(args, "mesh_smooth", 0)))
+                                       smooth=int(getattr(args, "mesh_smooth", 0)), refine=int(getattr(args, "mesh_refine", 0)))
     st = getattr(tensorf, "mesh_export_stats", None) or {}
     dropped = f"; dropped {st['components'] - st['components_kept']} of {st['components']} components, {st['triangles_dropped']} triangles" if "components" in st else ""
     merged = f"; simplified from {st['vertices_in']} vertices, {st['triangles_in']} triangles" if "triangles_in" in st else ""
     smoothed = f"; smoothed {st['smooth_iterations']} iterations, {st['boundary_edges']} boundary / {st['nonmanifold_edges']} non-manifold edges" \
         if "smooth_iterations" in st else ""
-    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles{dropped}{merged}{smoothed})")
+    refined = f"; refined {st['refine_iterations']} iterations, {st['refine_converged']} vertices converged, median |residual| " \
+        f"{st['refine_residual_median_before']:.3g} -> {st['refine_residual_median_after']:.3g}" if "refine_iterations" in st else ""
+    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles{dropped}{merged}{smoothed}{refined})")
     return path
 
 

@@ -254,6 +254,10 @@ class NerfPlusPlus(TensorVMSplit):
         raise NotImplementedError("NerfPlusPlus.render_normals: the normal pass marches uniform steps from the box entry (tvr_render_normals); NerfPlusPlus places "
                                   "its samples itself (explicit depths, tvr_render_z), and normal maps are not built for it")
 
+    def project_to_isosurface(self, verts, level, iterations=8, half_width=None, max_move=None, tol=None, pinned=None, stats=None):
+        raise NotImplementedError("NerfPlusPlus.project_to_isosurface: the projection is built for the models whose picture is the box's field alone; NerfPlusPlus "
+                                  "composes a background network behind it, and its meshes are not refined")
+
     def set_nerfplusplus(self, bg_freq=4, bg_view_freq=2, bg_D=4, radii=20):                  # :147-163
         self.bg_freq, self.bg_view_freq, self.radii, self.bg_D = bg_freq, bg_view_freq, radii, bg_D
         self.bg_embedder_position = Embedder(input_dim=4, max_freq_log2=bg_freq - 1, N_freqs=bg_freq)
