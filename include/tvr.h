@@ -798,6 +798,68 @@ int tvr_mesh_project(tvr_scene *scene, const float *verts, int64_t n_vertices, c
                      const float half_width[3], const float max_move[3], float tol, float *verts_out, size_t verts_out_bytes, float *residual_in /* or NULL */,
                      size_t residual_in_bytes, float *residual_out, size_t residual_out_bytes, int64_t *counts_dev /* [4], zeroed by the call */, void *stream);
 
+/* Depth-buffer rasteriser for indexed triangle meshes in the camera conventions of rays.py (csrc/tvr_mesh_raster.hip): what puts an exported mesh into the image space
+ * of tvr_render / tvr_render_normals.  ADDITIVE exports: TVR_VERSION is unchanged.  verts [n_vertices][3] fp32 WORLD positions, faces [n_triangles][3] int32.
+ * All arithmetic is fp32 with every operation rounded on its own (no fused multiply-add), in exactly the order written; divisions and the square root are IEEE correctly
+ * rounded.  A dot product a . b is (a.x * b.x + a.y * b.y) + a.z * b.z; a cross product a x b is (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x).
+ * CAMERA (tvr_mesh_camera).  c2w[12]: 3 x 4 row-major, the matrix rays.get_rays takes (after the BLENDER2OPENCV product); R = its 3 x 3 part, o = its last column.
+ *   Pixel p = j * W + i has the camera-space direction dir = (-(((i + .5) - cx) / fx), ((j + .5) - cy) / fy, -1): rays.get_ray_directions, so pixel p's ray is row p of
+ *   rays.frame_rays.  A vertex goes to camera space as q = R^T (v - o): d = v - o, q_k = (d_0 * R[0][k] + d_1 * R[1][k]) + d_2 * R[2][k]; the point o + s * R * dir of
+ *   the pixel's ray is q = s * dir.  The camera looks along -z: a corner's camera depth is -q.z.
+ * COVERAGE: homogeneous edge functions, no clipping (a triangle that crosses the camera plane is handled by the same test).  For triangle t with camera-space corners
+ *   q0, q1, q2 (vertex indices v0, v1, v2):  n_0 = q1 x q2, n_1 = q2 x q0, n_2 = q0 x q1;  det = q0 . n_0;  sg = +1 if det > 0, -1 if det < 0.  A triangle with det == 0
+ *   (or NaN) or a non-finite camera-space coordinate is SKIPPED and counted.  E_k = sg * (dir . n_k).  Edge k runs from corner (k+1)%3 to corner (k+2)%3; the pixel is
+ *   covered iff for every k: E_k > 0, or E_k == 0 and owner_k, with owner_k = (vertex index at the edge's start < vertex index at its end) XOR (sg < 0).
+ *   a x b and b x a are exact negations of each other, so two triangles that share an edge evaluate it to exactly opposite values: a ray through the shared edge of two
+ *   equally facing triangles is claimed by exactly one of them — no pinholes, no double claims, whatever the rounding of the values.  ACCEPTED: a ray exactly through a
+ *   vertex (two E_k == 0) may be claimed by none of the fan around it.
+ *   cull != 0 drops the triangles with det > 0: for a proper rotation R those are the ones whose outward side (right-hand rule, the orientation of tvr_mesh_emit with
+ *   flip == 0) faces away from the camera; det < 0 faces it.
+ * DEPTH, from the triangle's plane (det / sum of E loses four digits to cancellation at a camera distance of 4; the plane form does not):
+ *   pn = (q1 - q0) x (q2 - q0);  s = (pn . q0) / (dir . pn);  depth = s * sqrt(dir . dir)  — the Euclidean distance from o, what tvr_render's depth_map measures along the
+ *   loader's unit directions.  A covered pixel counts only if depth is finite and > near.
+ * BOX.  A triangle is offered the pixels of its screen box only.  With z_k = -q_k.z:  all three z_k <= 0: no pixel (wholly behind).  Some z_k <= 0: the whole image (the
+ *   price of not clipping).  Else u_k = cx - fx * (q_k.x / z_k), w_k = cy + fy * (q_k.y / z_k), and the box is  i in max(ceil(min u - 1.5), 0) .. min(floor(max u + .5), W-1),
+ *   j likewise from w and H: the pixels whose centres lie within one pixel of the corners' extent.  The pad is three orders of magnitude above the rounding of the
+ *   edge functions for any triangle that is not a sliver of a 10^-4 of a pixel, so the box changes no result; it is part of the definition so that it is one.
+ * RESULT per pixel: the covered triangle with the smallest depth; ties in depth go to the smallest triangle index.
+ *   depth [H*W] fp32, +inf where nothing is hit;  tri [H*W] int32, -1 where nothing is hit;  bary [H*W][3]: b_k = E_k / ((E_0 + E_1) + E_2) of the winner, zeros where
+ *   nothing is hit;  attr_out [H*W][n_attr] (attr [n_vertices][n_attr], n_attr <= TVR_MESH_RASTER_MAX_ATTR) = (b_0 * a[v0] + b_1 * a[v1]) + b_2 * a[v2], zeros where
+ *   nothing is hit;  counts_dev int32[4], zeroed by the call on `stream` (unless the fault flag is raised) = {pixels hit, triangles skipped, triangles that covered no pixel (culled, behind, off screen
+ *   or between pixel centres; whether another triangle won the pixel does not matter), triangles that took the large path}.
+ *   depth, tri, bary, attr_out and the first three counts are functions of (mesh, camera) alone: they do not depend on launch geometry, on the order atomics land in,
+ *   or on large_bbox.
+ * Mechanism, one fixed launch sequence without a host read: check the face indices; clear H*W 64-bit keys to all ones; one lane per triangle sets it up and walks a box
+ *   of at most large_bbox pixels (0 = TVR_MESH_RASTER_LARGE_BBOX) itself, a larger one goes to a queue (one atomic add per wave); a fixed grid of workgroups then draws the queue's
+ *   entries, 256 lanes striding over one box, a box shared by grid / entries workgroups when there are fewer entries than workgroups; a last kernel unpacks every pixel's key and recomputes E_k, b_k and the attributes by the same expressions.  A claim is
+ *   one 64-bit atomicMin of (depth bits << 32) | t (depth > 0: the bit pattern orders as the value), skipped when a relaxed agent-scope load shows a key that is not
+ *   larger (keys only decrease: a stale read can cost a redundant atomic, never a wrong skip).  No workgroup waits for another.
+ *   A face index outside 0 .. n_vertices-1 sets *fault_flag_dev = 1 and NOTHING else is written (the flag is only ever set; the caller zeroes it).  No load or store
+ *   leaves the caller's buffers whatever faces, verts and scratch hold.
+ * scratch: tvr_mesh_raster_scratch_bytes (256-byte aligned): 256 B + 8 B per pixel + 4 B per triangle, each array rounded up to 256 B; 0 for counts out of range.
+ * n_triangles == 0 is valid and yields an empty image (verts / faces may then be NULL).  Errors, all before any launch: TVR_ERR_INVALID for a NULL cam / depth / tri /
+ *   bary / scratch / counts_dev / fault_flag_dev, NULL faces or verts where there are triangles, a negative count, H or W < 1, a non-finite camera entry, fx or fy <= 0,
+ *   near < 0 or non-finite, cull outside 0 / 1, large_bbox < 0, n_attr outside 0 .. TVR_MESH_RASTER_MAX_ATTR, attr or attr_out NULL with n_attr > 0, a misaligned scratch;
+ *   TVR_ERR_UNSUPPORTED for H * W, n_triangles or n_vertices >= 2^31 and for H or W above TVR_MESH_RASTER_MAX_SIDE = 2^24 (beyond it a pixel centre i + .5
+ *   and the box's clamp (float)(W - 1) are no longer exact fp32 numbers, and "inside the image by construction" would not hold); TVR_ERR_SCRATCH for an undersized depth / tri / bary / attr_out / scratch (tvr_last_error()
+ *   names the buffer).
+ * NOT promised: anti-aliasing (one sample at the pixel centre), anything about rays exactly through a vertex, a facing rule for an improper R. */
+#define TVR_MESH_RASTER_LARGE_BBOX 64
+#define TVR_MESH_RASTER_MAX_ATTR 8
+#define TVR_MESH_RASTER_MAX_SIDE 16777216          /* 2^24: the largest H or W */
+typedef struct {
+    float c2w[12];
+    int32_t H, W;
+    float fx, fy, cx, cy;
+    float near_;                   /* >= 0 */
+    int32_t cull;                  /* 0 / 1 */
+    int32_t large_bbox;            /* pixels; 0 = TVR_MESH_RASTER_LARGE_BBOX */
+} tvr_mesh_camera;
+size_t tvr_mesh_raster_scratch_bytes(int64_t n_triangles, int32_t H, int32_t W);
+int tvr_mesh_raster(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const tvr_mesh_camera *cam, const float *attr /* or NULL */,
+                    int32_t n_attr, float *depth, size_t depth_bytes, int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes, float *attr_out /* or NULL */,
+                    size_t attr_out_bytes, void *scratch, size_t scratch_bytes, int32_t *counts_dev /* [4] */, uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,11 @@ class NgpNetParams(C.Structure):         # tvr_ngp_net_params
     _fields_ = [(n, C.c_void_p) for n in ("density0", "density1", "rgb0", "rgb1", "rgb2")]
 
 
+class MeshCamera(C.Structure):          # tvr_mesh_camera
+    _fields_ = [("c2w", C.c_float * 12), ("H", C.c_int32), ("W", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near_", C.c_float), ("cull", C.c_int32), ("large_bbox", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/tvr.h and include/tvr_ngp.h declare
 SYMBOLS = {
     "tvr_version": (C.c_int, []),
@@ -213,6 +218,9 @@ SYMBOLS = {
                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "tvr_mesh_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float,
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "tvr_mesh_raster_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "tvr_mesh_raster": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(MeshCamera), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/tvr_ngp.h
     "tvr_ngp_update_bitfield": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tvr_ngp_sample_scratch_bytes": (C.c_size_t, [C.c_int64]),

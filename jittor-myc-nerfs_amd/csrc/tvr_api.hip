@@ -2182,3 +2182,59 @@ int tvr_mesh_project(tvr_scene *s, const float *verts, int64_t n_vertices, const
                                 residual_in, residual_out, (unsigned long long *)counts_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- z-buffer rasteriser of indexed triangle meshes (tvr_mesh_raster.hip) -------------------------------------------------------------------------------------------------
+static int raster_counts(const char *fn, int64_t n_triangles, int64_t H, int64_t W)
+{
+    if (n_triangles < 0) return fail(TVR_ERR_INVALID, "%s: n_triangles = %lld is negative", fn, (long long)n_triangles);
+    if (H < 1 || W < 1) return fail(TVR_ERR_INVALID, "%s: H = %lld, W = %lld: an image has at least one row and one column", fn, (long long)H, (long long)W);
+    if (H > TVR_MESH_RASTER_MAX_SIDE || W > TVR_MESH_RASTER_MAX_SIDE)
+        return fail(TVR_ERR_UNSUPPORTED, "%s: H = %lld, W = %lld: a side above 2^24 = %d pixels is not taken (pixel centres i + .5 and the box's float clamp are exact "
+                    "only up to there)", fn, (long long)H, (long long)W, TVR_MESH_RASTER_MAX_SIDE);
+    if (H * W > INT32_MAX || n_triangles > INT32_MAX)
+        return fail(TVR_ERR_UNSUPPORTED, "%s: H * W = %lld / n_triangles = %lld: pixel and triangle indices are int32 and both counts must stay below 2^31", fn,
+                    (long long)(H * W), (long long)n_triangles);
+    return TVR_OK;
+}
+
+size_t tvr_mesh_raster_scratch_bytes(int64_t n_triangles, int32_t H, int32_t W)
+{
+    if (raster_counts(__func__, n_triangles, H, W) != TVR_OK) return 0;
+    return mesh_raster_scratch_bytes(n_triangles, (long long)H * W);
+}
+
+int tvr_mesh_raster(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const tvr_mesh_camera *cam, const float *attr, int32_t n_attr,
+                    float *depth, size_t depth_bytes, int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes, float *attr_out, size_t attr_out_bytes, void *scratch,
+                    size_t scratch_bytes, int32_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    if (!cam) return fail(TVR_ERR_INVALID, "%s: cam is NULL", __func__);
+    if (!depth || !tri || !bary || !scratch || !counts_dev || !fault_flag_dev)
+        return fail(TVR_ERR_INVALID, "%s: depth / tri / bary / scratch / counts_dev / fault_flag_dev is NULL", __func__);
+    if (n_vertices < 0) return fail(TVR_ERR_INVALID, "%s: n_vertices = %lld is negative", __func__, (long long)n_vertices);
+    if (n_triangles > 0 && (!faces || !verts)) return fail(TVR_ERR_INVALID, "%s: faces / verts is NULL with %lld triangles", __func__, (long long)n_triangles);
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(cam->c2w[k])) return fail(TVR_ERR_INVALID, "%s: cam->c2w[%d] = %g is not finite", __func__, k, (double)cam->c2w[k]);
+    if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !(cam->fx > 0.0f) || !(cam->fy > 0.0f))
+        return fail(TVR_ERR_INVALID, "%s: fx = %g, fy = %g must be finite and > 0", __func__, (double)cam->fx, (double)cam->fy);
+    if (!std::isfinite(cam->cx) || !std::isfinite(cam->cy)) return fail(TVR_ERR_INVALID, "%s: cx = %g, cy = %g must be finite", __func__, (double)cam->cx, (double)cam->cy);
+    if (!std::isfinite(cam->near_) || cam->near_ < 0.0f) return fail(TVR_ERR_INVALID, "%s: near = %g must be finite and >= 0", __func__, (double)cam->near_);
+    if (cam->cull != 0 && cam->cull != 1) return fail(TVR_ERR_INVALID, "%s: cull = %d is neither 0 nor 1", __func__, (int)cam->cull);
+    if (cam->large_bbox < 0) return fail(TVR_ERR_INVALID, "%s: large_bbox = %d is negative (0 = the default of %d pixels)", __func__, (int)cam->large_bbox,
+                                         TVR_MESH_RASTER_LARGE_BBOX);
+    if (n_attr < 0 || n_attr > TVR_MESH_RASTER_MAX_ATTR) return fail(TVR_ERR_INVALID, "%s: n_attr = %d outside 0 .. %d", __func__, (int)n_attr, TVR_MESH_RASTER_MAX_ATTR);
+    if (n_attr > 0 && (!attr || !attr_out)) return fail(TVR_ERR_INVALID, "%s: attr / attr_out is NULL with n_attr = %d", __func__, (int)n_attr);
+    int rc = raster_counts(__func__, n_triangles, cam->H, cam->W);
+    if (rc != TVR_OK) return rc;
+    if (n_vertices > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices = %lld: vertex indices are int32", __func__, (long long)n_vertices);
+    if ((uintptr_t)scratch % 256) return fail(TVR_ERR_INVALID, "%s: scratch is not 256-byte aligned", __func__);
+    const int64_t n_pixels = (int64_t)cam->H * cam->W;
+    NEED("depth [H*W]", depth_bytes, n_pixels, 1);
+    NEED("tri [H*W]", tri_bytes, n_pixels, 1);
+    NEED("bary [H*W,3]", bary_bytes, n_pixels, 3);
+    if (n_attr > 0) NEED("attr_out [H*W,n_attr]", attr_out_bytes, n_pixels, n_attr);
+    const size_t want = mesh_raster_scratch_bytes(n_triangles, n_pixels);
+    if (scratch_bytes < want) return fail(TVR_ERR_SCRATCH, "%s: scratch holds %zu B, tvr_mesh_raster_scratch_bytes asks for %zu B", __func__, scratch_bytes, want);
+    HIP_TRY(launch_mesh_raster(verts, n_vertices, faces, n_triangles, *cam, n_attr > 0 ? attr : nullptr, n_attr, depth, tri, bary, n_attr > 0 ? attr_out : nullptr, scratch,
+                               (int *)counts_dev, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

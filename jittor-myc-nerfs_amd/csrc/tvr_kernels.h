@@ -269,3 +269,11 @@ hipError_t launch_mesh_smooth(const float *verts, long long n_vertices, const in
 hipError_t launch_mesh_project(const SceneDev &sc, const CpDev *cp, const float *verts, long long n_vertices, const unsigned char *pinned, float target_feature,
                                int iterations, const float h[3], const float inv2h[3], const float max_move[3], float tol, float *verts_out, float *residual_in,
                                float *residual_out, unsigned long long *counts, hipStream_t stream);
+
+// tvr_mesh_raster.hip: the z-buffer rasteriser of indexed triangle meshes (include/tvr.h tvr_mesh_raster).  Scratch: a header of MESH_RASTER_HEADER_BYTES {uint32 bad
+// index seen, uint32 queue length}, H*W 64-bit keys (depth bits << 32 | triangle), a queue of n_triangles int32 (triangles whose box exceeds large_bbox), each array
+// rounded up to 256 B.
+#define MESH_RASTER_HEADER_BYTES 256
+size_t mesh_raster_scratch_bytes(long long n_triangles, long long n_pixels);
+hipError_t launch_mesh_raster(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const tvr_mesh_camera &cam, const float *attr, int n_attr,
+                              float *depth, int *tri, float *bary, float *attr_out, void *scratch, int *counts, unsigned *fault, hipStream_t stream);

@@ -302,3 +302,82 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath=None, N_vis=
     if writer is not None:
         writer.close()
     return frames
+
+
+# ---- mesh views beside the rendered views (mesh.render_mesh) ------------------------------------------------------------------------------------------
+def mesh_agreement(mesh_depth, mesh_hit, field_depth, field_acc, voxel) -> dict:
+    """How well a mesh view (mesh.render_mesh) and a field view (TensorBase.render_normals' depth and acc) of one camera agree, in image space:
+      iou               intersection over union of mesh_hit with field_acc > 0.5 (1.0 when both are empty)
+      depth_median_vox  over the pixels with mesh_hit and field_acc > 0.99: median of |mesh depth - field depth| / voxel
+      depth_p95_vox     their 95th percentile
+      depth_pixels      how many such pixels there are (the two depth entries are NaN when there is none)
+    voxel: the edge of one export voxel in world units (a number, or three whose mean is taken).  Pure; tensors on either device or arrays."""
+    def host(a, dt):
+        return np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=dt).reshape(-1)
+    md, fd, fa = host(mesh_depth, np.float64), host(field_depth, np.float64), host(field_acc, np.float64)
+    mh = host(mesh_hit, bool)
+    if not (md.shape == mh.shape == fd.shape == fa.shape):
+        raise ValueError(f"mesh_agreement: the four maps hold {md.size}, {mh.size}, {fd.size} and {fa.size} pixels")
+    vox = float(np.mean(np.asarray(voxel, dtype=np.float64)))
+    if not (np.isfinite(vox) and vox > 0):
+        raise ValueError(f"voxel = {voxel!r}: a positive finite edge length")
+    solid = fa > 0.5
+    union = int((mh | solid).sum())
+    both = mh & (fa > 0.99)
+    err = np.abs(md[both] - fd[both]) / vox
+    return {"iou": float((mh & solid).sum() / union) if union else 1.0,
+            "depth_median_vox": float(np.median(err)) if err.size else float("nan"),
+            "depth_p95_vox": float(np.percentile(err, 95)) if err.size else float("nan"),
+            "depth_pixels": int(err.size)}
+
+
+@torch.no_grad()
+def evaluation_mesh(test_dataset, tensorf, verts, faces, savePath, normals=None, colors=None, N_vis=-1, white_bg=True, device="cuda", voxel=None, N_samples=-1):
+    """Views of a mesh from the test poses, beside the rendered views: writes `{savePath}/mesh/{idx:03d}.png` per pose (H, W, focal and poses are the ones the dataset's
+    rays were made from, so pixel p of the picture is ray p of the frame) and returns the per-frame mesh_agreement against tensorf.render_normals' depth and acc.
+
+    verts [V,3] / faces [F,3]: tensors or arrays (a PLY read by mesh.read_ply_attributes).  colors [V,3] uint8 -> the colour view; else normals [V,3] -> the normal
+    view; with neither a flat-shaded view from the face normals (mesh.mesh_view_to_rgb8).  voxel: the export voxel in world units (default: extent / (gridSize - 1)
+    of the field, the voxel of export_mesh(spacing="samples") at the field's own grid).  The agreement means something for meshes exported with spacing="samples":
+    the reference's convention shrinks the mesh by (N - 1) / N about aabb[0], and a PLY does not record which was used.
+    NerfPlusPlus has no normal pass: the pictures are written and None is returned.  Nothing here is called by evaluation() / evaluation_path()."""
+    from . import mesh as M
+    dev = torch.device(device)
+    v = torch.as_tensor(np.asarray(verts) if not torch.is_tensor(verts) else verts).to(device=dev, dtype=torch.float32)
+    f = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces).to(device=dev, dtype=torch.int32)
+    attr, mode = None, "normal"
+    if colors is not None:
+        attr, mode = torch.as_tensor(np.asarray(colors) if not torch.is_tensor(colors) else colors).to(device=dev, dtype=torch.float32), "color"
+    elif normals is not None:
+        attr = torch.as_tensor(np.asarray(normals) if not torch.is_tensor(normals) else normals).to(device=dev, dtype=torch.float32)
+    fn = M.face_normals(v, f) if attr is None else None
+    from .variants import NerfPlusPlus
+    has_normal_pass = not isinstance(tensorf, NerfPlusPlus)               # its render_normals refuses: the samples lie at explicit depths
+    if voxel is None:
+        ext = (tensorf.aabb[1] - tensorf.aabb[0]).detach().cpu().numpy().astype(np.float64)
+        voxel = ext / (np.asarray([int(g) for g in tensorf.gridSize], dtype=np.float64) - 1.0)
+    os.makedirs(savePath + "/mesh", exist_ok=True)
+    W, H = test_dataset.img_wh
+    n = test_dataset.all_rays.shape[0]
+    interval = 1 if N_vis < 0 else max(n // N_vis, 1)
+    writer = _ImageWriter()
+    out = []
+    for idx, k in enumerate(range(0, n, interval)):
+        depth, tri, _, a = M.render_mesh(v, f, test_dataset.poses[k], H, W, test_dataset.focal, attributes=attr)
+        img = M.mesh_view_to_rgb8(tri, a, mode, white_bg=white_bg, face_normal=fn)
+        writer.write(f"{savePath}/mesh/{idx:03d}.png", img.cpu().numpy())
+        if has_normal_pass:
+            rays = test_dataset.all_rays[k].view(-1, 6).to(dev)
+            _, acc, fdepth = tensorf.render_normals(rays, N_samples=N_samples)
+            out.append(mesh_agreement(depth, tri >= 0, fdepth, acc, voxel))
+    writer.close()
+    return out if has_normal_pass else None
+
+
+def mesh_agreement_summary(frames) -> dict:
+    """{"frames": [...], "mean": {...}} of evaluation_mesh's list: the mean of each entry over the frames where it is a number."""
+    mean = {}
+    for key in ("iou", "depth_median_vox", "depth_p95_vox", "depth_pixels"):
+        vals = [fr[key] for fr in frames if np.isfinite(fr[key])]
+        mean[key] = float(np.mean(vals)) if vals else float("nan")
+    return {"frames": list(frames), "mean": mean}

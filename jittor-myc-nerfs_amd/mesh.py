@@ -522,3 +522,120 @@ def read_ply_attributes(path):
         attrs["colors"] = np.stack((vr["red"], vr["green"], vr["blue"]), -1).astype(np.uint8).reshape(nv, 3)
     verts = np.stack((vr["x"], vr["y"], vr["z"]), -1).astype(np.float32).reshape(nv, 3)
     return verts, rows["v"].astype(np.int32).reshape(nf, 3), attrs
+
+
+# ---- z-buffer rasteriser (csrc/tvr_mesh_raster.hip, include/tvr.h tvr_mesh_raster) ------------------------------------------------------------------------------------------
+RASTER_LARGE_BBOX = 64      # include/tvr.h TVR_MESH_RASTER_LARGE_BBOX: a screen box above this many pixels is drawn by a workgroup, not by one lane
+RASTER_MAX_ATTR = 8         # include/tvr.h TVR_MESH_RASTER_MAX_ATTR
+
+
+def mesh_camera(c2w, H: int, W: int, focal, center=None, near: float = 0.0, cull: bool = False, large_bbox: int = 0) -> "L.MeshCamera":
+    """The tvr_mesh_camera of a pose: c2w is the 3x4 (or 4x4) matrix rays.get_rays takes, focal a number or (fx, fy), center (cx, cy) or None = (W/2, H/2)."""
+    m = np.asarray(c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else c2w, dtype=np.float32)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"c2w has shape {m.shape}: a 3x4 or 4x4 camera-to-world matrix is taken")
+    if torch.is_tensor(focal):
+        focal = focal.detach().cpu().tolist()
+    fx, fy = (focal, focal) if np.ndim(focal) == 0 else tuple(focal)
+    cx, cy = (W / 2, H / 2) if center is None else tuple(center)
+    cam = L.MeshCamera()
+    cam.c2w[:] = [float(x) for x in m[:3, :4].reshape(-1)]
+    cam.H, cam.W, cam.fx, cam.fy, cam.cx, cam.cy = int(H), int(W), float(fx), float(fy), float(cx), float(cy)
+    cam.near_, cam.cull, cam.large_bbox = float(near), 1 if cull else 0, int(large_bbox)
+    return cam
+
+
+def render_mesh(verts: torch.Tensor, faces: torch.Tensor, c2w, H: int, W: int, focal, center=None, near: float = 0.0, cull: bool = False, attributes=None,
+                large_bbox: int = 0, stats: dict = None):
+    """Depth-buffer picture of an indexed triangle mesh from one camera, on the device -> (depth [H,W] float32, tri [H,W] int32, bary [H,W,3] float32,
+    attr [H,W,A] float32 or None).
+
+    The camera is rays.py's: c2w is what rays.get_rays takes (after BLENDER2OPENCV), pixel (j, i) looks along get_ray_directions(H, W, focal, center)[j, i], so it is
+    the ray of row j * W + i of frame_rays.  depth is the Euclidean distance from the camera to the nearest triangle the pixel's ray passes through (+inf where there is
+    none), tri that triangle's index (-1), bary its barycentric weights at the hit, attr the per-vertex `attributes` [V, A] (A <= 8) interpolated with them (zeros).
+    One sample per pixel centre; a ray through an edge two triangles share belongs to exactly one of them; ties in depth go to the smaller index; cull drops triangles
+    whose outward side (right-hand rule) faces away.  The result is a function of the arguments alone: the same bit for bit on every run and for every large_bbox (the
+    box size, in pixels, above which a triangle is drawn by a workgroup instead of one lane; 0 = 64).  include/tvr.h tvr_mesh_raster has the arithmetic.
+    A face index outside the vertices raises TvrError.  No CPU fallback.  `stats` (a dict) receives pixels_hit / triangles_skipped (zero area or non-finite) /
+    triangles_without_pixel / triangles_large."""
+    f = _faces_on_device(faces, "render_mesh")
+    if not torch.is_tensor(verts) or verts.device != f.device or verts.dim() != 2 or verts.shape[1] != 3:
+        raise L.TvrError(f"render_mesh takes verts [V, 3] on the faces' device ({f.device})")
+    v = verts.detach().to(torch.float32).contiguous()
+    V, F, dev = int(v.shape[0]), int(f.shape[0]), f.device
+    cam = mesh_camera(c2w, H, W, focal, center, near, cull, large_bbox)
+    a, A = None, 0
+    if attributes is not None:
+        if not torch.is_tensor(attributes) or attributes.device != dev or attributes.dim() != 2 or attributes.shape[0] != V:
+            raise L.TvrError(f"render_mesh takes attributes [V, A] on the faces' device ({dev}), one row per vertex")
+        a = attributes.detach().to(torch.float32).contiguous()
+        A = int(a.shape[1])
+        if A and V == 0:
+            a = torch.zeros((1, A), dtype=torch.float32, device=dev)        # no vertex, no row to read: the library still wants a pointer beside n_attr > 0
+    lib = L.lib()
+    nbytes = lib.tvr_mesh_raster_scratch_bytes(F, cam.H, cam.W)
+    if nbytes == 0:
+        raise L.TvrError("render_mesh: " + lib.tvr_last_error().decode(errors="replace"))
+    scratch = L.dev_bytes(nbytes, dev, what="mesh raster scratch")
+    depth = L.dev_empty((cam.H, cam.W), torch.float32, dev, what="mesh raster depth")
+    tri = L.dev_empty((cam.H, cam.W), torch.int32, dev, what="mesh raster tri")
+    bary = L.dev_empty((cam.H, cam.W, 3), torch.float32, dev, what="mesh raster bary")
+    out = L.dev_empty((cam.H, cam.W, A), torch.float32, dev, what="mesh raster attr") if A else None
+    counts = L.dev_empty((4,), torch.int32, dev, what="mesh raster counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh raster fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_raster(_ptr(v), V, _ptr(f), F, C.byref(cam), _ptr(a) if A else None, A, depth.data_ptr(), L.nbytes(depth), tri.data_ptr(), L.nbytes(tri),
+                                bary.data_ptr(), L.nbytes(bary), out.data_ptr() if A else None, L.nbytes(out) if A else 0, scratch.data_ptr(), L.nbytes(scratch),
+                                counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_raster")
+    if int(flag.item()) != 0:
+        raise L.TvrError(f"tvr_mesh_raster raised its fault flag: a face index lies outside 0 .. {V - 1} (include/tvr.h)")
+    if stats is not None:
+        hit, skipped, nopix, large = (int(x) for x in counts.cpu().tolist())
+        stats.update(pixels_hit=hit, triangles_skipped=skipped, triangles_without_pixel=nopix, triangles_large=large)
+    return depth, tri, bary, out
+
+
+def render_mesh_frame(verts, faces, transform_matrix, H: int, W: int, camera_angle_x: float, **kwargs):
+    """render_mesh from one frame of a transforms_*.json, as rays.frame_rays reads it: pose = transform_matrix @ BLENDER2OPENCV, focal = focal_from_angle."""
+    from . import rays as R
+    pose = np.asarray(transform_matrix, dtype=np.float64) @ R.BLENDER2OPENCV
+    return render_mesh(verts, faces, pose.astype(np.float32), H, W, R.focal_from_angle(float(camera_angle_x), W), **kwargs)
+
+
+def face_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Unit face normals [F,3] (right-hand rule; zeros for a face without area), on the tensors' device.  Host-side helper of the flat-shaded view."""
+    v, f = verts.to(torch.float32), faces.to(torch.int64)
+    n = torch.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]], dim=-1)
+    return n / n.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+
+
+def mesh_view_to_rgb8(tri: torch.Tensor, attr, mode: str = "normal", white_bg: bool = True, face_normal=None) -> torch.Tensor:
+    """uint8 [H,W,3] picture of a render_mesh result.  tri [H,W] (>= 0 where hit), attr [H,W,3] the interpolated attributes or None.
+
+    mode "normal": attr are interpolated vertex normals; they are renormalised and coloured as evaluation.normal_map_to_rgb8 colours a unit normal (0.5 n + 0.5), with
+    the hit mask in the place of acc.  mode "color": attr are vertex colours in 0 .. 255 (the PLY's uint8 values) and are shown as they are.  attr None: a flat-shaded
+    view from `face_normal` [F,3] (face_normals(verts, faces)), coloured like "normal" — what a bare reference-style PLY can show.  Pixels without a hit show the
+    background (white or black).  Pure; either device."""
+    hit = tri >= 0
+    bg = 1.0 if white_bg else 0.0
+    if attr is None:
+        if face_normal is None:
+            raise ValueError("mesh_view_to_rgb8 without attributes takes face_normal [F, 3] (mesh.face_normals) for the flat-shaded view")
+        fn = face_normal.to(torch.float32).reshape(-1, 3)
+        if fn.shape[0] == 0:                                          # a mesh without faces: nothing is hit, the picture is the background
+            fn = torch.zeros((1, 3), dtype=torch.float32, device=fn.device)
+        n = fn[tri.clamp_min(0).to(torch.int64)]
+        mode = "normal"
+    else:
+        if attr.shape[-1] != 3:
+            raise ValueError(f"mesh_view_to_rgb8 takes three attribute channels, got {attr.shape[-1]}")
+        n = attr.to(torch.float32)
+    if mode == "normal":
+        n = n / n.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+        x = 0.5 * n + 0.5
+    elif mode == "color":
+        x = n / 255.0
+    else:
+        raise ValueError(f"mode = {mode!r}: 'normal' or 'color'")
+    m = hit.unsqueeze(-1)
+    x = torch.where(m, x, torch.full_like(x, bg))
+    return torch.round(255.0 * x.clamp(0.0, 1.0)).to(torch.uint8)

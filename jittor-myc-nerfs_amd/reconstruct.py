@@ -10,7 +10,7 @@ What differs from the reference, on purpose:
     (train.py:172 calls it unconditionally and fails for the others);
   * `--export_mesh 1` (train.py:41-59) extracts the surface with the HIP marching cubes (mesh.py) instead of skimage and writes the PLY without plyfile; the
     level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_min_faces N` / `--mesh_keep_largest K` drop connected components (floaters), `--mesh_simplify S` merges the vertices of every cell of S voxels (vertex clustering), `--mesh_smooth N` runs N Taubin smoothing iterations, `--mesh_refine N` projects the vertices back onto the iso-surface with N Newton iterations, `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
-    geometry), and the command ends after the export instead of falling through into a training run;
+    geometry), `--render_mesh 1` (with `--render_only 1 --render_test 1`) draws the exported mesh from every test pose beside the rendered views and reports how well the two agree, and the command ends after the export instead of falling through into a training run;
   * progress is a plain print every `progress_refresh_rate` iterations.
 Host-side plumbing only: every pixel comes from the HIP kernels through `OctreeRender_trilinear_fast`.
 """
@@ -26,7 +26,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from .evaluation import BlenderRays, evaluation, evaluation_path
+from .evaluation import BlenderRays, evaluation, evaluation_mesh, evaluation_path, mesh_agreement_summary
 from .cp import TensorCP
 from .field import TensorVMSplit, load_checkpoint
 from .losses import TVLoss
@@ -96,6 +96,13 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--mesh_refine", type=int, default=0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
+    # (not a reference option) views of an exported mesh beside the rendered test views (mesh.render_mesh): with --render_only 1 --render_test 1, read --mesh_file
+    # (default: <ckpt minus .th>.ply), write imgs_test_all/mesh/{idx:03d}.png per pose and imgs_test_all/mesh_agreement.json
+    p.add_argument("--render_mesh", type=int, default=0,
+                   help="1: also draw the exported mesh from every test pose and report how well it agrees with the rendered depth and opacity (silhouette IoU, depth "
+                        "error in export voxels).  The agreement is meaningful for meshes exported with spacing='samples': the reference's voxel-size convention shrinks "
+                        "the mesh by (N - 1) / N about aabb[0], and the PLY does not record which was used.")
+    p.add_argument("--mesh_file", type=str, default=None, help="the PLY --render_mesh 1 reads (default: <ckpt minus .th>.ply)")
     for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int), ("mesh_grid", int)):
         p.add_argument("--" + name, type=typ, action="append")
     argv = sys.argv[1:] if cmd is None else list(cmd)
@@ -175,11 +182,47 @@ def render_test(args, device="cuda"):
         out["test"] = evaluation(test_dataset, tensorf, args, OctreeRender_trilinear_fast, f"{logfolder}/imgs_test_all/", N_vis=-1, N_samples=-1,
                                  white_bg=test_dataset.white_bg, ndc_ray=args.ndc_ray, device=device, normal_maps=normal_maps)
         print(f"======> {args.expname} test all psnr: {np.mean(out['test'])} <========================")
+        if getattr(args, "render_mesh", 0):
+            out["mesh"] = render_mesh_views(args, test_dataset, tensorf, f"{logfolder}/imgs_test_all/", device)
     if args.render_path:
         out["path"] = evaluation_path(test_dataset, tensorf, [p.numpy() for p in test_dataset.poses], OctreeRender_trilinear_fast,
                                       f"{logfolder}/imgs_path_all/", N_vis=-1, N_samples=-1, white_bg=test_dataset.white_bg, ndc_ray=args.ndc_ray,
                                       device=device, normal_maps=normal_maps)
     return out
+
+
+def mesh_export_voxel(tensorf, mesh_grid=None):
+    """The export voxel [3] in world units that --render_mesh measures depth differences in: extent / (N - 1), N = --mesh_grid when given (the grid the PLY was exported
+    on), else the field's own gridSize — export_mesh's default grid.  A PLY does not record its grid: the value used goes into mesh_agreement.json."""
+    grid = [int(g) for g in (mesh_grid if mesh_grid else tensorf.gridSize)]
+    if len(grid) != 3 or min(grid) < 2:
+        raise ValueError(f"mesh_grid takes three sizes [nx, ny, nz] of at least 2; got {grid}")
+    ext = (tensorf.aabb[1] - tensorf.aabb[0]).detach().cpu().numpy().astype(np.float64)
+    return ext / (np.asarray(grid, dtype=np.float64) - 1.0)
+
+
+def render_mesh_views(args, test_dataset, tensorf, savePath, device="cuda"):
+    """--render_mesh 1: the PLY (--mesh_file, default <ckpt minus .th>.ply) drawn from every test pose into {savePath}/mesh/, and {savePath}/mesh_agreement.json with
+    evaluation.mesh_agreement per frame and its mean (no agreement for NerfPlusPlus, which has no normal pass: the file then says so)."""
+    import json
+    from .mesh import read_ply_attributes
+    path = getattr(args, "mesh_file", None) or f"{args.ckpt[:-3]}.ply"
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"--render_mesh 1 needs a mesh: {path!r} does not exist (write it with --export_mesh 1, or name one with --mesh_file)")
+    verts, faces, attrs = read_ply_attributes(path)
+    voxel = mesh_export_voxel(tensorf, getattr(args, "mesh_grid", None))
+    frames = evaluation_mesh(test_dataset, tensorf, verts, faces, savePath.rstrip("/"), normals=attrs.get("normals"), colors=attrs.get("colors"), N_vis=-1,
+                             white_bg=test_dataset.white_bg, device=device, voxel=voxel)
+    report = {"mesh_file": path, "voxel": [float(x) for x in voxel],
+              "voxel_from": "--mesh_grid" if getattr(args, "mesh_grid", None) else "the field's gridSize (pass the export's --mesh_grid if it was made on another grid)",
+              "note": "meaningful for meshes exported with spacing='samples' (the reference convention shrinks the mesh by (N - 1) / N about aabb[0])"}
+    report.update(mesh_agreement_summary(frames) if frames is not None else {"frames": None, "mean": None})
+    with open(os.path.join(savePath, "mesh_agreement.json"), "w") as fjson:
+        json.dump(report, fjson, indent=1)
+    if frames:
+        m = report["mean"]
+        print(f"mesh views of {path}: silhouette IoU {m['iou']:.4f}, depth error median {m['depth_median_vox']:.3f} / 95 % {m['depth_p95_vox']:.3f} export voxels")
+    return report
 
 
 @torch.no_grad()
@@ -381,6 +424,8 @@ def main(cmd: Optional[List[str]] = None):
     torch.manual_seed(20211202)                                                                    # train.py:396-397
     np.random.seed(20211202)
     args = config_parser(cmd)
+    if getattr(args, "render_mesh", 0) and not (args.render_only and args.render_test):
+        raise SystemExit("--render_mesh 1 draws the mesh beside the test renders: it needs --render_only 1 --render_test 1 (and --ckpt); nothing was done")
     if args.export_mesh:
         path = export_mesh(args)
         if not (args.render_only and (args.render_test or args.render_path)):
