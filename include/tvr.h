@@ -860,6 +860,48 @@ int tvr_mesh_raster(const float *verts, int64_t n_vertices, const int32_t *faces
                     int32_t n_attr, float *depth, size_t depth_bytes, int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes, float *attr_out /* or NULL */,
                     size_t attr_out_bytes, void *scratch, size_t scratch_bytes, int32_t *counts_dev /* [4] */, uint32_t *fault_flag_dev, void *stream);
 
+/* Per-triangle texture atlas of an indexed triangle mesh (csrc/tvr_mesh_texture.hip): colour resolution that does not depend on the triangle count.  ADDITIVE exports:
+ * TVR_VERSION is unchanged.  No UV unwrapping: every triangle gets its own right-angled patch, two triangles share a square, the layout is closed-form, and the atlas is
+ * a function of (mesh, field, patch size) alone.  All device arithmetic is fp32 with every operation rounded on its own (no fused multiply-add), in exactly the order
+ * written; divisions are IEEE correctly rounded.
+ * PARAMETERS.  P = patch side in texels, TVR_MESH_ATLAS_MIN_P = 5 <= P <= TVR_MESH_ATLAS_MAX_P = 64;  L = P - 4 = texel steps along a patch edge (an edge carries L + 1
+ *   samples);  F = n_triangles, S = ceil(F / 2) squares;  C >= 1 squares per atlas row.  The atlas is Wa = C * P texels wide and Ha = max(ceil(S / C), 1) * P high (so
+ *   Ha >= P even for F = 0), row-major: the linear index of texel (X, Y) is Y * Wa + X.  Ha * Wa < 2^31.
+ * PLACEMENT.  Triangle t lives in square s = t >> 1, half h = t & 1; the square's corner texel is (X0, Y0) = ((s % C) * P, (s / C) * P).  Texel (a, b) of a square,
+ *   0 <= a, b < P, belongs to half 0 if a + b <= P - 1, with local coordinates (x, y) = (a, b); else to half 1 with (x, y) = (P - 1 - a, P - 1 - b).  Every texel has
+ *   exactly one owner or none: none when its square is >= S, or when it lies in half 1 of the last square and F is odd.  Those report triangle -1.
+ * TEXEL TO POINT.  Local (x, y) of triangle t with corners v0, v1, v2 (faces[t][0..2]):  b1 = x / L, b2 = y / L, b0 = (1 - b1) - b2 (x, y, L converted to fp32, exact);
+ *   p = (b0 * v0 + b1 * v1) + b2 * v2 per coordinate.  The corner texels (0,0), (L,0), (0,L) reproduce v0, v1, v2 exactly for finite vertices (a coordinate -0 comes out
+ *   +0).  Texels with x + y > L are the GUTTER: extrapolated in the triangle's plane, not clamped, so the texture samples one continuous function across the hypotenuse.
+ * SAMPLING a hit (t, b0, b1, b2) (tvr_mesh_raster's tri and bary):  x = min(max(b1 * L, 0), L), y = min(max(b2 * L, 0), L) (a NaN becomes 0);  i = floor(x),
+ *   j = floor(y), fx = x - i, fy = y - j;  the taps T00 = T(i, j), T10 = T(i+1, j), T01 = T(i, j+1), T11 = T(i+1, j+1) are texels in the half's LOCAL coordinates, mapped
+ *   to the atlas by the half's rule;  top = T00 + fx * (T10 - T00), bot = T01 + fx * (T11 - T01), out = top + fy * (bot - top), per channel.  uint8 texels are converted
+ *   to fp32 as they are (0 .. 255, no scaling).
+ * WHY L = P - 4.  With exact barycentrics the four taps have x + y <= L + 1; with the rasteriser's rounded ones (b1 + b2 may exceed 1 by an ulp) x + y <= L + 2 = P - 2.
+ *   Both halves own their texels up to exactly that sum (half 0: a + b <= P - 1; half 1: x + y <= P - 2), so no tap of a hit reads the other triangle's texels or leaves
+ *   the square; one more ring is left for an external viewer's filtering.
+ * tvr_mesh_atlas_points: the n texels with linear indices texel0 .. texel0 + n - 1 (a range, so that a bake is chunked and its memory bounded):  pos_out [n][3] fp32 the
+ *   point, tri_out [n] int32 the owner; unowned texels get -1 and a zero point.  One lane per texel.  A face index outside 0 .. n_vertices-1 in a triangle of the square
+ *   rows the range touches (every triangle a texel of the range can belong to; the whole mesh when the range is the whole atlas) sets *fault_flag_dev = 1 and NOTHING
+ *   else is written; the flag is only ever set, the caller zeroes it, and a flag that is already up on entry likewise keeps the call from writing.
+ * tvr_mesh_texture_sample: per pixel p of a tvr_mesh_raster result (tri [n_pix], bary [n_pix][3]) the sampling rule on `atlas` [Ha][Wa][3], fmt 0 = uint8, 1 = fp32;
+ *   out [n_pix][3] fp32, zeros where tri < 0 or tri >= n_triangles.  Every tri is compared with n_triangles and every tap's index with Ha * Wa before a load (a tap
+ *   outside reads as 0; none is for a consistent atlas).  bary values that are no barycentrics (b1 + b2 far above 1) stay inside the square but may read the other half.
+ * Both are memory-bound gathers without atomics, LDS or scratch: 16 B written per texel (the 36 + 12 B of a triangle are shared by its ~P^2 / 2 texels);
+ *   16 B read + 4 taps x 3 B (uint8) or x 12 B (fp32) gathered + 12 B written per pixel.  No load or store leaves the caller's buffers whatever faces, tri and bary hold.
+ * n_triangles == 0, n == 0 and n_pix == 0 are valid (the arrays of that length may be NULL).  Errors, all before any launch, tvr_last_error() names the argument:
+ *   TVR_ERR_INVALID for a NULL pointer where data is due, a negative count, P outside 5 .. 64, C < 1, a range that leaves the atlas, fmt outside 0 / 1, Ha or Wa that
+ *   are not the ones F, P, C make;  TVR_ERR_UNSUPPORTED for Ha * Wa, n_triangles, n_vertices or n_pix >= 2^31;  TVR_ERR_SCRATCH for an undersized pos_out / tri_out / out.
+ * TEXTURE COORDINATES of a file (host side, float64; mesh.atlas_uv): corner k of triangle t sits at the atlas texel (X, Y) of its local corner (0,0), (L,0), (0,L);
+ *   u = (X + .5) / Wa, v = 1 - (Y + .5) / Ha, image row 0 = Y = 0.
+ * NOT promised: seams under mip-mapping beyond one ring, view-dependent colour, any packing of patches by triangle size (a sliver gets the patch of a large triangle). */
+#define TVR_MESH_ATLAS_MIN_P 5
+#define TVR_MESH_ATLAS_MAX_P 64
+int tvr_mesh_atlas_points(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, int32_t P, int32_t C, int64_t texel0, int64_t n,
+                          float *pos_out, size_t pos_bytes, int32_t *tri_out, size_t tri_bytes, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_texture_sample(const int32_t *tri, const float *bary, int64_t n_pix, const void *atlas, int32_t fmt, int32_t Ha, int32_t Wa, int32_t P, int32_t C,
+                            int64_t n_triangles, float *out, size_t out_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

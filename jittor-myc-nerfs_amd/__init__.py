@@ -10,5 +10,6 @@ from .render import OctreeRender_trilinear_fast, N_to_reso, cal_n_samples, rende
 from .evaluation import BlenderRays, evaluation, evaluation_mesh, evaluation_path, mesh_agreement, normal_map_to_rgb8, rgb_ssim, rgb_ssim_torch  # noqa: F401
 from .losses import TVLoss  # noqa: F401
 from .mesh import marching_cubes, mesh_adjacency, mesh_view_to_rgb8, read_ply, read_ply_attributes, render_mesh, render_mesh_frame, simplify_clustering, smooth_taubin, write_ply  # noqa: F401
+from .mesh import atlas_points, atlas_shape, atlas_uv, read_obj, sample_texture, write_obj  # noqa: F401
 from .training import GradBucket, make_graphed_step, shard_batch  # noqa: F401
 from . import mesh, ngp, rays, synthetic  # noqa: F401

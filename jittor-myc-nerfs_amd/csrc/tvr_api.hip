@@ -2238,3 +2238,60 @@ int tvr_mesh_raster(const float *verts, int64_t n_vertices, const int32_t *faces
                                (int *)counts_dev, fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- per-triangle texture atlas (tvr_mesh_texture.hip) ---------------------------------------------------------------------------------------------------------------------
+// the atlas of F triangles at patch side P with C squares per row: *Ha, *Wa; every count in range and fewer than 2^31 texels, else an error that names the argument
+static int atlas_layout(const char *fn, int64_t n_triangles, int32_t P, int32_t C, int64_t *Ha, int64_t *Wa)
+{
+    if (n_triangles < 0) return fail(TVR_ERR_INVALID, "%s: n_triangles = %lld is negative", fn, (long long)n_triangles);
+    if (P < TVR_MESH_ATLAS_MIN_P || P > TVR_MESH_ATLAS_MAX_P)
+        return fail(TVR_ERR_INVALID, "%s: P = %d outside %d .. %d texels per patch side", fn, (int)P, TVR_MESH_ATLAS_MIN_P, TVR_MESH_ATLAS_MAX_P);
+    if (C < 1) return fail(TVR_ERR_INVALID, "%s: C = %d: an atlas row holds at least one square", fn, (int)C);
+    if (n_triangles > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_triangles = %lld: triangle indices are int32", fn, (long long)n_triangles);
+    const int64_t S = (n_triangles + 1) / 2, rows = S > 0 ? (S + C - 1) / C : 1;
+    *Wa = (int64_t)C * P;
+    *Ha = rows * P;
+    if (*Wa > INT32_MAX || *Ha > INT32_MAX || *Ha * *Wa > INT32_MAX)
+        return fail(TVR_ERR_UNSUPPORTED, "%s: an atlas of Ha = %lld x Wa = %lld texels (n_triangles = %lld, P = %d, C = %d): texel indices are int32 and Ha * Wa must stay "
+                    "below 2^31", fn, (long long)*Ha, (long long)*Wa, (long long)n_triangles, (int)P, (int)C);
+    return TVR_OK;
+}
+
+int tvr_mesh_atlas_points(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, int32_t P, int32_t C, int64_t texel0, int64_t n,
+                          float *pos_out, size_t pos_bytes, int32_t *tri_out, size_t tri_bytes, uint32_t *fault_flag_dev, void *stream)
+{
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_vertices < 0) return fail(TVR_ERR_INVALID, "%s: n_vertices = %lld is negative", __func__, (long long)n_vertices);
+    int64_t Ha, Wa;
+    int rc = atlas_layout(__func__, n_triangles, P, C, &Ha, &Wa);
+    if (rc != TVR_OK) return rc;
+    if (n_vertices > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices = %lld: vertex indices are int32", __func__, (long long)n_vertices);
+    if (n_triangles > 0 && (!faces || !verts)) return fail(TVR_ERR_INVALID, "%s: faces / verts is NULL with %lld triangles", __func__, (long long)n_triangles);
+    if (texel0 < 0 || n < 0 || texel0 > Ha * Wa || n > Ha * Wa - texel0)
+        return fail(TVR_ERR_INVALID, "%s: texel0 = %lld, n = %lld: the range leaves the atlas of %lld x %lld = %lld texels", __func__, (long long)texel0, (long long)n,
+                    (long long)Ha, (long long)Wa, (long long)(Ha * Wa));
+    if (n > 0 && (!pos_out || !tri_out)) return fail(TVR_ERR_INVALID, "%s: pos_out / tri_out is NULL with n = %lld texels", __func__, (long long)n);
+    NEED("pos_out [n,3]", pos_bytes, n, 3);
+    NEED("tri_out [n]", tri_bytes, n, 1);
+    HIP_TRY(launch_mesh_atlas_points(verts, n_vertices, faces, n_triangles, P, C, texel0, n, pos_out, tri_out, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_texture_sample(const int32_t *tri, const float *bary, int64_t n_pix, const void *atlas, int32_t fmt, int32_t Ha, int32_t Wa, int32_t P, int32_t C,
+                            int64_t n_triangles, float *out, size_t out_bytes, void *stream)
+{
+    if (n_pix < 0) return fail(TVR_ERR_INVALID, "%s: n_pix = %lld is negative", __func__, (long long)n_pix);
+    if (fmt != 0 && fmt != 1) return fail(TVR_ERR_INVALID, "%s: fmt = %d is neither 0 (uint8 RGB) nor 1 (fp32 RGB)", __func__, (int)fmt);
+    int64_t ha, wa;
+    int rc = atlas_layout(__func__, n_triangles, P, C, &ha, &wa);
+    if (rc != TVR_OK) return rc;
+    if (Ha != ha || Wa != wa)
+        return fail(TVR_ERR_INVALID, "%s: Ha = %d, Wa = %d, but %lld triangles at P = %d, C = %d make an atlas of %lld x %lld", __func__, (int)Ha, (int)Wa,
+                    (long long)n_triangles, (int)P, (int)C, (long long)ha, (long long)wa);
+    if (n_pix > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_pix = %lld: pixel indices are int32", __func__, (long long)n_pix);
+    if (!atlas) return fail(TVR_ERR_INVALID, "%s: atlas is NULL", __func__);
+    if (n_pix > 0 && (!tri || !bary || !out)) return fail(TVR_ERR_INVALID, "%s: tri / bary / out is NULL with n_pix = %lld", __func__, (long long)n_pix);
+    NEED("out [n_pix,3]", out_bytes, n_pix, 3);
+    HIP_TRY(launch_mesh_texture_sample(tri, bary, n_pix, atlas, fmt, ha * wa, P, C, n_triangles, out, (hipStream_t)stream));
+    return TVR_OK;
+}

@@ -277,3 +277,10 @@ hipError_t launch_mesh_project(const SceneDev &sc, const CpDev *cp, const float 
 size_t mesh_raster_scratch_bytes(long long n_triangles, long long n_pixels);
 hipError_t launch_mesh_raster(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const tvr_mesh_camera &cam, const float *attr, int n_attr,
                               float *depth, int *tri, float *bary, float *attr_out, void *scratch, int *counts, unsigned *fault, hipStream_t stream);
+
+// tvr_mesh_texture.hip: the per-triangle texture atlas (include/tvr.h tvr_mesh_atlas_points / tvr_mesh_texture_sample).  No scratch.  The host has checked the counts,
+// the layout (Wa = C * P, fewer than 2^31 texels) and the range; n <= 0 / n_pix <= 0 launch nothing.  fmt 0: atlas uint8 [n_texels][3], 1: fp32.
+hipError_t launch_mesh_atlas_points(const float *verts, long long n_vertices, const int *faces, long long n_triangles, int P, int C, long long texel0, long long n,
+                                    float *pos, int *tri, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_texture_sample(const int *tri, const float *bary, long long n_pix, const void *atlas, int fmt, long long n_texels, int P, int C,
+                                      long long n_triangles, float *out, hipStream_t stream);

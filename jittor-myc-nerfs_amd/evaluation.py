@@ -331,8 +331,23 @@ def mesh_agreement(mesh_depth, mesh_hit, field_depth, field_acc, voxel) -> dict:
             "depth_pixels": int(err.size)}
 
 
+def mesh_color_psnr(mesh_rgb8, mesh_hit, field_rgb, field_acc):
+    """PSNR in dB of a mesh view's colour (uint8 [H,W,3], mesh.mesh_view_to_rgb8) against the field's rendered colour (float [H*W,3] in 0 .. 1) over the pixels with
+    mesh_hit and field_acc > 0.99: -10 log10(mean squared difference of the colours in 0 .. 1).  None when there is no such pixel, +inf for equal colours.
+    Pure; tensors on either device or arrays."""
+    def host(a):
+        return np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+    m = host(mesh_hit).astype(bool).reshape(-1) & (host(field_acc).astype(np.float64).reshape(-1) > 0.99)
+    if not m.any():
+        return None
+    d = host(mesh_rgb8).astype(np.float64).reshape(-1, 3)[m] / 255.0 - np.clip(host(field_rgb).astype(np.float64).reshape(-1, 3)[m], 0.0, 1.0)
+    mse = float(np.mean(d * d))
+    return float("inf") if mse == 0 else float(-10.0 * np.log10(mse))
+
+
 @torch.no_grad()
-def evaluation_mesh(test_dataset, tensorf, verts, faces, savePath, normals=None, colors=None, N_vis=-1, white_bg=True, device="cuda", voxel=None, N_samples=-1):
+def evaluation_mesh(test_dataset, tensorf, verts, faces, savePath, normals=None, colors=None, N_vis=-1, white_bg=True, device="cuda", voxel=None, N_samples=-1,
+                    texture=None, texture_layout=None, color_psnr=False):
     """Views of a mesh from the test poses, beside the rendered views: writes `{savePath}/mesh/{idx:03d}.png` per pose (H, W, focal and poses are the ones the dataset's
     rays were made from, so pixel p of the picture is ray p of the frame) and returns the per-frame mesh_agreement against tensorf.render_normals' depth and acc.
 
@@ -340,17 +355,27 @@ def evaluation_mesh(test_dataset, tensorf, verts, faces, savePath, normals=None,
     view; with neither a flat-shaded view from the face normals (mesh.mesh_view_to_rgb8).  voxel: the export voxel in world units (default: extent / (gridSize - 1)
     of the field, the voxel of export_mesh(spacing="samples") at the field's own grid).  The agreement means something for meshes exported with spacing="samples":
     the reference's convention shrinks the mesh by (N - 1) / N about aabb[0], and a PLY does not record which was used.
+    texture [Ha,Wa,3] uint8 with texture_layout = (P, C): the per-triangle atlas of TensorBase.bake_texture (a textured OBJ read by mesh.read_obj; the layout from
+    mesh.atlas_layout_from_uv) -> the colour view through mesh.sample_texture; it takes precedence over colors and normals.
+    color_psnr=True adds "color_psnr" to every frame: mesh_color_psnr of the colour view (texture or vertex colours) against the field's rendered colour
+    (tensorf.render_rays on the frame's rays) over the pixels with a hit and acc > 0.99; None when the view has no colours.  Off by default: the frames are then
+    what they were.
     NerfPlusPlus has no normal pass: the pictures are written and None is returned.  Nothing here is called by evaluation() / evaluation_path()."""
     from . import mesh as M
     dev = torch.device(device)
     v = torch.as_tensor(np.asarray(verts) if not torch.is_tensor(verts) else verts).to(device=dev, dtype=torch.float32)
     f = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces).to(device=dev, dtype=torch.int32)
-    attr, mode = None, "normal"
-    if colors is not None:
+    attr, mode, atlas = None, "normal", None
+    if texture is not None:
+        if texture_layout is None:
+            raise ValueError("evaluation_mesh with a texture takes texture_layout = (P, C) (mesh.atlas_layout_from_uv)")
+        atlas, mode = torch.as_tensor(np.asarray(texture) if not torch.is_tensor(texture) else texture).to(device=dev, dtype=torch.uint8).contiguous(), "color"
+        tex_P, tex_C = (int(x) for x in texture_layout)
+    elif colors is not None:
         attr, mode = torch.as_tensor(np.asarray(colors) if not torch.is_tensor(colors) else colors).to(device=dev, dtype=torch.float32), "color"
     elif normals is not None:
         attr = torch.as_tensor(np.asarray(normals) if not torch.is_tensor(normals) else normals).to(device=dev, dtype=torch.float32)
-    fn = M.face_normals(v, f) if attr is None else None
+    fn = M.face_normals(v, f) if attr is None and atlas is None else None
     from .variants import NerfPlusPlus
     has_normal_pass = not isinstance(tensorf, NerfPlusPlus)               # its render_normals refuses: the samples lie at explicit depths
     if voxel is None:
@@ -363,13 +388,18 @@ def evaluation_mesh(test_dataset, tensorf, verts, faces, savePath, normals=None,
     writer = _ImageWriter()
     out = []
     for idx, k in enumerate(range(0, n, interval)):
-        depth, tri, _, a = M.render_mesh(v, f, test_dataset.poses[k], H, W, test_dataset.focal, attributes=attr)
+        depth, tri, bary, a = M.render_mesh(v, f, test_dataset.poses[k], H, W, test_dataset.focal, attributes=attr)
+        if atlas is not None:
+            a = M.sample_texture(tri, bary, atlas, tex_P, tex_C, f.shape[0])
         img = M.mesh_view_to_rgb8(tri, a, mode, white_bg=white_bg, face_normal=fn)
         writer.write(f"{savePath}/mesh/{idx:03d}.png", img.cpu().numpy())
         if has_normal_pass:
             rays = test_dataset.all_rays[k].view(-1, 6).to(dev)
             _, acc, fdepth = tensorf.render_normals(rays, N_samples=N_samples)
             out.append(mesh_agreement(depth, tri >= 0, fdepth, acc, voxel))
+            if color_psnr:
+                rgb = tensorf.render_rays(rays, white_bg=white_bg, N_samples=N_samples)[0] if mode == "color" else None
+                out[-1]["color_psnr"] = None if rgb is None else mesh_color_psnr(img, tri >= 0, rgb, acc)
     writer.close()
     return out if has_normal_pass else None
 
@@ -380,4 +410,7 @@ def mesh_agreement_summary(frames) -> dict:
     for key in ("iou", "depth_median_vox", "depth_p95_vox", "depth_pixels"):
         vals = [fr[key] for fr in frames if np.isfinite(fr[key])]
         mean[key] = float(np.mean(vals)) if vals else float("nan")
+    if any("color_psnr" in fr for fr in frames):                      # evaluation_mesh(color_psnr=True): None (null in the file) where the view has no colours
+        vals = [fr["color_psnr"] for fr in frames if fr.get("color_psnr") is not None and np.isfinite(fr["color_psnr"])]
+        mean["color_psnr"] = float(np.mean(vals)) if vals else None
     return {"frames": list(frames), "mean": mean}

@@ -949,6 +949,38 @@ class TensorBase(torch.nn.Module):
         rgb = self.renderModule(None, -n, self.compute_appfeature(self.normalize_coord(v)))
         return torch.round(255.0 * rgb.clamp(0, 1)).to(torch.uint8)
 
+    @torch.no_grad()
+    def bake_texture(self, verts, faces, P, C=None, chunk=1 << 20, half_width=None, stats=None):
+        """The per-triangle texture atlas of a mesh (mesh.atlas_shape(F, P, C); include/tvr.h tvr_mesh_atlas_points) baked from the field: uint8 [Ha, Wa, 3] on the device.
+        verts [V,3] are world positions where the field was sampled (what mesh_vertex_attributes takes), faces [F,3].  Every owned texel holds the vertex colour's
+        definition at the texel's point: the field's shading viewed head-on, round(255 * clamp(renderModule(None, -normal, compute_appfeature(.)), 0, 1)) with
+        normal = surface_normals(point, half_width); the point is clamped into the aabb first (only gutter texels, extrapolated past the hypotenuse, can leave it).
+        Unowned texels are 0.  The texels are taken `chunk` at a time (mesh.atlas_points on a range), so memory is bounded by the chunk, not the atlas; the result
+        does not depend on the chunk.  The field evaluation composes the existing calls; `stats` (a dict) receives atlas_texels / atlas_owned_texels / atlas_chunks."""
+        from . import mesh
+        v = self._device_points(verts, "bake_texture")
+        f = mesh._faces_on_device(faces, "bake_texture")
+        Ha, Wa, C = mesh.atlas_shape(f.shape[0], P, C)
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk = {chunk}: texels per step, at least 1")
+        self._vertex_colors(v[:0], v[:0])                         # a model without vertex colours (REFTensoRF) refuses here, before anything is baked
+        out = torch.zeros((Ha * Wa, 3), dtype=torch.uint8, device=self.device)
+        aabb = self.aabb.to(device=self.device, dtype=torch.float32)
+        owned = chunks = 0
+        for t0 in range(0, Ha * Wa, chunk):
+            pos, tri = mesh.atlas_points(v, f, P, C, t0, min(chunk, Ha * Wa - t0))
+            idx = (tri >= 0).nonzero().view(-1)
+            chunks += 1
+            if idx.numel() == 0:
+                continue
+            p = torch.maximum(torch.minimum(pos[idx], aabb[1]), aabb[0])
+            out[idx + t0] = self._vertex_colors(p, self.surface_normals(p, half_width))
+            owned += int(idx.numel())
+        if stats is not None:
+            stats.update(atlas_texels=Ha * Wa, atlas_owned_texels=owned, atlas_chunks=chunks)
+        return out.view(Ha, Wa, 3)
+
     def _mlp_render(self, viewdirs, features):
         sc = self._ensure_scene(settle=False)
         self._settle_range_check()
@@ -1009,7 +1041,7 @@ class TensorBase(torch.nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False, min_component_faces=0, keep_largest=0,
-                    simplify=0.0, smooth=0, refine=0):
+                    simplify=0.0, smooth=0, refine=0, texture=0):
         """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
         (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
 
@@ -1039,7 +1071,11 @@ class TensorBase(torch.nn.Module):
         smoothing and BEFORE the attributes, on mesh_sample_positions(verts) — where the field was sampled; with spacing="reference" the result is mapped back by
         (N - 1) / N about aabb[0].  Faces are untouched; normals and colours are evaluated at the projected positions.  The alpha mask is not consulted: where the
         mask, not the level, bounds the surface, vertices move towards the level set, at most one voxel.  An integer in 0 .. 64, else ValueError;
-        self.mesh_export_stats gains the refine_* entries of project_to_isosurface."""
+        self.mesh_export_stats gains the refine_* entries of project_to_isosurface.
+        texture: P, the patch side in texels (5 .. 64) of a per-triangle texture atlas (bake_texture; mesh.atlas_shape's default columns).  0 = off, the default:
+        nothing new is called or written.  It runs AFTER every other step, on mesh_sample_positions(verts) like the attributes, and writes
+        `<path minus .ply>.obj / .mtl / .png` BESIDE the PLY (mesh.write_obj with the written vertices, and the normals when `normals` is on); the PLY itself is what
+        it is without the option.  self.mesh_export_stats gains atlas_patch / atlas_columns / atlas_height / atlas_width and bake_texture's entries."""
         from . import mesh
         if min_component_faces < 0 or keep_largest < 0:
             raise ValueError(f"min_component_faces = {min_component_faces} / keep_largest = {keep_largest}: negative values mean nothing (0 switches an option off)")
@@ -1048,6 +1084,10 @@ class TensorBase(torch.nn.Module):
             raise ValueError(f"smooth = {smooth!r}: Taubin iterations, an integer in 0 .. {mesh.SMOOTH_MAX_ITERATIONS} (0 = off)")
         if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= self.PROJECT_MAX_ITERATIONS:
             raise ValueError(f"refine = {refine!r}: Newton iterations onto the iso-surface, an integer in 0 .. {self.PROJECT_MAX_ITERATIONS} (0 = off)")
+        if isinstance(texture, bool) or not isinstance(texture, (int, np.integer)) or not (int(texture) == 0 or mesh.ATLAS_MIN_P <= int(texture) <= mesh.ATLAS_MAX_P):
+            raise ValueError(f"texture = {texture!r}: the atlas' patch side in texels, 0 (off) or an integer in {mesh.ATLAS_MIN_P} .. {mesh.ATLAS_MAX_P}")
+        if texture and not str(path).endswith(".ply"):
+            raise ValueError(f"texture = {texture}: the atlas goes to <path minus .ply>.obj / .mtl / .png, and {str(path)!r} does not end in .ply")
         alpha, _ = self.getDenseAlpha(gridSize)
         aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
         n = torch.tensor([float(s) for s in alpha.shape], dtype=torch.float32, device=alpha.device)
@@ -1071,13 +1111,20 @@ class TensorBase(torch.nn.Module):
             at, _ = self.project_to_isosurface(self.mesh_sample_positions(verts, alpha.shape, spacing), level, iterations=int(refine),
                                                max_move=((aabb[1] - aabb[0]) / (n - 1)).tolist(), stats=self.mesh_export_stats)
             verts = at if spacing == "samples" else aabb[0] + (at - aabb[0]) * ((n - 1) / n)
-        if not (normals or colors):
+        if not (normals or colors or texture):
             mesh.write_ply(path, verts, faces)
             return verts, faces
         if at is None:
             at = self.mesh_sample_positions(verts, alpha.shape, spacing)
         attrs = self.mesh_vertex_attributes(at, normals=normals, colors=colors)
         mesh.write_ply(path, verts, faces, normals=attrs.get("normals"), colors=attrs.get("colors"))
+        if texture:
+            base = str(path)[:-4]
+            Ha, Wa, cols = mesh.atlas_shape(faces.shape[0], int(texture))
+            atlas = self.bake_texture(at, faces, int(texture), cols, stats=self.mesh_export_stats)
+            mesh.write_texture_png(base + ".png", atlas)
+            mesh.write_obj(base + ".obj", verts, faces, mesh.atlas_uv(faces.shape[0], int(texture), cols), base + ".png", normals=attrs.get("normals"))
+            self.mesh_export_stats.update(atlas_patch=int(texture), atlas_columns=cols, atlas_height=Ha, atlas_width=Wa)
         return verts, faces
 
     @staticmethod

@@ -639,3 +639,185 @@ def mesh_view_to_rgb8(tri: torch.Tensor, attr, mode: str = "normal", white_bg: b
     m = hit.unsqueeze(-1)
     x = torch.where(m, x, torch.full_like(x, bg))
     return torch.round(255.0 * x.clamp(0.0, 1.0)).to(torch.uint8)
+
+
+# ---- per-triangle texture atlas (csrc/tvr_mesh_texture.hip, include/tvr.h tvr_mesh_atlas_points / tvr_mesh_texture_sample) -------------------------------
+ATLAS_MIN_P, ATLAS_MAX_P = 5, 64        # include/tvr.h TVR_MESH_ATLAS_MIN_P / TVR_MESH_ATLAS_MAX_P: the patch side in texels
+
+
+def atlas_shape(F: int, P: int, C: int = None):
+    """(Ha, Wa, C) of the atlas of F triangles at patch side P with C squares per row (default: ceil(sqrt(S)), S = ceil(F / 2) squares, so the atlas is about
+    square): Wa = C * P, Ha = max(ceil(S / C), 1) * P.  P outside 5 .. 64, C < 1 or F < 0 is a ValueError."""
+    import math
+    F, P = int(F), int(P)
+    if F < 0:
+        raise ValueError(f"F = {F}: a triangle count")
+    if not ATLAS_MIN_P <= P <= ATLAS_MAX_P:
+        raise ValueError(f"P = {P}: the patch side in texels, {ATLAS_MIN_P} .. {ATLAS_MAX_P}")
+    S = (F + 1) // 2
+    C = (math.isqrt(S - 1) + 1 if S > 0 else 1) if C is None else int(C)
+    if C < 1:
+        raise ValueError(f"C = {C}: an atlas row holds at least one square")
+    return max(-(-S // C), 1) * P, C * P, C
+
+
+def atlas_points(verts: torch.Tensor, faces: torch.Tensor, P: int, C: int, texel0: int, n: int):
+    """Where the texels texel0 .. texel0 + n - 1 of the atlas (linear index Y * Wa + X) lie on the mesh, on the device -> (points [n,3] float32, tri [n] int32): the
+    owning triangle and the point b0 v0 + b1 v1 + b2 v2 of the texel's local coordinates (include/tvr.h tvr_mesh_atlas_points); -1 and a zero point for a texel no
+    triangle owns.  A face index outside the vertices raises TvrError.  No CPU fallback."""
+    f = _faces_on_device(faces, "atlas_points")
+    if not torch.is_tensor(verts) or verts.device != f.device or verts.dim() != 2 or verts.shape[1] != 3:
+        raise L.TvrError(f"atlas_points takes verts [V, 3] on the faces' device ({f.device})")
+    v = verts.detach().to(torch.float32).contiguous()
+    V, F, dev, n = int(v.shape[0]), int(f.shape[0]), f.device, int(n)
+    pos = L.dev_empty((max(n, 0), 3), torch.float32, dev, what="atlas points")
+    tri = L.dev_empty((max(n, 0),), torch.int32, dev, what="atlas owners")
+    flag = L.dev_bytes(4, dev, zero=True, what="atlas fault flag").view(torch.int32)
+    L.check(L.lib().tvr_mesh_atlas_points(_ptr(v), V, _ptr(f), F, int(P), int(C), int(texel0), n, _ptr(pos), L.nbytes(pos), _ptr(tri), L.nbytes(tri), flag.data_ptr(),
+                                          _stream_ptr(dev)), "tvr_mesh_atlas_points")
+    if int(flag.item()) != 0:
+        raise L.TvrError(f"tvr_mesh_atlas_points raised its fault flag: a face index lies outside 0 .. {V - 1} (include/tvr.h)")
+    return pos, tri
+
+
+def atlas_uv(F: int, P: int, C: int = None) -> np.ndarray:
+    """[F,3,2] float64 texture coordinates of every triangle corner in the atlas of atlas_shape(F, P, C): corner k of triangle t sits at the atlas texel (X, Y) of its
+    local corner (0,0), (L,0), (0,L), L = P - 4; u = (X + .5) / Wa, v = 1 - (Y + .5) / Ha (image row 0 = Y = 0, the OBJ convention's top)."""
+    Ha, Wa, C = atlas_shape(F, P, C)
+    P, Lp = int(P), int(P) - 4
+    t = np.arange(int(F), dtype=np.int64)
+    s, h = t >> 1, t & 1
+    X0, Y0 = (s % C) * P, (s // C) * P
+    lx, ly = np.array([0, Lp, 0], dtype=np.int64), np.array([0, 0, Lp], dtype=np.int64)
+    a = np.where(h[:, None] == 0, lx[None], P - 1 - lx[None])
+    b = np.where(h[:, None] == 0, ly[None], P - 1 - ly[None])
+    X, Y = (X0[:, None] + a).astype(np.float64), (Y0[:, None] + b).astype(np.float64)
+    return np.stack(((X + 0.5) / Wa, 1.0 - (Y + 0.5) / Ha), -1)
+
+
+def atlas_layout_from_uv(uv: np.ndarray, Ha: int, Wa: int):
+    """(P, C) of an atlas written by write_obj, from its per-corner uv [F,3,2] and the picture's size: triangle 0's corners 0 and 1 lie L = P - 4 texels apart.
+    ValueError when the coordinates are not atlas_uv's for that layout (a file this package did not write)."""
+    uv = np.asarray(uv, dtype=np.float64).reshape(-1, 3, 2)
+    F = uv.shape[0]
+    if F == 0:
+        if Ha != Wa or not ATLAS_MIN_P <= Ha <= ATLAS_MAX_P:
+            raise ValueError(f"an atlas of {Ha} x {Wa} texels is not the one patch of a mesh without triangles")
+        return int(Ha), 1
+    P = int(round((uv[0, 1, 0] - uv[0, 0, 0]) * Wa)) + 4
+    if not ATLAS_MIN_P <= P <= ATLAS_MAX_P or Wa % P:
+        raise ValueError(f"texture coordinates that put a patch side of {P} texels into an atlas {Wa} wide: not an atlas of this package")
+    C = Wa // P
+    if atlas_shape(F, P, C)[:2] != (int(Ha), int(Wa)) or not np.allclose(uv, atlas_uv(F, P, C), rtol=0, atol=1e-7):
+        raise ValueError(f"the texture coordinates are not those of the per-triangle atlas of {F} triangles at P = {P}, C = {C} ({Ha} x {Wa} texels)")
+    return P, C
+
+
+def sample_texture(tri: torch.Tensor, bary: torch.Tensor, atlas: torch.Tensor, P: int, C: int, F: int) -> torch.Tensor:
+    """The atlas' colour at every hit of a render_mesh result, on the device -> [..., 3] float32 in the atlas' own units (0 .. 255 for uint8), zeros where tri < 0.
+    tri [...] int32, bary [..., 3] float32, atlas [Ha, Wa, 3] uint8 or float32 of atlas_shape(F, P, C): bilinear between the four texels around (b1 * L, b2 * L) in the
+    triangle's own patch (include/tvr.h tvr_mesh_texture_sample).  No CPU fallback."""
+    if not (torch.is_tensor(tri) and torch.is_tensor(bary) and torch.is_tensor(atlas)) or tri.device.type != "cuda" or bary.device != tri.device or \
+            atlas.device != tri.device:
+        raise L.TvrError("sample_texture runs on an MI355X (HIP) device only: tri, bary and atlas are tensors on one such device. There is no CPU fallback.")
+    if bary.shape != tuple(tri.shape) + (3,):
+        raise L.TvrError(f"sample_texture takes tri [...] and bary [..., 3]; got {tuple(tri.shape)} and {tuple(bary.shape)}")
+    if atlas.dim() != 3 or atlas.shape[2] != 3 or atlas.dtype not in (torch.uint8, torch.float32):
+        raise L.TvrError(f"sample_texture takes an atlas [Ha, Wa, 3] of uint8 or float32; got {tuple(atlas.shape)} {atlas.dtype}")
+    t, b, a = tri.detach().to(torch.int32).contiguous(), bary.detach().to(torch.float32).contiguous(), atlas.detach().contiguous()
+    n, dev = int(t.numel()), t.device
+    out = L.dev_empty(tuple(tri.shape) + (3,), torch.float32, dev, what="texture samples")
+    L.check(L.lib().tvr_mesh_texture_sample(_ptr(t), _ptr(b), n, a.data_ptr(), 0 if a.dtype == torch.uint8 else 1, int(a.shape[0]), int(a.shape[1]), int(P), int(C),
+                                            int(F), _ptr(out), L.nbytes(out), _stream_ptr(dev)), "tvr_mesh_texture_sample")
+    return out
+
+
+def write_texture_png(path, atlas) -> None:
+    """The atlas [Ha, Wa, 3] uint8 (tensor on any device, or array) as a PNG, row 0 = atlas row Y = 0."""
+    from PIL import Image
+    a = atlas.detach().cpu().numpy() if torch.is_tensor(atlas) else np.asarray(atlas)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"a texture is uint8 [Ha, Wa, 3]; got {a.dtype} {a.shape}")
+    Image.fromarray(np.ascontiguousarray(a)).save(path)
+
+
+def read_texture_png(path) -> np.ndarray:
+    """The picture write_texture_png wrote, uint8 [Ha, Wa, 3]."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert("RGB"), dtype=np.uint8)              # (a copy: the array PIL exposes is read-only)
+
+
+def write_obj(path, verts, faces, uv, texture_png, normals=None) -> None:
+    """Wavefront OBJ of a textured mesh: `path` (x.obj) and x.mtl beside it.  verts [V,3], faces [F,3], uv [F,3,2] (atlas_uv: one `vt` per triangle corner),
+    texture_png the picture's path (its base name goes into the .mtl's map_Kd: the three files travel together), normals [V,3] optional.  The .obj carries mtllib,
+    usemtl, v, vt, [vn] and f a/ta[/na] (1-based); v with 9 significant digits (fp32 round-trips), vt with 10 decimals."""
+    import os
+    path = str(path)
+    if not path.endswith(".obj"):
+        raise ValueError(f"{path!r}: write_obj writes x.obj and x.mtl")
+    v, f = _host(verts, np.float32), _host(faces, np.int64)
+    t = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+    if len(t) != 3 * len(f):
+        raise ValueError(f"uv holds {len(t)} corners for {len(f)} triangles")
+    nr = None if normals is None else _host(normals, np.float32)
+    if nr is not None and len(nr) != len(v):
+        raise ValueError(f"normals holds {len(nr)} rows for {len(v)} vertices")
+    mtl = path[:-4] + ".mtl"
+    with open(mtl, "w") as out:
+        out.write(f"newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {os.path.basename(str(texture_png))}\n")
+    lines = [f"mtllib {os.path.basename(mtl)}", "usemtl atlas"]
+    lines += ["v %.9g %.9g %.9g" % tuple(r) for r in v.tolist()]
+    lines += ["vt %.10f %.10f" % tuple(r) for r in t.tolist()]
+    if nr is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(r) for r in nr.tolist()]
+    c = 3 * np.arange(len(f), dtype=np.int64)[:, None] + np.arange(1, 4, dtype=np.int64)[None]
+    if nr is None:
+        lines += ["f %d/%d %d/%d %d/%d" % (a[0], b[0], a[1], b[1], a[2], b[2]) for a, b in zip((f + 1).tolist(), c.tolist())]
+    else:
+        lines += ["f %d/%d/%d %d/%d/%d %d/%d/%d" % (a[0], b[0], a[0], a[1], b[1], a[1], a[2], b[2], a[2]) for a, b in zip((f + 1).tolist(), c.tolist())]
+    with open(path, "w") as out:
+        out.write("\n".join(lines) + "\n")
+
+
+def read_obj(path):
+    """Reads back what write_obj writes, and no more: (verts [V,3] float32, faces [F,3] int32, uv [F,3,2] float64, texture path) — the picture named by the .mtl's
+    map_Kd, beside the .obj.  `vn` lines are skipped (a textured view needs none).  Anything else is a ValueError."""
+    import os
+    path = str(path)
+    v, vt, fv, ft, mtllib = [], [], [], [], None
+    with open(path) as src:
+        for ln, line in enumerate(src, 1):
+            tok = line.split()
+            if not tok or tok[0] in ("vn", "usemtl"):
+                continue
+            try:
+                if tok[0] == "v" and len(tok) == 4:
+                    v.append([float(x) for x in tok[1:]])
+                elif tok[0] == "vt" and len(tok) == 3:
+                    vt.append([float(x) for x in tok[1:]])
+                elif tok[0] == "f" and len(tok) == 4:
+                    parts = [x.split("/") for x in tok[1:]]
+                    fv.append([int(p[0]) - 1 for p in parts])
+                    ft.append([int(p[1]) - 1 for p in parts])
+                elif tok[0] == "mtllib" and len(tok) == 2:
+                    mtllib = tok[1]
+                else:
+                    raise ValueError
+            except (ValueError, IndexError):
+                raise ValueError(f"{path}:{ln}: only what write_obj writes is read (mtllib, usemtl, v, vt, vn, f a/ta[/na] of triangles)") from None
+    if mtllib is None:
+        raise ValueError(f"{path}: no mtllib line: not a textured OBJ of write_obj")
+    verts, uvs = np.asarray(v, dtype=np.float32).reshape(-1, 3), np.asarray(vt, dtype=np.float64).reshape(-1, 2)
+    faces, fts = np.asarray(fv, dtype=np.int64).reshape(-1, 3), np.asarray(ft, dtype=np.int64).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() >= len(verts) or fts.min() < 0 or fts.max() >= len(uvs)):
+        raise ValueError(f"{path}: a face names a vertex or a texture coordinate the file does not hold")
+    texture = None
+    with open(os.path.join(os.path.dirname(path), mtllib)) as src:
+        for line in src:
+            tok = line.split()
+            if tok[:1] == ["map_Kd"] and len(tok) == 2:
+                texture = os.path.join(os.path.dirname(path), tok[1])
+    if texture is None:
+        raise ValueError(f"{path}: {mtllib} names no map_Kd picture")
+    return verts, faces.astype(np.int32), uvs[fts.reshape(-1)].reshape(-1, 3, 2), texture

@@ -9,7 +9,7 @@ What differs from the reference, on purpose:
   * no TensorBoard writer, no `ndc_ray` datasets (the reference ships only the Blender loader); `set_nerfplusplus` is called for NerfPlusPlus only
     (train.py:172 calls it unconditionally and fails for the others);
   * `--export_mesh 1` (train.py:41-59) extracts the surface with the HIP marching cubes (mesh.py) instead of skimage and writes the PLY without plyfile; the
-    level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_min_faces N` / `--mesh_keep_largest K` drop connected components (floaters), `--mesh_simplify S` merges the vertices of every cell of S voxels (vertex clustering), `--mesh_smooth N` runs N Taubin smoothing iterations, `--mesh_refine N` projects the vertices back onto the iso-surface with N Newton iterations, `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
+    level and the grid are options (`mesh_level`, `mesh_grid`), `--mesh_min_faces N` / `--mesh_keep_largest K` drop connected components (floaters), `--mesh_simplify S` merges the vertices of every cell of S voxels (vertex clustering), `--mesh_smooth N` runs N Taubin smoothing iterations, `--mesh_refine N` projects the vertices back onto the iso-surface with N Newton iterations, `--mesh_texture P` bakes a per-triangle texture atlas of P texels per patch side and writes a textured OBJ beside the PLY, `--mesh_normals 1` / `--mesh_colors 1` add per-vertex normals / colours (the reference writes bare
     geometry), `--render_mesh 1` (with `--render_only 1 --render_test 1`) draws the exported mesh from every test pose beside the rendered views and reports how well the two agree, and the command ends after the export instead of falling through into a training run;
   * progress is a plain print every `progress_refresh_rate` iterations.
 Host-side plumbing only: every pixel comes from the HIP kernels through `OctreeRender_trilinear_fast`.
@@ -94,6 +94,9 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--mesh_smooth", type=int, default=0)
     # put the vertices back on the iso-surface (TensorBase.project_to_isosurface): Newton iterations, after the smoothing and before the attributes; 0 = off
     p.add_argument("--mesh_refine", type=int, default=0)
+    # texture the mesh (TensorBase.bake_texture): the patch side P in texels (5 .. 64) of a per-triangle atlas baked from the field after every other step; writes
+    # <ckpt minus .th>.obj / .mtl / .png beside the PLY; 0 = off
+    p.add_argument("--mesh_texture", type=int, default=0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     # (not a reference option) views of an exported mesh beside the rendered test views (mesh.render_mesh): with --render_only 1 --render_test 1, read --mesh_file
@@ -102,7 +105,7 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
                    help="1: also draw the exported mesh from every test pose and report how well it agrees with the rendered depth and opacity (silhouette IoU, depth "
                         "error in export voxels).  The agreement is meaningful for meshes exported with spacing='samples': the reference's voxel-size convention shrinks "
                         "the mesh by (N - 1) / N about aabb[0], and the PLY does not record which was used.")
-    p.add_argument("--mesh_file", type=str, default=None, help="the PLY --render_mesh 1 reads (default: <ckpt minus .th>.ply)")
+    p.add_argument("--mesh_file", type=str, default=None, help="the PLY, or the textured OBJ of --mesh_texture, that --render_mesh 1 reads (default: <ckpt minus .th>.ply)")
     for name, typ in (("bbox", float), ("n_lamb_sigma", int), ("n_lamb_sh", int), ("upsamp_list", int), ("update_AlphaMask_list", int), ("mesh_grid", int)):
         p.add_argument("--" + name, type=typ, action="append")
     argv = sys.argv[1:] if cmd is None else list(cmd)
@@ -203,25 +206,37 @@ def mesh_export_voxel(tensorf, mesh_grid=None):
 
 def render_mesh_views(args, test_dataset, tensorf, savePath, device="cuda"):
     """--render_mesh 1: the PLY (--mesh_file, default <ckpt minus .th>.ply) drawn from every test pose into {savePath}/mesh/, and {savePath}/mesh_agreement.json with
-    evaluation.mesh_agreement per frame and its mean (no agreement for NerfPlusPlus, which has no normal pass: the file then says so)."""
+    evaluation.mesh_agreement per frame and its mean (no agreement for NerfPlusPlus, which has no normal pass: the file then says so).  A --mesh_file that ends in
+    .obj is the textured mesh of --mesh_texture: it is read with its PNG (mesh.read_obj) and drawn through mesh.sample_texture.  Every frame and the mean carry
+    color_psnr, the PSNR of the mesh view's colour against the field's rendered colour over the pixels with a hit and acc > 0.99 — for a textured OBJ and for a PLY with
+    vertex colours alike, so the two can be compared; null without colours or for NerfPlusPlus."""
     import json
-    from .mesh import read_ply_attributes
+    from .mesh import atlas_layout_from_uv, read_obj, read_ply_attributes, read_texture_png
     path = getattr(args, "mesh_file", None) or f"{args.ckpt[:-3]}.ply"
     if not os.path.exists(path):
         raise FileNotFoundError(f"--render_mesh 1 needs a mesh: {path!r} does not exist (write it with --export_mesh 1, or name one with --mesh_file)")
-    verts, faces, attrs = read_ply_attributes(path)
+    kw = {}
+    if path.endswith(".obj"):
+        verts, faces, uv, png = read_obj(path)
+        atlas = read_texture_png(png)
+        kw = dict(texture=atlas, texture_layout=atlas_layout_from_uv(uv, atlas.shape[0], atlas.shape[1]))
+    else:
+        verts, faces, attrs = read_ply_attributes(path)
+        kw = dict(normals=attrs.get("normals"), colors=attrs.get("colors"))
     voxel = mesh_export_voxel(tensorf, getattr(args, "mesh_grid", None))
-    frames = evaluation_mesh(test_dataset, tensorf, verts, faces, savePath.rstrip("/"), normals=attrs.get("normals"), colors=attrs.get("colors"), N_vis=-1,
-                             white_bg=test_dataset.white_bg, device=device, voxel=voxel)
+    frames = evaluation_mesh(test_dataset, tensorf, verts, faces, savePath.rstrip("/"), N_vis=-1, white_bg=test_dataset.white_bg, device=device, voxel=voxel,
+                             color_psnr=True, **kw)
     report = {"mesh_file": path, "voxel": [float(x) for x in voxel],
               "voxel_from": "--mesh_grid" if getattr(args, "mesh_grid", None) else "the field's gridSize (pass the export's --mesh_grid if it was made on another grid)",
               "note": "meaningful for meshes exported with spacing='samples' (the reference convention shrinks the mesh by (N - 1) / N about aabb[0])"}
-    report.update(mesh_agreement_summary(frames) if frames is not None else {"frames": None, "mean": None})
+    report.update(mesh_agreement_summary(frames) if frames is not None else {"frames": None, "mean": None, "color_psnr": None})
     with open(os.path.join(savePath, "mesh_agreement.json"), "w") as fjson:
         json.dump(report, fjson, indent=1)
     if frames:
         m = report["mean"]
         print(f"mesh views of {path}: silhouette IoU {m['iou']:.4f}, depth error median {m['depth_median_vox']:.3f} / 95 % {m['depth_p95_vox']:.3f} export voxels")
+        if m.get("color_psnr") is not None:
+            print(f"mesh views of {path}: colour against the rendered views, PSNR {m['color_psnr']:.2f} dB")
     return report
 
 
@@ -241,7 +256,8 @@ def export_mesh(args, device="cuda"):
     verts, faces = tensorf.export_mesh(path, level=getattr(args, "mesh_level", 0.0005), gridSize=grid, normals=bool(getattr(args, "mesh_normals", 0)),
                                        colors=bool(getattr(args, "mesh_colors", 0)), min_component_faces=int(getattr(args, "mesh_min_faces", 0)),
                                        keep_largest=int(getattr(args, "mesh_keep_largest", 0)), simplify=float(getattr(args, "mesh_simplify", 0.0)),
-                                       smooth=int(getattr(args, "mesh_smooth", 0)), refine=int(getattr(args, "mesh_refine", 0)))
+                                       smooth=int(getattr(args, "mesh_smooth", 0)), refine=int(getattr(args, "mesh_refine", 0)),
+                                       **({"texture": int(args.mesh_texture)} if getattr(args, "mesh_texture", 0) else {}))
     st = getattr(tensorf, "mesh_export_stats", None) or {}
     dropped = f"; dropped {st['components'] - st['components_kept']} of {st['components']} components, {st['triangles_dropped']} triangles" if "components" in st else ""
     merged = f"; simplified from {st['vertices_in']} vertices, {st['triangles_in']} triangles" if "triangles_in" in st else ""
@@ -249,7 +265,9 @@ def export_mesh(args, device="cuda"):
         if "smooth_iterations" in st else ""
     refined = f"; refined {st['refine_iterations']} iterations, {st['refine_converged']} vertices converged, median |residual| " \
         f"{st['refine_residual_median_before']:.3g} -> {st['refine_residual_median_after']:.3g}" if "refine_iterations" in st else ""
-    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles{dropped}{merged}{smoothed}{refined})")
+    textured = f"; textured at {st['atlas_patch']} texels per patch side, atlas {st['atlas_width']} x {st['atlas_height']} in {path[:-4]}.obj / .mtl / .png" \
+        if "atlas_patch" in st else ""
+    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles{dropped}{merged}{smoothed}{refined}{textured})")
     return path
 
 
