@@ -95,8 +95,10 @@ def positional_encoding(positions, freqs):
 
 
 # tensorf-myc/models/tensorBase.py:17-24
-def raw2alpha(sigma, dist, jittor_semantics=False):
+def raw2alpha(sigma, dist, jittor_semantics=False, sample_keep=None):
     alpha = 1.0 - torch.exp(-sigma * dist)
+    if sample_keep is not None:                  # the kernels' early exit, restated by the caller as a detached 0 / 1 mask (see execute)
+        alpha = alpha * sample_keep
     t = torch.cat([torch.ones(alpha.shape[0], 1), 1.0 - alpha + 1e-10], -1)
     if jittor_semantics:
         # Jittor 1.3.x is believed to evaluate jt.cumprod as exp(cumsum(log(x))) — not verifiable offline; this branch MODELS that
@@ -255,7 +257,10 @@ def shade_ref(sc: OracleScene, xyz_n_sel, views_sel, weight_sel):
 
 # tensorf-myc/models/tensorBase.py:476-536 (ndc_ray=False branch); with sc.ref set, tensorf-myc/models/REFTensoRF.py:174-256,
 # which differs only in the appearance branch (shade_ref)
-def execute(sc: OracleScene, rays_chunk, white_bg=True, N_samples=-1, jitter=None, dump=False, sampler=None):
+#
+# sample_keep (optional, [n, S] of 0 / 1, detached): multiplies alpha.  The reference has no early exit; the HIP march ends a ray once its transmittance falls
+# below eps_T, which is the reference's arithmetic with alpha = 0 on the samples behind the exit.  tests/march_backward_common.py computes that mask.
+def execute(sc: OracleScene, rays_chunk, white_bg=True, N_samples=-1, jitter=None, dump=False, sampler=None, sample_keep=None):
     rays_chunk = _t(rays_chunk)
     viewdirs = rays_chunk[:, 3:6]
     if sampler is not None:                         # a subclass's sample_ray override (NerfPlusPlus, nerfplusplus.py:239-269)
@@ -285,7 +290,8 @@ def execute(sc: OracleScene, rays_chunk, white_bg=True, N_samples=-1, jitter=Non
         sigma[ray_valid] = feature2density(sc, sf)
         sigma_feature_full[ray_valid] = sf
 
-    alpha, weight, bg_weight = raw2alpha(sigma, dists * sc.distance_scale, getattr(sc, "jittor_semantics", False))
+    alpha, weight, bg_weight = raw2alpha(sigma, dists * sc.distance_scale, getattr(sc, "jittor_semantics", False),
+                                         None if sample_keep is None else _t(sample_keep))
     app_mask = weight > sc.thres
     if app_mask.any():
         if sc.ref is not None:

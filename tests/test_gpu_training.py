@@ -28,7 +28,9 @@ def _oracle_with_grads(arrs, hyper):
 @pytest.mark.parametrize("static", [True, False])
 @pytest.mark.parametrize("white_bg,use_jitter", [(True, False), (False, True)])
 def test_gradients_match_oracle_autograd(tiny_dump, tiny_arrays, hyper_tiny, white_bg, use_jitter, static):
-    """static = True: the step as tvr_train_forward / tvr_train_backward (device-side counts, no host read); False: the eager chain of autograd Functions."""
+    """static = True: the step as tvr_train_forward / tvr_train_backward (device-side counts, no host read); False: the eager chain of autograd Functions.
+    This is the ONE-CHUNK, NO-EXIT case: 48 samples (march_backward_kernel's chunk loop runs once, nothing is carried), eps_T = 0 (no early exit), grid 16x20x24
+    (the LDS form of both scatter kernels).  More than one chunk, early exit, skipped chunks and the grids beyond the LDS limits: tests/test_gpu_march_backward.py."""
     from oracle import tensorf_oracle as TO
     rays_np = tiny_dump["rays"]
     S = TINY["N_samples"]
