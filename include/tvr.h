@@ -172,6 +172,31 @@ int tvr_scene_set_alpha(tvr_scene *scene, const float *alpha_volume_dev, const i
  * attach itself) and synchronise before capturing on another stream.  Capture again after attaching or detaching.  ADDITIVE exports: TVR_VERSION is unchanged. */
 size_t tvr_density_volume_bytes(const tvr_scene_desc *desc);
 int tvr_scene_set_density_volume(tvr_scene *scene, void *volume_dev, size_t volume_bytes, void *stream);
+/* BAKED APPEARANCE VOLUME (inference).  The same identity for the appearance features: inside a grid cell  plane_ic(u,v) * line_ic(w)  is trilinear, basis_mat is linear
+ * and has no bias, so the 27 features  F = basis_mat . cat_i(P_i * L_i)  are exactly the trilinear interpolation of the cell's eight corner values of F.  A TensorVMSplit
+ * scene with at most two encoding frequencies may carry them:
+ *   tvr_appearance_volume_bytes(desc)   (gx+1)(gy+1)(gz+1) records of 128 B, x fastest, the +1 layer padding as in the density volume (3.49 GB at 300^3); 0 for a bad
+ *                                    descriptor and for descriptors whose scenes take no volume (REFTensoRF, more than two encoding frequencies);
+ *   tvr_scene_set_appearance_volume(scene, buf, bytes, stream)   attaches `buf` (device memory, the CALLER's, kept by reference, 256-byte aligned); buf == NULL detaches.
+ *                                    TVR_ERR_INVALID for a NULL scene; TVR_ERR_SCRATCH for a buffer that is too small or misaligned; TVR_ERR_UNSUPPORTED for a CP scene, a
+ *                                    REFTensoRF scene (its four heads read the 144 products), a scene with more than two encoding frequencies, and any grid whose volume
+ *                                    reaches 4 GiB (the gather keeps 32-bit byte offsets; tvr_appearance_volume_bytes reports the size, the caller keeps the factored form).
+ *                                    If tvr_scene_update has run, the volume is baked here on `stream`; otherwise by the first render.
+ * RECORD: 32 fp32 = one cache line.  Slot 8 g + j (g = 0..3) holds feature 4 g + j for j < 4 and feature 16 + 4 g + (j - 4) for j >= 4 — the eight base values lane
+ * group g of the render kernel owns, as one 32-B segment; the slots of rows 27..31 (view direction, constant) hold 0.
+ * ONE EVALUATOR PER SCENE: while a volume is attached EVERY call that runs the render path's shade in the default arithmetic — tvr_render (with and without `dense`),
+ * tvr_render_z, tvr_scene_validate_arith's TVR_ARITH_F32 probes, the pieces of a call rendered piecewise — reads eight corner records per sample and interpolates 27
+ * channels (seven lerps each) instead of gathering 144 channels over six taps and contracting them with basis_mat; with none attached the factored kernel runs, unchanged.
+ * tvr_app_feature, tvr_mlp_render, the training forwards and the reduced arithmetics always evaluate the factored form.  The fp16-range check of the volume form covers
+ * what it splits (features, layer-2 inputs); it never sees the 144 products: attach a volume only to parameters whose range is PROVEN (the Python host's rule).
+ * BAKE: one kernel; every value the sum over k = 48 plane + channel, in that order, of fp64 FMAs  basis[row][k] * (plane_k * line_k)  (the inner product is exact in
+ * fp64), rounded once.  It reads what the factored kernel reads: the packed planes and lines, and basis_mat as the kernel's matrix operands hold it — the sum of the
+ * fp16 hi and lo parts, i.e. basis_mat truncated to 22 bits.
+ * STALENESS, STREAMS, CAPTURE: exactly as the density volume — tvr_scene_update / tvr_scene_touch mark it stale, the next call that launches the render shade in the
+ * default arithmetic bakes on ITS stream before any fork and records an event, calls on other streams wait on it; under capture the bake is captured in front and the
+ * volume stays marked stale.  ADDITIVE exports: TVR_VERSION is unchanged. */
+size_t tvr_appearance_volume_bytes(const tvr_scene_desc *desc);
+int tvr_scene_set_appearance_volume(tvr_scene *scene, void *volume_dev, size_t volume_bytes, void *stream);
 /* fp16-range check of the inference entry points (tvr_render(_z), tvr_app_feature(_ref), tvr_mlp_render(_ref)); ON when a scene is created.
  * ON: every value that enters a matrix product through the fp16 hi / lo split is held against fp16's largest finite value on the way (one v_max3 per two
  * values, ~1.5 % of the shade kernel's time); an appearance sample with an operand at or beyond 65 504 gets NaN as its colour / features, so its pixel is NaN,

@@ -105,6 +105,8 @@ SYMBOLS = {
                                       C.POINTER(C.c_float * 3), C.c_void_p, C.c_size_t, C.c_void_p]),
     "tvr_density_volume_bytes": (C.c_size_t, [C.POINTER(SceneDesc)]),
     "tvr_scene_set_density_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tvr_appearance_volume_bytes": (C.c_size_t, [C.POINTER(SceneDesc)]),
+    "tvr_scene_set_appearance_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tvr_scene_set_range_check": (C.c_int, [C.c_void_p, C.c_int32]),
     "tvr_scene_set_arith": (C.c_int, [C.c_void_p, C.c_int32]),
     "tvr_scene_set_render_pieces": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -138,6 +138,11 @@ struct tvr_scene {
     bool dvol_stale, dvol_recorded;
     hipStream_t dvol_stream;
     hipEvent_t ev_dvol;
+    // the baked appearance volume (tvr_scene_set_appearance_volume): the same rules for the render shade (ensure_fvol)
+    float4 *fvol;
+    bool fvol_stale, fvol_recorded;
+    hipStream_t fvol_stream;
+    hipEvent_t ev_fvol;
 };
 
 struct tvr_profile {
@@ -266,6 +271,11 @@ static int scene_create_impl(const tvr_scene_desc *desc, void *packed_dev, size_
     s->dvol_recorded = false;
     s->dvol_stream = nullptr;
     s->ev_dvol = nullptr;
+    s->fvol = nullptr;
+    s->fvol_stale = true;
+    s->fvol_recorded = false;
+    s->fvol_stream = nullptr;
+    s->ev_fvol = nullptr;
     SceneDev &v = s->dev;
     memset(&v, 0, sizeof(v));
     for (int k = 0; k < 3; ++k) {
@@ -382,6 +392,7 @@ int tvr_scene_update(tvr_scene *s, const tvr_scene_params *p, void *stream_)
     s->params_set = true;
     s->h16_stale = true;                  // (the first render in TVR_ARITH_F16 converts the fp16 copies: nothing is converted for steps that never read them)
     s->dvol_stale = true;                 // (likewise the density volume: the next render bakes it — a training step that never renders pays nothing)
+    s->fvol_stale = true;                 // (and the appearance volume)
     s->arith_valid = 0;                   // new parameters: a reduced arithmetic has to be measured again before it runs (tvr_scene_validate_arith)
     s->dev.arith = TVR_ARITH_F32;
     return TVR_OK;
@@ -428,6 +439,7 @@ int tvr_scene_touch(tvr_scene *s)
     if (!s) return fail(TVR_ERR_INVALID, "tvr_scene_touch: scene is NULL");
     s->h16_stale = true;         // the next TVR_ARITH_F16 render converts the fp32 images first
     s->dvol_stale = true;        // and the next render of a scene with a density volume bakes it first
+    s->fvol_stale = true;        // likewise the appearance volume
     s->arith_valid = 0;          // and a reduced arithmetic has to be validated again
     s->dev.arith = TVR_ARITH_F32;
     return TVR_OK;
@@ -483,6 +495,7 @@ int tvr_scene_destroy(tvr_scene *s)
         if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     }
     if (s && s->ev_dvol) (void)hipEventDestroy(s->ev_dvol);
+    if (s && s->ev_fvol) (void)hipEventDestroy(s->ev_fvol);
     delete s;
     return TVR_OK;
 }
@@ -543,6 +556,70 @@ int tvr_scene_set_density_volume(tvr_scene *s, void *buf, size_t bytes, void *st
     s->dvol_stale = true;
     s->dvol_recorded = false;
     if (s->params_set) return ensure_dvol(s, (hipStream_t)stream);       // parameters are packed: bake now, on the caller's stream
+    return TVR_OK;
+}
+
+}  // extern "C"
+
+// The appearance volume (tvr.h, BAKED APPEARANCE VOLUME): one TVR16_VOL_RECORD-byte record per value of the density volume.
+static size_t appearance_volume_need(const tvr_scene_desc &d) { return density_volume_values(d) * (size_t)TVR16_VOL_RECORD; }
+static bool takes_appearance_volume(const tvr_scene_desc &d) { return d.variant == 0 && d.view_pe <= 2 && d.fea_pe <= 2; }     // the scenes shade16_kernel<., false> renders
+
+// ensure_dvol for the render shade: called by render_impl on the caller's stream, in front of any fork, when the call's shade kernel reads the volume
+static int ensure_fvol(tvr_scene *s, hipStream_t stream)
+{
+    if (!s->fvol) return TVR_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    if (s->fvol_stale) {
+        HIP_TRY(launch_appearance_volume(s->dev, s->fvol, stream));
+        if (capturing) return TVR_OK;
+        if (!s->ev_fvol) HIP_TRY(hipEventCreateWithFlags(&s->ev_fvol, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(s->ev_fvol, stream));
+        s->fvol_recorded = true;
+        s->fvol_stream = stream;
+        s->fvol_stale = false;
+    } else if (!capturing && s->fvol_recorded && stream != s->fvol_stream) {
+        HIP_TRY(hipStreamWaitEvent(stream, s->ev_fvol, 0));
+    }
+    return TVR_OK;
+}
+
+extern "C" {
+
+size_t tvr_appearance_volume_bytes(const tvr_scene_desc *desc)
+{
+    if (check_desc(desc) != TVR_OK) return 0;
+    if (!takes_appearance_volume(*desc)) {
+        tvr_set_error(TVR_OK, "tvr_appearance_volume_bytes: REFTensoRF scenes and scenes with more than two encoding frequencies take no appearance volume");
+        return 0;
+    }
+    return appearance_volume_need(*desc);
+}
+
+int tvr_scene_set_appearance_volume(tvr_scene *s, void *buf, size_t bytes, void *stream)
+{
+    if (!s) return fail(TVR_ERR_INVALID, "tvr_scene_set_appearance_volume: scene is NULL");
+    if (!buf) {                            // detach: the factored gather and the basis product run from the next call on
+        s->fvol = nullptr;
+        s->fvol_stale = true;
+        s->fvol_recorded = false;
+        return TVR_OK;
+    }
+    NOT_CP(s);
+    if (s->desc.variant != 0) return fail(TVR_ERR_UNSUPPORTED, "tvr_scene_set_appearance_volume: a REFTensoRF scene's heads read the 144 products themselves; no volume form");
+    if (!takes_appearance_volume(s->desc))
+        return fail(TVR_ERR_UNSUPPORTED, "tvr_scene_set_appearance_volume: scenes with more than two encoding frequencies do not render on the kernel that reads the volume");
+    const size_t need = appearance_volume_need(s->desc);
+    if (need >= ((size_t)1 << 32))
+        return fail(TVR_ERR_UNSUPPORTED, "tvr_scene_set_appearance_volume: the volume of this grid takes %zu B; the gather addresses it with 32-bit byte offsets (below 4 GiB)", need);
+    if (bytes < need) return fail(TVR_ERR_SCRATCH, "tvr_scene_set_appearance_volume: buffer %zu B < required %zu B", bytes, need);
+    if ((uintptr_t)buf % 256) return fail(TVR_ERR_SCRATCH, "tvr_scene_set_appearance_volume: buffer must be 256-byte aligned");
+    s->fvol = (float4 *)buf;
+    s->fvol_stale = true;
+    s->fvol_recorded = false;
+    if (s->params_set && s->dev.arith == TVR_ARITH_F32) return ensure_fvol(s, (hipStream_t)stream);       // parameters are packed: bake now, on the caller's stream
     return TVR_OK;
 }
 
@@ -667,7 +744,7 @@ static int render_one(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S
     sa.q_ray = mo.q_ray;
     sa.rays = rays;
     sa.stats = mo.stats;
-    HIP_TRY(launch_shade(s->dev, SH_SRC_QUEUE, SH_DST_QUEUE, sa, stream));
+    HIP_TRY(launch_shade(s->dev, SH_SRC_QUEUE, SH_DST_QUEUE, sa, stream, s->fvol));
     if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
     if (dense && dense->rgb) {
         HIP_TRY(hipMemsetAsync(dense->rgb, 0, (size_t)n_rays * S * 3 * sizeof(float), stream));
@@ -714,6 +791,8 @@ static int render_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     }
     if (!s->cp) {                          // the density volume, if one is attached: current, and this stream behind its bake, before anything forks
         int rcv = ensure_dvol(s, stream);
+        if (rcv != TVR_OK) return rcv;
+        if (s->dev.arith == TVR_ARITH_F32) rcv = ensure_fvol(s, stream);          // (the reduced arithmetics shade on the factored kernels: nothing to bake for them)
         if (rcv != TVR_OK) return rcv;
     }
     // the per-sample outputs of `dense` are a debugging / parity surface ([n,S,*] arrays): such calls stay one launch set

@@ -94,6 +94,7 @@ static_assert(TVR_MLP_IMAGE_BYTES_REF + 16 <= 160 * 1024, "REFTensoRF's LDS imag
 #define TVR16_IMAGE_BYTES (TVR16_BASL + TVR16_BAS_BYTES - TVR16_BAS_STEP)       // 163 360 B (+ 16 B of matrix tokens <= 163 840)
 #define TVR16_REFG_BYTES (10 * TVR16_FRAG + 256)
 #define TVR16_BASG_BYTES (2 * TVR16_FRAG)            // global: lo parts of basis k-step 3, row blocks 0 and 1 as full fragments (rows >= 27 zero)
+#define TVR16_VOL_RECORD 128                         // bytes per record of the baked appearance volume (tvr_shade16.hip, vol_features)
 static_assert(TVR16_IMAGE_BYTES + 16 <= 160 * 1024, "the 16x16x32 LDS image must fit the CU's 160 KB");
 static_assert(TVR16_W3 % 16 == 0 && TVR16_BASH % 16 == 0, "float4 / uint4 reads need 16-B alignment");
 

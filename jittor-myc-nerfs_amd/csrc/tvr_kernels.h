@@ -76,9 +76,12 @@ hipError_t launch_density_feature(const SceneDev &sc, const float *xyz, long lon
 hipError_t launch_density_gradient(const SceneDev &sc, const float *xyz, long long m, const float h[3], const float inv2h[3], float *sigma_feature, float *grad,
                                    hipStream_t stream);
 hipError_t launch_alpha_sample(const SceneDev &sc, const float *xyz, long long m, float *out, hipStream_t stream);
-hipError_t launch_shade(const SceneDev &sc, int src, int dst, const ShadeArgs &a, hipStream_t stream);
+// fvol: the scene's baked appearance volume (tvr_scene_set_appearance_volume, baked by launch_appearance_volume) or nullptr — only the render path's kernel on 16x16x32
+// tiles (queue -> queue, default arithmetic) reads it; every other mode evaluates the factored form
+hipError_t launch_shade(const SceneDev &sc, int src, int dst, const ShadeArgs &a, hipStream_t stream, const float4 *fvol = nullptr);
 // tvr_shade16.hip: the render path (queue -> queue, TensorVMSplit, default arithmetic, at most two encoding frequencies) on 16x16x32 tiles, and its fragment images
-hipError_t launch_shade16(const SceneDev &sc, const ShadeArgs &a, hipStream_t stream);
+hipError_t launch_shade16(const SceneDev &sc, const ShadeArgs &a, hipStream_t stream, const float4 *fvol = nullptr);
+hipError_t launch_appearance_volume(const SceneDev &sc, void *out, hipStream_t stream);
 struct MlpShape;
 hipError_t launch_pack16(const float *W1, const float *b1, const float *W2, const float *b2, const float *W3, const float *b3, const float *basis, void *img, void *basg,
                          const MlpShape &sh, hipStream_t stream, const float *const *ref_W = nullptr, const float *const *ref_b = nullptr, void *refg = nullptr);

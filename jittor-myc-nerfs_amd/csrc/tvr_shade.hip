@@ -969,7 +969,7 @@ static hipError_t launch_shade_ar(const SceneDev &sc, const ShadeArgs &a, hipStr
 }
 
 template <bool REF>
-static hipError_t launch_shade_v(const SceneDev &sc, int src, int dst, const ShadeArgs &a, hipStream_t stream)
+static hipError_t launch_shade_v(const SceneDev &sc, int src, int dst, const ShadeArgs &a, hipStream_t stream, const float4 *fvol)
 {
     const bool rc = sc.range_check != 0;        // the inference entry points; the training forward has its own saturation flag (tvr_mlp_train.hip)
     if constexpr (!REF) {
@@ -988,7 +988,7 @@ static hipError_t launch_shade_v(const SceneDev &sc, int src, int dst, const Sha
 #ifndef TVR_SHADE16_REF
 #define TVR_SHADE16_REF 1
 #endif
-    if (src == SH_SRC_QUEUE && dst == SH_DST_QUEUE && sc.arith == TVR_ARITH_F32 && sc.img16 && (!REF || (TVR_SHADE16_REF && sc.refg16))) return launch_shade16(sc, a, stream);
+    if (src == SH_SRC_QUEUE && dst == SH_DST_QUEUE && sc.arith == TVR_ARITH_F32 && sc.img16 && (!REF || (TVR_SHADE16_REF && sc.refg16))) return launch_shade16(sc, a, stream, REF ? nullptr : fvol);
 #endif
     if (src == SH_SRC_QUEUE && dst == SH_DST_QUEUE) return rc ? launch_shade_ar<SH_SRC_QUEUE, SH_DST_QUEUE, REF, true>(sc, a, stream) : launch_shade_ar<SH_SRC_QUEUE, SH_DST_QUEUE, REF, false>(sc, a, stream);
     if (src == SH_SRC_XYZ && dst == SH_DST_FEAT) return rc ? launch_shade_t<SH_SRC_XYZ, SH_DST_FEAT, REF, true>(sc, a, stream) : launch_shade_t<SH_SRC_XYZ, SH_DST_FEAT, REF, false>(sc, a, stream);
@@ -997,9 +997,9 @@ static hipError_t launch_shade_v(const SceneDev &sc, int src, int dst, const Sha
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_shade(const SceneDev &sc, int src, int dst, const ShadeArgs &a, hipStream_t stream)
+hipError_t launch_shade(const SceneDev &sc, int src, int dst, const ShadeArgs &a, hipStream_t stream, const float4 *fvol)
 {
-    return sc.variant == 1 ? launch_shade_v<true>(sc, src, dst, a, stream) : launch_shade_v<false>(sc, src, dst, a, stream);
+    return sc.variant == 1 ? launch_shade_v<true>(sc, src, dst, a, stream, fvol) : launch_shade_v<false>(sc, src, dst, a, stream, fvol);
 }
 
 // ---- scene packing (reference layout -> channels-last, zero-padded) ----

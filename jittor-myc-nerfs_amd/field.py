@@ -256,6 +256,7 @@ class TensorBase(torch.nn.Module):
             L.lib().tvr_scene_destroy(self._scene)
         self._scene, self._packed, self._sig = None, None, None
         self._dvol, self._dvol_refused = None, False      # the scene's baked density volume (_settle_density_volume) goes with the scene
+        self._fvol, self._fvol_refused = None, False      # ... and its baked appearance volume (_settle_appearance_volume)
         self._grad_scratch = None
         self._alpha_dirty = True
 
@@ -294,6 +295,7 @@ class TensorBase(torch.nn.Module):
                              "There is no CPU fallback.")
         ps = self._param_list()
         sig = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in ps)
+        replayed = False
         if self._replays_pending():
             # a hipGraph replay of a captured training step packs the parameters at the START of the step and updates them at its end, bumping no version counter
             # and running no host code: the packed images are one optimizer step behind whatever the host sees.  The first host-driven call behind a replay re-packs
@@ -301,7 +303,7 @@ class TensorBase(torch.nn.Module):
             # proof (below).  Graphs made by training.make_graphed_step count their replays (GRAPH_REPLAYS): calls with no replay in between pay nothing (round 6,
             # ADVICE r5 — before, ONE captured step made every later inference call re-pack and re-validate for the life of the model); a capture made any other
             # way cannot tell the host about its replays and keeps the conservative behaviour: every call.
-            force = True
+            force = replayed = True
             self._replays_seen = GRAPH_REPLAYS[0]
         if self._scene is None:
             d = L.SceneDesc()
@@ -361,6 +363,7 @@ class TensorBase(torch.nn.Module):
                 self._captured_update = True
             self._sig = sig
             self._range_proven = None                  # new parameters: the fp16-range proof (below) is void until an inference call asks again
+            self._bounds_proven = None                 # (and the bounds themselves: _fp16_bounds_proven)
             L.check(lib.tvr_scene_set_range_check(self._scene, 1), "tvr_scene_set_range_check")
         if self._alpha_dirty:
             am = self._alphaMask
@@ -383,6 +386,8 @@ class TensorBase(torch.nn.Module):
             self._arith_set = self.mlp_arith
         if settle and not force:
             self._settle_density_volume()
+        if settle and (replayed or not force):         # (a re-pack forced by graph replays voids the bounds the appearance volume's attach rule rests on: decide again)
+            self._settle_appearance_volume()
         return self._scene
 
     # ---- the gate of the reduced arithmetics (include/tvr.h, tvr_scene_validate_arith) -----------------------------------------------------
@@ -484,6 +489,56 @@ class TensorBase(torch.nn.Module):
         L.check(lib.tvr_scene_set_density_volume(self._scene, vol.data_ptr(), vol.numel(), _stream_ptr(self.device)), "tvr_scene_set_density_volume")
         self._dvol = vol
 
+    # ---- the baked appearance volume (include/tvr.h, BAKED APPEARANCE VOLUME) -------------------------------------------------------------------------------
+    # The render path's shade kernel of a TensorVMSplit scene (at most two encoding frequencies, default arithmetic) reads the 27 appearance features from a volume of
+    # (gx+1)(gy+1)(gz+1) records of 128 B baked from the appearance factors and basis_mat (3.49 GB at 300^3) instead of gathering 144 channels and contracting them per
+    # sample: the same function up to fp32 rounding.  `appearance_volume = False` (class or instance) turns it off.  Attached at the first inference render, beside the
+    # density volume, ONLY IF (a) both volumes together take at most a quarter of the free device memory, and (b) the parameters' interval bounds prove the fp16 range
+    # (fp16_range_report()["proven"], whatever `fp16_range_check` says: the volume form never sees the 144 products, so a scene whose bounds fail keeps the factored
+    # kernel and its in-kernel check).  Both are decided per parameter state: nothing attaches or detaches between two calls on the same parameters.
+    appearance_volume = True
+
+    def _fp16_bounds_proven(self) -> bool:
+        """fp16_range_report()["proven"] for the parameters as packed, computed once per parameter state (one host read)."""
+        if getattr(self, "_bounds_proven", None) is None:
+            self._bounds_proven = bool(self.fp16_range_report()["proven"])
+        return self._bounds_proven
+
+    def _appearance_volume_eligible(self) -> bool:
+        """What does not depend on the parameters' values: the switch, the scene's kind, no parameters moving behind the host's back (raw captured training steps)."""
+        return (bool(self.appearance_volume) and not self._cp and self._variant == 0 and self.view_pe <= 2 and self.fea_pe <= 2
+                and not (getattr(self, "_captured_update", False) and getattr(self, "_captured_raw", True)))
+
+    def _settle_appearance_volume(self):
+        """_settle_density_volume's twin, called behind it: attach / detach the appearance volume as `appearance_volume` and the rule above say."""
+        lib = L.lib()
+        want = self._appearance_volume_eligible() and not self._fvol_refused
+        if want and not torch.cuda.is_current_stream_capturing():
+            want = self._fp16_bounds_proven()
+        elif want:
+            want = bool(getattr(self, "_bounds_proven", None)) if self._fvol is None else True        # inside a capture nothing is read back, allocated or dropped
+        if not want:
+            if self._fvol is not None and not torch.cuda.is_current_stream_capturing():
+                L.check(lib.tvr_scene_set_appearance_volume(self._scene, None, 0, None), "tvr_scene_set_appearance_volume")
+                self._fvol = None
+            return
+        if self._fvol is not None or torch.cuda.is_current_stream_capturing():
+            return
+        need = int(lib.tvr_appearance_volume_bytes(C.byref(self._scene_desc)))
+        held = 0 if self._dvol is None else int(self._dvol.numel())
+        free, _ = torch.cuda.mem_get_info(self.device)
+        cached = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        if need == 0 or need >= 1 << 32 or (need + held) * self.DENSITY_VOLUME_MEMORY_SHARE > free + cached + held:
+            self._fvol_refused = True
+            return
+        try:
+            vol = L.dev_bytes(need, self.device, what="appearance volume")
+        except torch.OutOfMemoryError:
+            self._fvol_refused = True
+            return
+        L.check(lib.tvr_scene_set_appearance_volume(self._scene, vol.data_ptr(), vol.numel(), _stream_ptr(self.device)), "tvr_scene_set_appearance_volume")
+        self._fvol = vol
+
     render_rays_is_the_frame = True           # render_rays(rays) IS forward(rays, is_train=False) for this class and REFTensoRF (render.FrameStream relies on it)
 
     def scene_settled(self) -> bool:
@@ -496,6 +551,10 @@ class TensorBase(torch.nn.Module):
             return False
         if not self._cp and bool(self.density_volume) != (self._dvol is not None) and not (self.density_volume and self._dvol_refused):
             return False                                                            # the next call attaches (and bakes) or detaches the density volume
+        if getattr(self, "_bounds_proven", None) is None and self._appearance_volume_eligible() and not self._fvol_refused:
+            return False                                                            # the appearance volume's attach rule has not seen these parameters yet
+        if ((self._appearance_volume_eligible() and not self._fvol_refused and bool(getattr(self, "_bounds_proven", None))) != (self._fvol is not None)):
+            return False                                                            # the next call attaches (and bakes) or detaches the appearance volume
         if tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in self._param_list()) != self._sig:
             return False
         if self.mlp_arith != "f32" and self.view_pe <= 2 and self.fea_pe <= 2:
@@ -607,7 +666,7 @@ class TensorBase(torch.nn.Module):
             return
         mode = self.fp16_range_check
         if mode == "auto":
-            self._range_proven = bool(self.fp16_range_report()["proven"])
+            self._range_proven = self._fp16_bounds_proven()
         elif mode in ("on", "off"):
             self._range_proven = mode == "off"
         else:

@@ -239,6 +239,7 @@ class NerfPlusPlus(TensorVMSplit):
     # model's frame is its background network (98.7 ms); what a volume gains on the foreground's explicit-depth march (tvr_render_z) is NOT measured.  The
     # library serves tvr_render_z from an attached volume like every other render entry (include/tvr.h), so `model.density_volume = True` opts a model in.
     density_volume = False
+    appearance_volume = False        # likewise opt-in: `model.appearance_volume = True`
     render_rays_is_the_frame = False          # forward() adds the background; render_rays alone is the foreground field (render.FrameStream refuses this model)
 
     def scene_settled(self) -> bool:
