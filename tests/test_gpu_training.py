@@ -228,7 +228,8 @@ def test_fused_regularisers_match_the_torch_formulations(tiny_arrays, hyper_tiny
             nd = dotp.view(-1)[1:].view(n_comp - 1, n_comp + 1)[..., :-1]
             total = total + torch.mean(torch.abs(nd))
         return total
-    vs = [torch.randn((1, c, n, 1), device="cuda", generator=g).requires_grad_(True) for c, n in ((16, 300), (16, 53), (48, 300), (48, 129), (5, 7), (2, 301))]
+    vs = [torch.randn((1, c, n, 1), device="cuda", generator=g).requires_grad_(True) for c, n in ((16, 300), (16, 53), (48, 300), (48, 129), (5, 7), (2, 301),
+                                                                                                      (48, 321), (16, 1000))]   # nc * ns > 15 360 floats: ortho_kernel's global-memory path
     rs = [t.detach().double().requires_grad_(True) for t in vs]
     v = _LineOrthoFn.apply(*vs)
     (1e-4 * v).backward()
