@@ -927,6 +927,74 @@ int tvr_mesh_atlas_points(const float *verts, int64_t n_vertices, const int32_t 
 int tvr_mesh_texture_sample(const int32_t *tri, const float *bary, int64_t n_pix, const void *atlas, int32_t fmt, int32_t Ha, int32_t Wa, int32_t P, int32_t C,
                             int64_t n_triangles, float *out, size_t out_bytes, void *stream);
 
+/* Ray queries against an indexed triangle mesh (csrc/tvr_mesh_bvh.hip): a linear bounding-volume hierarchy over the triangles, closest-hit and any-hit casts of
+ * arbitrary rays, and the cosine-weighted openness (ambient occlusion) of points on the mesh.  ADDITIVE exports: TVR_VERSION is unchanged.  DESIGN.md §4.17.
+ * verts [n_vertices][3] fp32, faces [n_triangles][3] int32.  All arithmetic is fp32 with every operation rounded on its own (no fused multiply-add), in exactly the order
+ * written; divisions are IEEE correctly rounded; dot and cross products are tvr_mesh_raster's.
+ * RAY: an origin o and a direction d, fp32; d need not be unit length; t is parametric, the hit point is o + t * d.
+ * (RAY, TRIANGLE): tvr_mesh_raster's own expressions with the camera rotation taken as the identity, the camera centre at o and dir = d.  q_k = v_k - o;
+ *   n_0 = q1 x q2, n_1 = q2 x q0, n_2 = q0 x q1;  det = q0 . n_0;  sg = +1 if det > 0, -1 if det < 0;  det == 0, NaN or a non-finite q: no hit.  E_k = sg * (d . n_k);
+ *   inside iff for every k: E_k > 0, or E_k == 0 and owner_k = (vertex index at the start of edge k < index at its end) XOR (sg < 0), edge k running from corner (k+1)%3
+ *   to corner (k+2)%3.  t = (pn . q0) / (d . pn) with pn = (q1 - q0) x (q2 - q0).  A hit needs t finite and t_min < t <= t_max.  cull != 0 drops det > 0.
+ *   As in the rasteriser, the two evaluations of a shared edge are exact negations of each other: a ray that passes between two equally facing triangles across their
+ *   shared edge belongs to exactly one of them.  NOT promised: anything for a ray exactly through a vertex (it may miss the whole fan).
+ * CLOSEST HIT (mode TVR_MESH_BVH_CLOSEST): the hit with the smallest t, ties going to the smaller triangle index.  t [n_rays] (+inf on a miss), tri [n_rays] (-1),
+ *   bary [n_rays][3]: b_k = E_k / ((E_0 + E_1) + E_2) (zeros).  ANY HIT (mode TVR_MESH_BVH_ANY): hit [n_rays] uint8 only, 1 iff some triangle is hit; which one was found
+ *   is not defined.  The buffers of the other mode may be NULL.  A ray with a non-finite component or d == 0 never hits and is counted (refused).  A triangle with a
+ *   non-finite vertex is never hit and is counted by the build.  Results do not depend on the order or the batching of the rays.
+ * THE HIERARCHY is a linear BVH (Karras 2012) over 64-bit keys, one per triangle: (30-bit Morton code of the centroid ((v0 + v1) + v2) * (1/3) in the bounding box of
+ *   the triangles whose vertices are all finite, 10 bits per axis, x highest) << 32 | triangle index; a triangle with a non-finite vertex or an index outside
+ *   0 .. n_vertices-1 gets the largest code 2^30 - 1.
+ *   tvr_mesh_bvh_keys writes keys_out [n_triangles]; THE CALLER SORTS THEM ascending (they are unique, so every correct sort gives the same order; the Python side uses
+ *   torch.sort on the device); tvr_mesh_bvh_build takes the sorted keys and writes the blob.  build checks that the keys ascend strictly, carry codes below 2^30 and name
+ *   every triangle exactly once; if not, or if a face index is outside 0 .. n_vertices-1, *fault_flag_dev = 1, the header's `bad` word is set and no tree is written.
+ *   Node numbering: 2F-1 nodes; 0 .. F-2 are internal (0 is the root), node F-1+i is the leaf of the i-th sorted key; F == 1: node 0 is the one leaf; F == 0: no node.
+ *   Boxes are exact min / max of the corners; the leaf of a skipped triangle has the empty box lo = +inf, hi = -inf.  Topology: every internal node finds its key range
+ *   and its split from the sorted keys alone.  Refit: 62 launches; launch p computes the internal nodes whose two children were finished by an EARLIER launch (a pass
+ *   number per node says which), so no workgroup hands data to another inside a launch and the kernel boundary is the only ordering.  The height is at most 62 (the keys
+ *   have 62 significant bits, every level splits on one); a root left unfinished raises the fault flag.  No host read anywhere.
+ *   The blob is a function of (verts, faces) alone: the same bytes on every run (build zeroes the padding).  60 B per triangle + 256 B.
+ *   counts_dev of build (int32[4], may be NULL): {triangles skipped, height, internal nodes, the header's bad word}.
+ *   tvr_mesh_bvh_describe gives the blob's layout (byte offsets from its start, strides in bytes): header {uint32 magic, F, bad, height, skipped, 3 reserved; float lo[3],
+ *   hi[3] = the root's box}, boxes [2F-1][lo xyz, hi xyz], children [F-1][2] int32 node numbers, leaf_order [F] int32 triangle indices.
+ * TRAVERSAL (tvr_mesh_bvh_cast): one lane per ray; a 64-entry stack per lane in LDS; the nearer child is visited first and the farther one pushed, so the stack never
+ *   holds more than one entry per level; a push beyond 64 entries is dropped and raises the fault flag.  A node is skipped only if the ray's PADDED slab test misses its
+ *   box or enters it at a t strictly greater than the best hit so far (strictly: an equal t may still win the tie on the index).  Padding: every face of the box is moved
+ *   outwards by 2^-15 x the largest per-axis distance from o to the box; a stated margin for the rounding of E_k, not a proof.
+ *   counts_dev of cast / occlusion (int64[4], may be NULL; zeroed by the call): {rays hit, rays refused, node tests, triangle tests}, summed per wave, one atomic per
+ *   wave and counter.  Every index read from the blob and the faces is checked against its bound before use; an inconsistent blob (wrong magic, F, or bad != 0) or an
+ *   index outside its range raises the fault flag, and no load or store leaves the caller's buffers.
+ * AMBIENT OCCLUSION (tvr_mesh_bvh_occlusion): points [n_points][3], normals [n_points][3], a direction table dirs [n_dirs][3] (finite), bias, t_max; out [n_points].
+ *   Per point, for k = 0 .. n_dirs-1 in order: c = dirs_k . n;  d'_k = dirs_k if c >= 0, else -dirs_k;  w_k = d'_k . n (= |c|);  the ray runs from
+ *   (p.x + bias * n.x, p.y + bias * n.y, p.z + bias * n.z) along d'_k in any-hit mode over (0, t_max], cull off;  out = (sum w_k * visible_k) / (sum w_k), both sums in k
+ *   order.  out = 1 where the normal is zero or non-finite or sum w_k is not > 0.  One lane per point.  counts_dev as for cast, per ray.
+ * Errors, all before any launch, tvr_last_error() names the argument: TVR_ERR_INVALID for a NULL pointer where data is due, a negative count, a misaligned blob or
+ *   scratch (256 B) or keys (8 B), mode or cull outside 0 / 1, a NaN t_min / t_max, a non-finite bias, n_dirs above TVR_MESH_BVH_MAX_DIRS; TVR_ERR_UNSUPPORTED for
+ *   n_triangles above TVR_MESH_BVH_MAX_TRIANGLES (the *_bytes queries then return 0) and for n_vertices, n_rays or n_points >= 2^31; TVR_ERR_SCRATCH for an undersized
+ *   blob, scratch, keys or output.  n_triangles == 0 is valid (an empty tree: every ray misses), so are n_rays == 0 and n_points == 0. */
+#define TVR_MESH_BVH_MAX_TRIANGLES 1073741824      /* 2^30: the 2F - 1 node numbers fit int32 */
+#define TVR_MESH_BVH_MAX_DIRS 65536
+#define TVR_MESH_BVH_CLOSEST 0
+#define TVR_MESH_BVH_ANY 1
+typedef struct {
+    size_t header, boxes, children, leaf_order, total;     /* byte offsets from the blob's start; total == tvr_mesh_bvh_bytes */
+    size_t box_stride, child_stride, leaf_stride;          /* bytes per node / per internal node / per leaf */
+    size_t n_nodes, n_internal;
+} tvr_mesh_bvh_layout;
+size_t tvr_mesh_bvh_bytes(int64_t n_triangles);
+size_t tvr_mesh_bvh_scratch_bytes(int64_t n_triangles);
+int tvr_mesh_bvh_describe(int64_t n_triangles, tvr_mesh_bvh_layout *out);
+int tvr_mesh_bvh_keys(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, uint64_t *keys_out, size_t keys_bytes, void *scratch,
+                      size_t scratch_bytes, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_bvh_build(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const uint64_t *sorted_keys, void *bvh, size_t bvh_bytes,
+                       void *scratch, size_t scratch_bytes, int32_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_bvh_cast(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const float *origins,
+                      const float *dirs, int64_t n_rays, float t_min, float t_max, int32_t mode, int32_t cull, float *t, size_t t_bytes, int32_t *tri, size_t tri_bytes,
+                      float *bary, size_t bary_bytes, uint8_t *hit, size_t hit_bytes, int64_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_bvh_occlusion(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const float *points,
+                           const float *normals, int64_t n_points, const float *dirs, int32_t n_dirs, float bias, float t_max, float *out, size_t out_bytes,
+                           int64_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,10 @@ class MeshCamera(C.Structure):          # tvr_mesh_camera
                 ("near_", C.c_float), ("cull", C.c_int32), ("large_bbox", C.c_int32)]
 
 
+class MeshBvhLayout(C.Structure):       # tvr_mesh_bvh_layout
+    _fields_ = [(n, C.c_size_t) for n in ("header", "boxes", "children", "leaf_order", "total", "box_stride", "child_stride", "leaf_stride", "n_nodes", "n_internal")]
+
+
 # name -> (restype, argtypes); every symbol include/tvr.h and include/tvr_ngp.h declare
 SYMBOLS = {
     "tvr_version": (C.c_int, []),
@@ -227,6 +231,17 @@ SYMBOLS = {
                                         C.c_size_t, C.c_void_p, C.c_void_p]),
     "tvr_mesh_texture_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
                                           C.c_size_t, C.c_void_p]),
+    "tvr_mesh_bvh_bytes": (C.c_size_t, [C.c_int64]),
+    "tvr_mesh_bvh_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "tvr_mesh_bvh_describe": (C.c_int, [C.c_int64, C.POINTER(MeshBvhLayout)]),
+    "tvr_mesh_bvh_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "tvr_mesh_bvh_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "tvr_mesh_bvh_cast": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "tvr_mesh_bvh_occlusion": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                         C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/tvr_ngp.h
     "tvr_ngp_update_bitfield": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tvr_ngp_sample_scratch_bytes": (C.c_size_t, [C.c_int64]),

@@ -2374,3 +2374,143 @@ int tvr_mesh_texture_sample(const int32_t *tri, const float *bary, int64_t n_pix
     HIP_TRY(launch_mesh_texture_sample(tri, bary, n_pix, atlas, fmt, ha * wa, P, C, n_triangles, out, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- linear BVH over a mesh's triangles, ray casts and ambient occlusion (tvr_mesh_bvh.hip) ----------------------------------------------------------------------------
+static int bvh_counts(const char *fn, int64_t n_triangles)
+{
+    if (n_triangles < 0) return fail(TVR_ERR_INVALID, "%s: n_triangles = %lld is negative", fn, (long long)n_triangles);
+    if (n_triangles > TVR_MESH_BVH_MAX_TRIANGLES)
+        return fail(TVR_ERR_UNSUPPORTED, "%s: n_triangles = %lld: at most TVR_MESH_BVH_MAX_TRIANGLES = %d (the 2F - 1 node indices are int32)", fn, (long long)n_triangles,
+                    TVR_MESH_BVH_MAX_TRIANGLES);
+    return TVR_OK;
+}
+
+// what every call that reads a mesh checks: counts, pointers
+static int bvh_mesh(const char *fn, const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles)
+{
+    const int rc = bvh_counts(fn, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (n_vertices < 0) return fail(TVR_ERR_INVALID, "%s: n_vertices = %lld is negative", fn, (long long)n_vertices);
+    if (n_vertices > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices = %lld: vertex indices are int32", fn, (long long)n_vertices);
+    if (n_triangles > 0 && (!faces || !verts)) return fail(TVR_ERR_INVALID, "%s: faces / verts is NULL with %lld triangles", fn, (long long)n_triangles);
+    return TVR_OK;
+}
+
+// a blob or scratch buffer: not NULL, 256-byte aligned, at least `want` bytes
+static int bvh_buffer(const char *fn, const char *what, const void *p, size_t have, size_t want, const char *query)
+{
+    if (!p) return fail(TVR_ERR_INVALID, "%s: %s is NULL", fn, what);
+    if ((uintptr_t)p % 256) return fail(TVR_ERR_INVALID, "%s: %s is not 256-byte aligned", fn, what);
+    if (have < want) return fail(TVR_ERR_SCRATCH, "%s: %s holds %zu B, %s asks for %zu B", fn, what, have, query, want);
+    return TVR_OK;
+}
+
+size_t tvr_mesh_bvh_bytes(int64_t n_triangles)
+{
+    if (bvh_counts(__func__, n_triangles) != TVR_OK) return 0;
+    return mesh_bvh_bytes(n_triangles, nullptr);
+}
+
+size_t tvr_mesh_bvh_scratch_bytes(int64_t n_triangles)
+{
+    if (bvh_counts(__func__, n_triangles) != TVR_OK) return 0;
+    return mesh_bvh_scratch_bytes(n_triangles);
+}
+
+int tvr_mesh_bvh_describe(int64_t n_triangles, tvr_mesh_bvh_layout *out)
+{
+    if (!out) return fail(TVR_ERR_INVALID, "%s: out is NULL", __func__);
+    const int rc = bvh_counts(__func__, n_triangles);
+    if (rc != TVR_OK) return rc;
+    MeshBvhCarve c;
+    mesh_bvh_bytes(n_triangles, &c);
+    out->header = c.header; out->boxes = c.box; out->children = c.child; out->leaf_order = c.leaf_tri; out->total = c.total;
+    out->box_stride = 6 * sizeof(float); out->child_stride = 2 * sizeof(int32_t); out->leaf_stride = sizeof(int32_t);
+    out->n_nodes = n_triangles ? 2 * (size_t)n_triangles - 1 : 0;
+    out->n_internal = n_triangles ? (size_t)n_triangles - 1 : 0;
+    return TVR_OK;
+}
+
+int tvr_mesh_bvh_keys(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, uint64_t *keys_out, size_t keys_bytes, void *scratch,
+                      size_t scratch_bytes, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_triangles > 0 && !keys_out) return fail(TVR_ERR_INVALID, "%s: keys_out is NULL with %lld triangles", __func__, (long long)n_triangles);
+    if (keys_out && (uintptr_t)keys_out % 8) return fail(TVR_ERR_INVALID, "%s: keys_out is not 8-byte aligned", __func__);
+    if (keys_bytes < (size_t)n_triangles * sizeof(uint64_t))
+        return fail(TVR_ERR_SCRATCH, "%s: keys_out holds %zu B, %lld triangles x uint64 need %zu B", __func__, keys_bytes, (long long)n_triangles, (size_t)n_triangles * 8);
+    rc = bvh_buffer(__func__, "scratch", scratch, scratch_bytes, mesh_bvh_scratch_bytes(n_triangles), "tvr_mesh_bvh_scratch_bytes");
+    if (rc != TVR_OK) return rc;
+    HIP_TRY(launch_mesh_bvh_keys(verts, n_vertices, faces, n_triangles, (unsigned long long *)keys_out, scratch, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_bvh_build(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const uint64_t *sorted_keys, void *bvh, size_t bvh_bytes,
+                       void *scratch, size_t scratch_bytes, int32_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_triangles > 0 && !sorted_keys) return fail(TVR_ERR_INVALID, "%s: sorted_keys is NULL with %lld triangles", __func__, (long long)n_triangles);
+    if (sorted_keys && (uintptr_t)sorted_keys % 8) return fail(TVR_ERR_INVALID, "%s: sorted_keys is not 8-byte aligned", __func__);
+    rc = bvh_buffer(__func__, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+    if (rc != TVR_OK) return rc;
+    rc = bvh_buffer(__func__, "scratch", scratch, scratch_bytes, mesh_bvh_scratch_bytes(n_triangles), "tvr_mesh_bvh_scratch_bytes");
+    if (rc != TVR_OK) return rc;
+    HIP_TRY(launch_mesh_bvh_build(verts, n_vertices, faces, n_triangles, (const unsigned long long *)sorted_keys, bvh, scratch, (int *)counts_dev, fault_flag_dev,
+                                  (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_bvh_cast(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const float *origins,
+                      const float *dirs, int64_t n_rays, float t_min, float t_max, int32_t mode, int32_t cull, float *t, size_t t_bytes, int32_t *tri, size_t tri_bytes,
+                      float *bary, size_t bary_bytes, uint8_t *hit, size_t hit_bytes, int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_rays < 0) return fail(TVR_ERR_INVALID, "%s: n_rays = %lld is negative", __func__, (long long)n_rays);
+    if (n_rays > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_rays = %lld: at most 2^31 - 1 rays per call", __func__, (long long)n_rays);
+    if (mode != TVR_MESH_BVH_CLOSEST && mode != TVR_MESH_BVH_ANY) return fail(TVR_ERR_INVALID, "%s: mode = %d is neither 0 (closest hit) nor 1 (any hit)", __func__, (int)mode);
+    if (cull != 0 && cull != 1) return fail(TVR_ERR_INVALID, "%s: cull = %d is neither 0 nor 1", __func__, (int)cull);
+    if (std::isnan(t_min) || std::isnan(t_max)) return fail(TVR_ERR_INVALID, "%s: t_min = %g / t_max = %g is NaN", __func__, (double)t_min, (double)t_max);
+    rc = bvh_buffer(__func__, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+    if (rc != TVR_OK) return rc;
+    if (n_rays > 0 && (!origins || !dirs)) return fail(TVR_ERR_INVALID, "%s: origins / dirs is NULL with %lld rays", __func__, (long long)n_rays);
+    if (mode == TVR_MESH_BVH_ANY) {
+        if (n_rays > 0 && !hit) return fail(TVR_ERR_INVALID, "%s: hit is NULL in any-hit mode", __func__);
+        if (hit_bytes < (size_t)n_rays) return fail(TVR_ERR_SCRATCH, "%s: hit holds %zu B, the kernel writes %lld uint8", __func__, hit_bytes, (long long)n_rays);
+    } else {
+        if (n_rays > 0 && (!t || !tri || !bary)) return fail(TVR_ERR_INVALID, "%s: t / tri / bary is NULL in closest-hit mode", __func__);
+        NEED("t [n_rays]", t_bytes, n_rays, 1);
+        NEED("tri [n_rays]", tri_bytes, n_rays, 1);
+        NEED("bary [n_rays,3]", bary_bytes, n_rays, 3);
+    }
+    HIP_TRY(launch_mesh_bvh_cast(verts, n_vertices, faces, n_triangles, bvh, origins, dirs, n_rays, t_min, t_max, mode == TVR_MESH_BVH_ANY, cull, t, tri, bary, hit,
+                                 (unsigned long long *)counts_dev, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_bvh_occlusion(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const float *points,
+                           const float *normals, int64_t n_points, const float *dirs, int32_t n_dirs, float bias, float t_max, float *out, size_t out_bytes,
+                           int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_points < 0 || n_dirs < 0) return fail(TVR_ERR_INVALID, "%s: n_points = %lld / n_dirs = %d is negative", __func__, (long long)n_points, (int)n_dirs);
+    if (n_points > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_points = %lld: at most 2^31 - 1 points per call", __func__, (long long)n_points);
+    if (n_dirs > TVR_MESH_BVH_MAX_DIRS) return fail(TVR_ERR_INVALID, "%s: n_dirs = %d above TVR_MESH_BVH_MAX_DIRS = %d", __func__, (int)n_dirs, TVR_MESH_BVH_MAX_DIRS);
+    if (!std::isfinite(bias)) return fail(TVR_ERR_INVALID, "%s: bias = %g must be finite", __func__, (double)bias);
+    if (std::isnan(t_max)) return fail(TVR_ERR_INVALID, "%s: t_max is NaN", __func__);
+    rc = bvh_buffer(__func__, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+    if (rc != TVR_OK) return rc;
+    if (n_points > 0 && (!points || !normals || !out)) return fail(TVR_ERR_INVALID, "%s: points / normals / out is NULL with %lld points", __func__, (long long)n_points);
+    if (n_dirs > 0 && !dirs) return fail(TVR_ERR_INVALID, "%s: dirs is NULL with n_dirs = %d", __func__, (int)n_dirs);
+    NEED("out [n_points]", out_bytes, n_points, 1);
+    HIP_TRY(launch_mesh_bvh_occlusion(verts, n_vertices, faces, n_triangles, bvh, points, normals, n_points, dirs, n_dirs, bias, t_max, out,
+                                      (unsigned long long *)counts_dev, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

@@ -287,3 +287,23 @@ hipError_t launch_mesh_atlas_points(const float *verts, long long n_vertices, co
                                     float *pos, int *tri, unsigned *fault, hipStream_t stream);
 hipError_t launch_mesh_texture_sample(const int *tri, const float *bary, long long n_pix, const void *atlas, int fmt, long long n_texels, int P, int C,
                                       long long n_triangles, float *out, hipStream_t stream);
+
+// tvr_mesh_bvh.hip: the linear BVH over a mesh's triangles and its ray queries (include/tvr.h tvr_mesh_bvh_*).  The blob: a header of MESH_BVH_HEADER_BYTES, the boxes
+// of the 2F-1 nodes (internal nodes 0 .. F-2, then the leaves in key order; 6 fp32 each), the F-1 child pairs, the F triangle indices of the leaves, each array rounded
+// up to 256 B.  The build's scratch: 256 B of header, one pass word per internal node, one bit per triangle.  The host has checked counts, pointers, sizes and alignment.
+#define MESH_BVH_HEADER_BYTES 256
+struct MeshBvhCarve {
+    size_t header, box, child, leaf_tri, total;
+};
+size_t mesh_bvh_bytes(long long n_triangles, MeshBvhCarve *carve);
+size_t mesh_bvh_scratch_bytes(long long n_triangles);
+hipError_t launch_mesh_bvh_keys(const float *verts, long long n_vertices, const int *faces, long long n_triangles, unsigned long long *keys, void *scratch, unsigned *fault,
+                                hipStream_t stream);
+hipError_t launch_mesh_bvh_build(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const unsigned long long *keys, void *bvh, void *scratch,
+                                 int *counts, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_bvh_cast(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *origins, const float *dirs,
+                                long long n_rays, float t_min, float t_max, int any_hit, int cull, float *t, int *tri, float *bary, unsigned char *hit,
+                                unsigned long long *counts, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_bvh_occlusion(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *points,
+                                     const float *normals, long long n_points, const float *dirs, int n_dirs, float bias, float t_max, float *out, unsigned long long *counts,
+                                     unsigned *fault, hipStream_t stream);

@@ -1100,7 +1100,7 @@ class TensorBase(torch.nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, level=0.0005, gridSize=None, spacing="reference", flip=False, normals=False, colors=False, min_component_faces=0, keep_largest=0,
-                    simplify=0.0, smooth=0, refine=0, texture=0):
+                    simplify=0.0, smooth=0, refine=0, texture=0, ao=0, ao_radius=None):
         """The field's surface as a PLY file (train.py:41-59 -> utils.py:146-207): getDenseAlpha(gridSize), the HIP marching cubes (mesh.marching_cubes) at `level`
         (default: the value at train.py:59), mesh.write_ply.  Works for every model class: the volume comes from compute_alpha.  Returns (verts, faces) on the device.
 
@@ -1134,7 +1134,15 @@ class TensorBase(torch.nn.Module):
         texture: P, the patch side in texels (5 .. 64) of a per-triangle texture atlas (bake_texture; mesh.atlas_shape's default columns).  0 = off, the default:
         nothing new is called or written.  It runs AFTER every other step, on mesh_sample_positions(verts) like the attributes, and writes
         `<path minus .ply>.obj / .mtl / .png` BESIDE the PLY (mesh.write_obj with the written vertices, and the normals when `normals` is on); the PLY itself is what
-        it is without the option.  self.mesh_export_stats gains atlas_patch / atlas_columns / atlas_height / atlas_width and bake_texture's entries."""
+        it is without the option.  self.mesh_export_stats gains atlas_patch / atlas_columns / atlas_height / atlas_width and bake_texture's entries.
+        ao: K, the number of directions (mesh.fibonacci_sphere(K)) of an ambient-occlusion pass over the final mesh (mesh.build_bvh, mesh.ambient_occlusion): the
+        cosine-weighted openness of every vertex, written as the grey round(255 * AO) into the PLY's `red green blue` — what makes a mesh without colours legible
+        in a viewer.  0 = off, the default: nothing new is called and the file is what it was without the option.  It runs AFTER every geometry step, over the
+        written vertices, with the field's normals at mesh_sample_positions(verts) (computed even when `normals` is off; they are written only when it is on); the
+        rays start half an export voxel (its smallest edge) off the surface and end after `ao_radius` such voxels (None = unlimited).  Works for REFTensoRF too: the
+        grey does not come from the appearance branch.  With colors=True or texture > 0 it is a ValueError — the field's colours already hold the scene's lighting.
+        An integer in 0 .. 65536, ao_radius None or finite and > 0, else ValueError; self.mesh_export_stats gains ao_directions / ao_bias / ao_t_max / ao_mean /
+        bvh_height and the ray counters of mesh.ambient_occlusion."""
         from . import mesh
         if min_component_faces < 0 or keep_largest < 0:
             raise ValueError(f"min_component_faces = {min_component_faces} / keep_largest = {keep_largest}: negative values mean nothing (0 switches an option off)")
@@ -1147,6 +1155,13 @@ class TensorBase(torch.nn.Module):
             raise ValueError(f"texture = {texture!r}: the atlas' patch side in texels, 0 (off) or an integer in {mesh.ATLAS_MIN_P} .. {mesh.ATLAS_MAX_P}")
         if texture and not str(path).endswith(".ply"):
             raise ValueError(f"texture = {texture}: the atlas goes to <path minus .ply>.obj / .mtl / .png, and {str(path)!r} does not end in .ply")
+        if isinstance(ao, bool) or not isinstance(ao, (int, np.integer)) or not 0 <= int(ao) <= mesh.BVH_MAX_DIRS:
+            raise ValueError(f"ao = {ao!r}: the number of ambient-occlusion directions, an integer in 0 .. {mesh.BVH_MAX_DIRS} (0 = off)")
+        if ao and (colors or texture):
+            raise ValueError("ao writes its grey into the PLY's red green blue and cannot be combined with colors=True or texture > 0: the field's colours already "
+                             "contain the scene's lighting")
+        if ao_radius is not None and not (np.isfinite(float(ao_radius)) and float(ao_radius) > 0):
+            raise ValueError(f"ao_radius = {ao_radius!r}: the occlusion rays' length in export voxels, None (unlimited) or a finite value > 0")
         alpha, _ = self.getDenseAlpha(gridSize)
         aabb = self.aabb.to(device=alpha.device, dtype=torch.float32)
         n = torch.tensor([float(s) for s in alpha.shape], dtype=torch.float32, device=alpha.device)
@@ -1170,13 +1185,22 @@ class TensorBase(torch.nn.Module):
             at, _ = self.project_to_isosurface(self.mesh_sample_positions(verts, alpha.shape, spacing), level, iterations=int(refine),
                                                max_move=((aabb[1] - aabb[0]) / (n - 1)).tolist(), stats=self.mesh_export_stats)
             verts = at if spacing == "samples" else aabb[0] + (at - aabb[0]) * ((n - 1) / n)
-        if not (normals or colors or texture):
+        if not (normals or colors or texture or ao):
             mesh.write_ply(path, verts, faces)
             return verts, faces
         if at is None:
             at = self.mesh_sample_positions(verts, alpha.shape, spacing)
-        attrs = self.mesh_vertex_attributes(at, normals=normals, colors=colors)
-        mesh.write_ply(path, verts, faces, normals=attrs.get("normals"), colors=attrs.get("colors"))
+        attrs = self.mesh_vertex_attributes(at, normals=bool(normals or ao), colors=colors)
+        if ao:
+            vox = float(voxel.min())
+            st = {}
+            occ = mesh.ambient_occlusion(mesh.build_bvh(verts, faces, stats=st), attrs["normals"], n_dirs=int(ao), bias=0.5 * vox,
+                                         t_max=float("inf") if ao_radius is None else float(ao_radius) * vox, stats=st)
+            attrs["colors"] = torch.round(255.0 * occ.clamp(0.0, 1.0)).to(torch.uint8).unsqueeze(1).expand(-1, 3).contiguous()
+            self.mesh_export_stats.update(ao_directions=int(ao), ao_bias=0.5 * vox, ao_t_max=None if ao_radius is None else float(ao_radius) * vox,
+                                          ao_mean=float(occ.mean()) if occ.numel() else None, bvh_height=st["height"],
+                                          **{k: st[k] for k in ("rays_hit", "rays_refused", "node_tests", "triangle_tests")})
+        mesh.write_ply(path, verts, faces, normals=attrs.get("normals") if normals else None, colors=attrs.get("colors"))
         if texture:
             base = str(path)[:-4]
             Ha, Wa, cols = mesh.atlas_shape(faces.shape[0], int(texture))

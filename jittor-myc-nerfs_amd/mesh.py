@@ -821,3 +821,185 @@ def read_obj(path):
     if texture is None:
         raise ValueError(f"{path}: {mtllib} names no map_Kd picture")
     return verts, faces.astype(np.int32), uvs[fts.reshape(-1)].reshape(-1, 3, 2), texture
+
+
+# ---- ray queries: a linear BVH, closest / any hit, ambient occlusion (csrc/tvr_mesh_bvh.hip, include/tvr.h tvr_mesh_bvh_*) ---------------------------------
+BVH_MAX_TRIANGLES = 1 << 30     # include/tvr.h TVR_MESH_BVH_MAX_TRIANGLES
+BVH_MAX_DIRS = 65536            # include/tvr.h TVR_MESH_BVH_MAX_DIRS
+BVH_CAST_CHUNK = 1 << 24        # rays per tvr_mesh_bvh_cast call of cast_rays (results do not depend on it)
+
+
+class MeshBVH:
+    """What build_bvh returns: the blob (uint8, on the device) and the mesh it was built over — verts [V,3] float32 and faces [F,3] int32 as the library reads them
+    (the casts read both again, so they must not change while the hierarchy is in use).  height / triangles_skipped are the build's counts."""
+
+    def __init__(self, blob, verts, faces, height, triangles_skipped):
+        self.blob, self.verts, self.faces, self.height, self.triangles_skipped = blob, verts, faces, int(height), int(triangles_skipped)
+
+    @property
+    def n_triangles(self) -> int:
+        return int(self.faces.shape[0])
+
+    @property
+    def n_vertices(self) -> int:
+        return int(self.verts.shape[0])
+
+    @property
+    def device(self):
+        return self.blob.device
+
+    def layout(self) -> dict:
+        """tvr_mesh_bvh_describe of this blob: byte offsets, strides and node counts (what a test reads the tree with)."""
+        return bvh_layout(self.n_triangles)
+
+
+def bvh_layout(n_triangles: int) -> dict:
+    """tvr_mesh_bvh_describe(F) as a dict (header / boxes / children / leaf_order / total offsets, box / child / leaf strides, n_nodes, n_internal).  Host only."""
+    lay = L.MeshBvhLayout()
+    L.check(L.lib().tvr_mesh_bvh_describe(int(n_triangles), C.byref(lay)), "tvr_mesh_bvh_describe")
+    return {n: int(getattr(lay, n)) for n, _ in L.MeshBvhLayout._fields_}
+
+
+def _mesh_on_device(verts, faces, what: str):
+    f = _faces_on_device(faces, what)
+    if not torch.is_tensor(verts) or verts.device != f.device or verts.dim() != 2 or verts.shape[1] != 3:
+        raise L.TvrError(f"{what} takes verts [V, 3] on the faces' device ({f.device})")
+    return verts.detach().to(torch.float32).contiguous(), f
+
+
+def build_bvh(verts: torch.Tensor, faces: torch.Tensor, stats: dict = None) -> MeshBVH:
+    """A bounding-volume hierarchy over the triangles of an indexed mesh, on the device: what cast_rays and ambient_occlusion walk.
+
+    One 64-bit key per triangle (Morton code of the centroid, triangle index) from tvr_mesh_bvh_keys, sorted with torch.sort on the device (plumbing: the keys are
+    unique, every correct sort gives the same order), then tvr_mesh_bvh_build: Karras' topology from the sorted keys, exact boxes, a refit in kernel-separated passes.
+    The blob is a function of (verts, faces) alone — the same bytes on every run.  A triangle with a non-finite vertex is kept out of every box and is never hit.
+    A face index outside the vertices raises TvrError.  No CPU fallback.  `stats` (a dict) receives triangles_skipped / height / internal_nodes / blob_bytes."""
+    v, f = _mesh_on_device(verts, faces, "build_bvh")
+    V, F, dev, lib = int(v.shape[0]), int(f.shape[0]), f.device, L.lib()
+    nblob, nscratch = lib.tvr_mesh_bvh_bytes(F), lib.tvr_mesh_bvh_scratch_bytes(F)
+    if nblob == 0 or nscratch == 0:
+        raise L.TvrError("build_bvh: " + lib.tvr_last_error().decode(errors="replace"))
+    blob = L.dev_bytes(nblob, dev, what="mesh bvh blob")
+    scratch = L.dev_bytes(nscratch, dev, what="mesh bvh scratch")
+    keys = L.dev_empty((F,), torch.int64, dev, what="mesh bvh keys")
+    counts = L.dev_empty((4,), torch.int32, dev, what="mesh bvh build counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh bvh fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_bvh_keys(_ptr(v), V, _ptr(f), F, _ptr(keys), L.nbytes(keys), scratch.data_ptr(), L.nbytes(scratch), flag.data_ptr(), _stream_ptr(dev)),
+            "tvr_mesh_bvh_keys")
+    ordered = torch.sort(keys)[0].contiguous()               # keys stay below 2^62: the signed order is the unsigned one
+    L.check(lib.tvr_mesh_bvh_build(_ptr(v), V, _ptr(f), F, _ptr(ordered), blob.data_ptr(), L.nbytes(blob), scratch.data_ptr(), L.nbytes(scratch), counts.data_ptr(),
+                                   flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_bvh_build")
+    if int(flag.item()) != 0:
+        raise L.TvrError(f"tvr_mesh_bvh_build raised its fault flag: a face index lies outside 0 .. {V - 1}, or the keys were not sorted (include/tvr.h)")
+    skipped, height, internal, _ = (int(x) for x in counts.cpu().tolist())
+    if stats is not None:
+        stats.update(triangles_skipped=skipped, height=height, internal_nodes=internal, blob_bytes=int(nblob))
+    return MeshBVH(blob, v, f, height, skipped)
+
+
+def _bvh_arg(bvh, what: str) -> MeshBVH:
+    if not isinstance(bvh, MeshBVH):
+        raise L.TvrError(f"{what} takes the MeshBVH that build_bvh returns; got {type(bvh).__name__}")
+    return bvh
+
+
+def _rays_on_device(x, dev, what: str, name: str) -> torch.Tensor:
+    if not torch.is_tensor(x) or x.device.type != "cuda":
+        where = x.device if torch.is_tensor(x) else type(x).__name__
+        raise L.TvrError(f"{what} runs on an MI355X (HIP) device only; {name} is on {where}. There is no CPU fallback.")
+    if x.device != dev:
+        raise L.TvrError(f"{what}: {name} is on {x.device}, the hierarchy on {dev}")
+    return x.detach().to(torch.float32)
+
+
+def cast_rays(bvh: MeshBVH, rays_or_origins, dirs=None, t_min: float = 0.0, t_max: float = float("inf"), any_hit: bool = False, cull: bool = False, stats: dict = None):
+    """What rays hit on a mesh -> (t [N] float32, tri [N] int32, bary [N,3] float32), or with any_hit=True -> hit [N] uint8.
+
+    rays_or_origins is [N,6] rows (origin, direction) as rays.py makes them, or origins [N,3] beside dirs [N,3].  A direction need not be unit length; t is parametric
+    (the hit point is o + t d) and a hit needs t_min < t <= t_max.  Closest hit: the smallest t, ties to the smaller triangle index; +inf / -1 / zeros on a miss; bary
+    are the hit's barycentric weights.  Any hit: 1 iff some triangle is hit (it returns at the first one found).  cull drops triangles whose outward side (right-hand
+    rule) faces away from the ray.  A (ray, triangle) pair is judged by the rasteriser's expressions (include/tvr.h): a ray across an edge two triangles share belongs
+    to exactly one of them; nothing is promised for a ray exactly through a vertex.  A ray with a non-finite component or a zero direction never hits.  Results do not
+    depend on the order or batching of the rays.  No CPU fallback.  `stats` (a dict) receives rays_hit / rays_refused / node_tests / triangle_tests."""
+    b = _bvh_arg(bvh, "cast_rays")
+    dev = b.device
+    r = _rays_on_device(rays_or_origins, dev, "cast_rays", "rays_or_origins")
+    if dirs is None:
+        if r.dim() != 2 or r.shape[1] != 6:
+            raise L.TvrError(f"cast_rays takes rays [N, 6], or origins [N, 3] and dirs [N, 3]; got {tuple(r.shape)} and no dirs")
+        o, d = r[:, :3].contiguous(), r[:, 3:].contiguous()
+    else:
+        d = _rays_on_device(dirs, dev, "cast_rays", "dirs")
+        if r.dim() != 2 or r.shape[1] != 3 or d.shape != r.shape:
+            raise L.TvrError(f"cast_rays takes rays [N, 6], or origins [N, 3] and dirs [N, 3]; got {tuple(r.shape)} and {tuple(d.shape)}")
+        o, d = r.contiguous(), d.contiguous()
+    N, lib = int(o.shape[0]), L.lib()
+    hit = L.dev_empty((N,), torch.uint8, dev, what="mesh bvh hit") if any_hit else None
+    t = None if any_hit else L.dev_empty((N,), torch.float32, dev, what="mesh bvh t")
+    tri = None if any_hit else L.dev_empty((N,), torch.int32, dev, what="mesh bvh tri")
+    bary = None if any_hit else L.dev_empty((N, 3), torch.float32, dev, what="mesh bvh bary")
+    counts = L.dev_empty((4,), torch.int64, dev, what="mesh bvh cast counts")
+    total = torch.zeros(4, dtype=torch.int64, device=dev)
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh bvh fault flag").view(torch.int32)
+    for i0 in range(0, max(N, 1), BVH_CAST_CHUNK):
+        n = min(BVH_CAST_CHUNK, N - i0)
+        oc, dc = o[i0:i0 + n], d[i0:i0 + n]
+        outs = []                                                    # (pointer, bytes) of this chunk's rows of t, tri, bary, hit; (NULL, 0) for the other mode's
+        for x in (t, tri, bary, hit):
+            rows = None if x is None else x[i0:i0 + n]
+            outs += [None, 0] if rows is None else [_ptr(rows), L.nbytes(rows)]
+        L.check(lib.tvr_mesh_bvh_cast(_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), _ptr(oc), _ptr(dc), n, float(t_min),
+                                      float(t_max), 1 if any_hit else 0, 1 if cull else 0, *outs, counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)),
+                "tvr_mesh_bvh_cast")
+        total += counts
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_bvh_cast raised its fault flag: the blob does not belong to this mesh, or a face index lies outside the vertices (include/tvr.h)")
+    if stats is not None:
+        h, r_, nt, tt = (int(x) for x in total.cpu().tolist())
+        stats.update(rays_hit=h, rays_refused=r_, node_tests=nt, triangle_tests=tt)
+    return hit if any_hit else (t, tri, bary)
+
+
+def fibonacci_sphere(K: int) -> torch.Tensor:
+    """The default direction table of ambient_occlusion: K unit vectors spread over the sphere, float32 [K,3] on the host, computed in float64:
+    z_k = 1 - (2k + 1) / K, azimuth 2 pi frac(k * 0.6180339887498949), (x, y) = sqrt(1 - z^2) (cos, sin)."""
+    K = int(K)
+    if K < 1 or K > BVH_MAX_DIRS:
+        raise ValueError(f"fibonacci_sphere takes 1 .. {BVH_MAX_DIRS} directions; got {K}")
+    k = np.arange(K, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / K
+    phi = 2.0 * np.pi * np.modf(k * 0.6180339887498949)[0]
+    s = np.sqrt(np.maximum(1.0 - z * z, 0.0))
+    return torch.from_numpy(np.stack((s * np.cos(phi), s * np.sin(phi), z), -1).astype(np.float32))
+
+
+def ambient_occlusion(bvh: MeshBVH, normals, n_dirs: int = 64, bias: float = 1e-3, t_max: float = float("inf"), points=None, dirs=None, stats: dict = None) -> torch.Tensor:
+    """Cosine-weighted openness in [0, 1] of points on a mesh -> [M] float32 on the device: 1 = nothing in sight, 0 = every direction blocked.
+
+    points [M,3] (default: the mesh's vertices) with normals [M,3]; dirs [K,3] a direction table (default: fibonacci_sphere(n_dirs)).  Per point and table entry the
+    direction is flipped into the normal's hemisphere, weighted by its cosine w = d . n, and an any-hit ray runs from p + bias n over (0, t_max];
+    the result is sum(w * visible) / sum(w), summed in table order (include/tvr.h tvr_mesh_bvh_occlusion), 1 where the normal is zero or non-finite.  bias is in the
+    mesh's units (the default suits a mesh of unit size).  Two runs give the same bits.  No CPU fallback.  `stats` as for cast_rays, per ray."""
+    b = _bvh_arg(bvh, "ambient_occlusion")
+    dev = b.device
+    n = _rays_on_device(normals, dev, "ambient_occlusion", "normals").contiguous()
+    p = b.verts if points is None else _rays_on_device(points, dev, "ambient_occlusion", "points").contiguous()
+    if p.dim() != 2 or p.shape[1] != 3 or n.shape != p.shape:
+        raise L.TvrError(f"ambient_occlusion takes points [M, 3] and normals [M, 3]; got {tuple(p.shape)} and {tuple(n.shape)}")
+    table = fibonacci_sphere(n_dirs) if dirs is None else dirs
+    if not torch.is_tensor(table) or table.dim() != 2 or table.shape[1] != 3:
+        raise L.TvrError("ambient_occlusion takes dirs [K, 3]")
+    table = table.detach().to(device=dev, dtype=torch.float32).contiguous()
+    M, K = int(p.shape[0]), int(table.shape[0])
+    out = L.dev_empty((M,), torch.float32, dev, what="mesh bvh occlusion")
+    counts = L.dev_empty((4,), torch.int64, dev, what="mesh bvh occlusion counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh bvh fault flag").view(torch.int32)
+    L.check(L.lib().tvr_mesh_bvh_occlusion(_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), _ptr(p), _ptr(n), M, _ptr(table),
+                                           K, float(bias), float(t_max), _ptr(out), L.nbytes(out), counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)),
+            "tvr_mesh_bvh_occlusion")
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_bvh_occlusion raised its fault flag: the blob does not belong to this mesh, or a face index lies outside the vertices (include/tvr.h)")
+    if stats is not None:
+        h, r_, nt, tt = (int(x) for x in counts.cpu().tolist())
+        stats.update(rays_hit=h, rays_refused=r_, node_tests=nt, triangle_tests=tt)
+    return out

@@ -97,6 +97,10 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # texture the mesh (TensorBase.bake_texture): the patch side P in texels (5 .. 64) of a per-triangle atlas baked from the field after every other step; writes
     # <ckpt minus .th>.obj / .mtl / .png beside the PLY; 0 = off
     p.add_argument("--mesh_texture", type=int, default=0)
+    # shade the mesh by ambient occlusion (mesh.build_bvh / mesh.ambient_occlusion): K directions per vertex after every geometry step, the grey round(255 * AO) written as
+    # the PLY's red green blue (--render_mesh 1 then draws it as vertex colours); --mesh_ao_radius R ends the rays after R export voxels (0 = unlimited); 0 = off
+    p.add_argument("--mesh_ao", type=int, default=0)
+    p.add_argument("--mesh_ao_radius", type=float, default=0.0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     # (not a reference option) views of an exported mesh beside the rendered test views (mesh.render_mesh): with --render_only 1 --render_test 1, read --mesh_file
@@ -257,7 +261,9 @@ def export_mesh(args, device="cuda"):
                                        colors=bool(getattr(args, "mesh_colors", 0)), min_component_faces=int(getattr(args, "mesh_min_faces", 0)),
                                        keep_largest=int(getattr(args, "mesh_keep_largest", 0)), simplify=float(getattr(args, "mesh_simplify", 0.0)),
                                        smooth=int(getattr(args, "mesh_smooth", 0)), refine=int(getattr(args, "mesh_refine", 0)),
-                                       **({"texture": int(args.mesh_texture)} if getattr(args, "mesh_texture", 0) else {}))
+                                       **({"texture": int(args.mesh_texture)} if getattr(args, "mesh_texture", 0) else {}),
+                                       **({"ao": int(args.mesh_ao), "ao_radius": float(args.mesh_ao_radius) if getattr(args, "mesh_ao_radius", 0.0) else None}
+                                          if getattr(args, "mesh_ao", 0) else {}))
     st = getattr(tensorf, "mesh_export_stats", None) or {}
     dropped = f"; dropped {st['components'] - st['components_kept']} of {st['components']} components, {st['triangles_dropped']} triangles" if "components" in st else ""
     merged = f"; simplified from {st['vertices_in']} vertices, {st['triangles_in']} triangles" if "triangles_in" in st else ""
@@ -267,7 +273,8 @@ def export_mesh(args, device="cuda"):
         f"{st['refine_residual_median_before']:.3g} -> {st['refine_residual_median_after']:.3g}" if "refine_iterations" in st else ""
     textured = f"; textured at {st['atlas_patch']} texels per patch side, atlas {st['atlas_width']} x {st['atlas_height']} in {path[:-4]}.obj / .mtl / .png" \
         if "atlas_patch" in st else ""
-    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles{dropped}{merged}{smoothed}{refined}{textured})")
+    shaded = f"; ambient occlusion from {st['ao_directions']} directions, mean openness {st['ao_mean']:.3f}" if st.get("ao_mean") is not None else ""
+    print(f"saving mesh to {path} ({verts.shape[0]} vertices, {faces.shape[0]} triangles{dropped}{merged}{smoothed}{refined}{textured}{shaded})")
     return path
 
 
