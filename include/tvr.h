@@ -995,6 +995,43 @@ int tvr_mesh_bvh_occlusion(const float *verts, int64_t n_vertices, const int32_t
                            const float *normals, int64_t n_points, const float *dirs, int32_t n_dirs, float bias, float t_max, float *out, size_t out_bytes,
                            int64_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
 
+/* The closest point of a mesh to arbitrary points, on the hierarchy above (csrc/tvr_mesh_bvh.hip; mesh.closest_points / mesh_distance).  An ADDITIVE export: TVR_VERSION
+ * is unchanged.  DESIGN.md §4.18.  points [n_points][3] fp32; dist [n_points], tri [n_points], bary [n_points][3].  All arithmetic is fp32, every operation rounded on
+ * its own (no fused multiply-add), in exactly the order written; divisions and the square root are IEEE correctly rounded; u . v = (u.x * v.x + u.y * v.y) + u.z * v.z.
+ * (POINT p, TRIANGLE): translate first, a = v0 - p, b = v1 - p, c = v2 - p (every error is then relative to the distance, not to the coordinates); a pair with a
+ *   non-finite component of a, b or c is no candidate.  The point of the triangle closest to the origin by the Voronoi regions (Ericson, Real-Time Collision Detection
+ *   §5.1.5):  ab = b - a, ac = c - a, bc = c - b;  d1 = -(ab . a), d2 = -(ac . a), d3 = -(ab . b), d4 = -(ac . b), d5 = -(ab . c), d6 = -(ac . c);
+ *   n = ab x ac;  va = (b x bc) . n, vb = (ac x a) . n, vc = (a x ab) . n, with u x v = (u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x).
+ *   (In exact arithmetic these are Ericson's d3 * d6 - d5 * d4, d5 * d2 - d1 * d6, d1 * d4 - d3 * d2; as triple products their error grows with a triangle's aspect
+ *   ratio, not with its square — marching cubes makes slivers.)  The regions in this FIXED order, the first that holds gives the closest point x (per axis) and the
+ *   weights (w0, w1, w2):
+ *     1 vertex A  d1 <= 0 and d2 <= 0                          x = a                          (1, 0, 0)
+ *     2 vertex B  d3 >= 0 and d4 <= d3                         x = b                          (0, 1, 0)
+ *     3 edge AB   vc <= 0 and d1 >= 0 and d3 <= 0              v = d1 / (d1 - d3)             x = a + v * ab                 (1 - v, v, 0)
+ *     4 vertex C  d6 >= 0 and d5 <= d6                         x = c                          (0, 0, 1)
+ *     5 edge AC   vb <= 0 and d2 >= 0 and d6 <= 0              w = d2 / (d2 - d6)             x = a + w * ac                 (1 - w, 0, w)
+ *     6 edge BC   va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    w = (d4 - d3) / ((d4 - d3) + (d5 - d6))    x = b + w * bc         (0, 1 - w, w)
+ *     7 face      otherwise    den = (va + vb) + vc, v = vb / den, w = vc / den                x = (a + v * ab) + w * ac      ((1 - v) - w, v, w)
+ *   D = x . x.  A pair whose D is not finite (NaN: a zero-area triangle that reaches region 7; +inf: an overflow) is no candidate.
+ * RESULT: the candidate with the smallest D, ties going to the smaller triangle index, provided D <= max_dist * max_dist (one fp32 product; max_dist = +inf is allowed):
+ *   dist = sqrt(D), tri, bary = (w0, w1, w2).  Otherwise, and for an empty tree: dist = +inf, tri = -1, bary = 0.  A point with a non-finite component is refused: the
+ *   same outputs, and it is counted.  A point that IS a vertex of the mesh gets dist == 0.0 exactly and the smallest triangle index of that vertex's fan (regions 1, 2, 4
+ *   return the translated vertex, which is 0; at corner C, vc is a sum of squares and region 3 does not hold).  A triangle with a non-finite vertex is never named (the build keeps it out of every box).  Results do not depend on the
+ *   order or the batching of the points; two runs are bit-equal.
+ * TRAVERSAL: the cast's — one lane per point, the 64-entry stack per lane in LDS, 128-lane workgroups, the child with the smaller lower bound first and the other pushed,
+ *   a guarded push, a step budget of 2F - 1, a popped node tested again.  A node is skipped only if the lower bound of its box is STRICTLY greater than the best D so far
+ *   (max_dist * max_dist before any candidate; strictly: an equal D may still win on the index).  The lower bound: l = lo - p, h = hi - p per axis; m = the largest of
+ *   |l|, |h| over the axes; pad = m * 2^-15; g = max(max(l - pad, -(h + pad)), 0) per axis; bound = g . g — the squared distance to the box with every face moved outwards
+ *   by pad.  As for the casts, a stated margin for the rounding of D, not a proof; what is tested is bit-equality with a brute-force restatement of the definition.
+ *   counts_dev (int64[4], may be NULL; zeroed by the call): {points answered, points refused, node tests, triangle tests}.  Index and blob checks as for the casts.
+ * Errors, all before any launch: TVR_ERR_INVALID for a NULL pointer where data is due, a negative count, a misaligned blob, a NaN or negative max_dist;
+ *   TVR_ERR_UNSUPPORTED for n_vertices or n_points >= 2^31 and n_triangles above TVR_MESH_BVH_MAX_TRIANGLES; TVR_ERR_SCRATCH for an undersized blob or output.
+ *   n_points == 0 and n_triangles == 0 are valid.
+ * NOT built: a sign (it needs angle-weighted pseudo-normals at edges and vertices), k nearest, refitting a tree after its vertices moved. */
+int tvr_mesh_bvh_nearest(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const float *points,
+                         int64_t n_points, float max_dist, float *dist, size_t dist_bytes, int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes,
+                         int64_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2514,3 +2514,24 @@ int tvr_mesh_bvh_occlusion(const float *verts, int64_t n_vertices, const int32_t
                                       (unsigned long long *)counts_dev, fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+int tvr_mesh_bvh_nearest(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const float *points,
+                         int64_t n_points, float max_dist, float *dist, size_t dist_bytes, int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes,
+                         int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_points < 0) return fail(TVR_ERR_INVALID, "%s: n_points = %lld is negative", __func__, (long long)n_points);
+    if (n_points > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_points = %lld: at most 2^31 - 1 points per call", __func__, (long long)n_points);
+    if (std::isnan(max_dist) || max_dist < 0.0f) return fail(TVR_ERR_INVALID, "%s: max_dist = %g is NaN or negative", __func__, (double)max_dist);
+    rc = bvh_buffer(__func__, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+    if (rc != TVR_OK) return rc;
+    if (n_points > 0 && (!points || !dist || !tri || !bary)) return fail(TVR_ERR_INVALID, "%s: points / dist / tri / bary is NULL with %lld points", __func__, (long long)n_points);
+    NEED("dist [n_points]", dist_bytes, n_points, 1);
+    NEED("tri [n_points]", tri_bytes, n_points, 1);
+    NEED("bary [n_points,3]", bary_bytes, n_points, 3);
+    HIP_TRY(launch_mesh_bvh_nearest(verts, n_vertices, faces, n_triangles, bvh, points, n_points, max_dist, dist, tri, bary, (unsigned long long *)counts_dev,
+                                    fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

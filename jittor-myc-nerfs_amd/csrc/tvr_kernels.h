@@ -304,6 +304,8 @@ hipError_t launch_mesh_bvh_build(const float *verts, long long n_vertices, const
 hipError_t launch_mesh_bvh_cast(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *origins, const float *dirs,
                                 long long n_rays, float t_min, float t_max, int any_hit, int cull, float *t, int *tri, float *bary, unsigned char *hit,
                                 unsigned long long *counts, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_bvh_nearest(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *points,
+                                   long long n_points, float max_dist, float *dist, int *tri, float *bary, unsigned long long *counts, unsigned *fault, hipStream_t stream);
 hipError_t launch_mesh_bvh_occlusion(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *points,
                                      const float *normals, long long n_points, const float *dirs, int n_dirs, float bias, float t_max, float *out, unsigned long long *counts,
                                      unsigned *fault, hipStream_t stream);

@@ -9,6 +9,8 @@
 //   build    check (keys strictly ascending, codes below 2^30, every triangle exactly once, face indices inside 0 .. V-1), leaves (exact min / max boxes in key order),
 //            topology (Karras 2012: every internal node finds its range and split from the sorted keys alone), 62 refit passes, finish (header, counts, root check)
 //   cast     one lane per ray, a 64-entry stack per lane in LDS, nearer child first; occlusion: one lane per point, its K rays in table order
+//   nearest  the closest point of the mesh to a point (mesh.closest_points / mesh_distance): the cast's walk with the boxes ordered and pruned by a
+//            padded lower bound of their squared distance; a (point, triangle) pair by Ericson's regions in the frame translated to the point
 //
 // REFIT.  No workgroup hands data to another inside a launch.  `pass` [F-1] holds, per internal node, the number of the launch that computed its box (0 = not yet; leaves
 // count as pass 1).  Launch p = 2 .. 63 computes a node iff it has no box and both children carry a pass number in 1 .. p-1, i.e. were finished by an EARLIER launch:
@@ -505,6 +507,163 @@ __global__ __launch_bounds__(BV_CAST_THREADS) void bv_cast_kernel(BvTree T, cons
     bv_count(counts, hit, refused, node_tests, tri_tests);
 }
 
+// ---- closest point (tvr_mesh_bvh_nearest) ------------------------------------------------------------------------------------------------------------------
+struct BvNear {
+    float D;                                         // the bound: max_dist^2 before a candidate, the best squared distance after
+    unsigned tri;                                    // 0xffffffff before a candidate
+    float w0, w1, w2;
+};
+
+// A lower bound of the squared distance from p to box b, every face of the box moved outwards by BV_PAD x the largest distance, along an axis, from p to the box.
+// false for an empty box (lo = +inf, hi = -inf) and for a bound STRICTLY above `best` (an equal D may still win on the index).
+__device__ __forceinline__ bool bv_near_box(const float *__restrict__ b, float px, float py, float pz, float best, float &lb)
+{
+    const float lx = b[0] - px, ly = b[1] - py, lz = b[2] - pz, hx = b[3] - px, hy = b[4] - py, hz = b[5] - pz;
+    const float m = fmaxf(fmaxf(fmaxf(fabsf(lx), fabsf(hx)), fmaxf(fabsf(ly), fabsf(hy))), fmaxf(fabsf(lz), fabsf(hz)));
+    const float pad = m * BV_PAD;
+    const float gx = fmaxf(fmaxf(lx - pad, -(hx + pad)), 0.0f), gy = fmaxf(fmaxf(ly - pad, -(hy + pad)), 0.0f), gz = fmaxf(fmaxf(lz - pad, -(hz + pad)), 0.0f);
+    lb = bv_dot(gx, gy, gz, gx, gy, gz);
+    return !(lb > best) && lx <= hx;
+}
+
+// (point, triangle t): the definition of include/tvr.h tvr_mesh_bvh_nearest — Ericson's regions in the frame translated to p.  false when D is not finite.
+__device__ __forceinline__ bool bv_near_triangle(const BvTree &T, unsigned t, float px, float py, float pz, float &D, float w[3], unsigned *__restrict__ fault)
+{
+    const int *f = T.faces + (size_t)t * 3;
+    const int v0 = f[0], v1 = f[1], v2 = f[2];
+    if ((unsigned)v0 >= T.V || (unsigned)v1 >= T.V || (unsigned)v2 >= T.V) {
+        *fault = 1u;
+        return false;
+    }
+    const float *p0 = T.verts + (size_t)v0 * 3, *p1 = T.verts + (size_t)v1 * 3, *p2 = T.verts + (size_t)v2 * 3;
+    const float ax = p0[0] - px, ay = p0[1] - py, az = p0[2] - pz;
+    const float bx = p1[0] - px, by = p1[1] - py, bz = p1[2] - pz;
+    const float cx = p2[0] - px, cy = p2[1] - py, cz = p2[2] - pz;
+    const bool finite = bv_finite(ax) && bv_finite(ay) && bv_finite(az) && bv_finite(bx) && bv_finite(by) && bv_finite(bz) && bv_finite(cx) && bv_finite(cy) && bv_finite(cz);
+    if (!finite) return false;
+    const float abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
+    const float d1 = -bv_dot(abx, aby, abz, ax, ay, az), d2 = -bv_dot(acx, acy, acz, ax, ay, az);
+    const float d3 = -bv_dot(abx, aby, abz, bx, by, bz), d4 = -bv_dot(acx, acy, acz, bx, by, bz);
+    const float d5 = -bv_dot(abx, aby, abz, cx, cy, cz), d6 = -bv_dot(acx, acy, acz, cx, cy, cz);
+    // va, vb, vc: the triple products of the corners with the normal — Ericson's d-products in exact arithmetic, without their cancellation on thin triangles
+    const float bcx = cx - bx, bcy = cy - by, bcz = cz - bz;
+    const float nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+    const float va = bv_dot(by * bcz - bz * bcy, bz * bcx - bx * bcz, bx * bcy - by * bcx, nx, ny, nz);            // (b x bc) . n
+    const float vb = bv_dot(acy * az - acz * ay, acz * ax - acx * az, acx * ay - acy * ax, nx, ny, nz);            // (ac x a) . n
+    const float vc = bv_dot(ay * abz - az * aby, az * abx - ax * abz, ax * aby - ay * abx, nx, ny, nz);            // (a x ab) . n
+    float x, y, z;
+    if (d1 <= 0.0f && d2 <= 0.0f) {                                  // 1: vertex A
+        x = ax; y = ay; z = az;
+        w[0] = 1.0f; w[1] = 0.0f; w[2] = 0.0f;
+    } else if (d3 >= 0.0f && d4 <= d3) {                             // 2: vertex B
+        x = bx; y = by; z = bz;
+        w[0] = 0.0f; w[1] = 1.0f; w[2] = 0.0f;
+    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {             // 3: edge AB
+        const float v = d1 / (d1 - d3);
+        x = ax + v * abx; y = ay + v * aby; z = az + v * abz;
+        w[0] = 1.0f - v; w[1] = v; w[2] = 0.0f;
+    } else if (d6 >= 0.0f && d5 <= d6) {                             // 4: vertex C
+        x = cx; y = cy; z = cz;
+        w[0] = 0.0f; w[1] = 0.0f; w[2] = 1.0f;
+    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {             // 5: edge AC
+        const float u = d2 / (d2 - d6);
+        x = ax + u * acx; y = ay + u * acy; z = az + u * acz;
+        w[0] = 1.0f - u; w[1] = 0.0f; w[2] = u;
+    } else if (va <= 0.0f && d4 - d3 >= 0.0f && d5 - d6 >= 0.0f) {   // 6: edge BC
+        const float u = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        x = bx + u * bcx; y = by + u * bcy; z = bz + u * bcz;
+        w[0] = 0.0f; w[1] = 1.0f - u; w[2] = u;
+    } else {                                                         // 7: the face
+        const float den = (va + vb) + vc, v = vb / den, u = vc / den;
+        x = (ax + v * abx) + u * acx; y = (ay + v * aby) + u * acy; z = (az + v * abz) + u * acz;
+        w[0] = (1.0f - v) - u; w[1] = v; w[2] = u;
+    }
+    D = bv_dot(x, y, z, x, y, z);
+    return bv_finite(D);                                             // (a NaN is not finite: a zero-area triangle in region 7)
+}
+
+// Walk the tree for one point.  H.D holds max_dist^2 on entry.  The shape of bv_walk: the nearer box first, the other pushed, a popped node tested again.
+__device__ __forceinline__ void bv_near_walk(const BvTree &T, float px, float py, float pz, BvNear &H, unsigned *stack, unsigned stride, unsigned &node_tests,
+                                             unsigned &tri_tests, unsigned *__restrict__ fault)
+{
+    if (T.F == 0) return;
+    const unsigned n_nodes = 2u * T.F - 1u, first_leaf = T.F - 1u;
+    unsigned sp = 0, node = 0;
+    float lb;
+    ++node_tests;
+    if (!bv_near_box(T.box, px, py, pz, H.D, lb)) return;
+    for (unsigned budget = n_nodes;; --budget) {
+        if (budget == 0u) {                                          // a tree visits every node at most once: a blob with a cycle in it ends here
+            *fault = 1u;
+            return;
+        }
+        bool pop = true;
+        if (node >= first_leaf) {
+            const unsigned t = (unsigned)T.leaf_tri[node - first_leaf];
+            if (t < T.F) {
+                float w[3], D;
+                ++tri_tests;
+                if (bv_near_triangle(T, t, px, py, pz, D, w, fault) && (D < H.D || (D == H.D && t < H.tri))) {
+                    H.D = D; H.tri = t; H.w0 = w[0]; H.w1 = w[1]; H.w2 = w[2];
+                }
+            } else
+                *fault = 1u;
+        } else {
+            const unsigned a = (unsigned)T.child[(size_t)node * 2], b = (unsigned)T.child[(size_t)node * 2 + 1];
+            if (a < n_nodes && b < n_nodes) {
+                float la, lbb;
+                node_tests += 2;
+                const bool ha = bv_near_box(T.box + (size_t)a * 6, px, py, pz, H.D, la), hb = bv_near_box(T.box + (size_t)b * 6, px, py, pz, H.D, lbb);
+                if (ha && hb) {
+                    const bool a_first = la <= lbb;                  // the nearer child first, the farther one waits: at most one entry per level
+                    const unsigned far_ = a_first ? b : a;
+                    node = a_first ? a : b;
+                    if (sp < BV_STACK) stack[(sp++) * stride] = far_;
+                    else *fault = 1u;                                // (never: the height is at most 62)
+                    pop = false;
+                } else if (ha || hb) {
+                    node = ha ? a : b;
+                    pop = false;
+                }
+            } else
+                *fault = 1u;
+        }
+        while (pop) {
+            if (sp == 0) return;
+            node = stack[(--sp) * stride];
+            if (node >= n_nodes) { *fault = 1u; continue; }
+            ++node_tests;
+            pop = !bv_near_box(T.box + (size_t)node * 6, px, py, pz, H.D, lb);      // the bound may have dropped since the push
+        }
+    }
+}
+
+__global__ __launch_bounds__(BV_CAST_THREADS) void bv_nearest_kernel(BvTree T, const float *__restrict__ points, unsigned N, float max_sq, float *__restrict__ dist_out,
+                                                                     int *__restrict__ tri_out, float *__restrict__ bary_out, unsigned long long *__restrict__ counts,
+                                                                     unsigned *__restrict__ fault)
+{
+    __shared__ unsigned stack[BV_STACK * BV_CAST_THREADS];            // entry e of lane l at [e * BV_CAST_THREADS + l]
+    const bool ok = bv_blob_ok(T, fault);
+    const unsigned i = blockIdx.x * BV_CAST_THREADS + threadIdx.x;
+    bool answered = false, refused = false;
+    unsigned node_tests = 0, tri_tests = 0;
+    if (i < N) {
+        const float *p = points + (size_t)i * 3;
+        const float px = p[0], py = p[1], pz = p[2];
+        BvNear H;
+        H.D = max_sq; H.tri = 0xffffffffu; H.w0 = H.w1 = H.w2 = 0.0f;
+        refused = !(bv_finite(px) && bv_finite(py) && bv_finite(pz));
+        if (ok && !refused) bv_near_walk(T, px, py, pz, H, stack + threadIdx.x, BV_CAST_THREADS, node_tests, tri_tests, fault);
+        answered = H.tri != 0xffffffffu;
+        dist_out[i] = answered ? sqrtf(H.D) : __uint_as_float(0x7f800000u);
+        tri_out[i] = answered ? (int)H.tri : -1;
+        bary_out[(size_t)i * 3 + 0] = answered ? H.w0 : 0.0f;
+        bary_out[(size_t)i * 3 + 1] = answered ? H.w1 : 0.0f;
+        bary_out[(size_t)i * 3 + 2] = answered ? H.w2 : 0.0f;
+    }
+    bv_count(counts, answered, refused, node_tests, tri_tests);
+}
+
 __global__ __launch_bounds__(BV_CAST_THREADS) void bv_occlusion_kernel(BvTree T, const float *__restrict__ points, const float *__restrict__ normals, unsigned M,
                                                                        const float *__restrict__ dirs, unsigned K, float bias, float t_max, float *__restrict__ out,
                                                                        unsigned long long *__restrict__ counts, unsigned *__restrict__ fault)
@@ -582,5 +741,20 @@ hipError_t launch_mesh_bvh_occlusion(const float *verts, long long V, const int 
     const BvTree T = bv_tree(verts, V, faces, F, const_cast<void *>(bvh));
     const unsigned nb = (unsigned)((M + BV_CAST_THREADS - 1) / BV_CAST_THREADS);
     hipLaunchKernelGGL(bv_occlusion_kernel, dim3(nb), dim3(BV_CAST_THREADS), 0, stream, T, points, normals, (unsigned)M, dirs, (unsigned)K, bias, t_max, out, counts, fault);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_bvh_nearest(const float *verts, long long V, const int *faces, long long F, const void *bvh, const float *points, long long N, float max_dist,
+                                   float *dist, int *tri, float *bary, unsigned long long *counts, unsigned *fault, hipStream_t stream)
+{
+    if (counts) {
+        hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), stream);
+        if (e != hipSuccess) return e;
+    }
+    if (N <= 0) return hipSuccess;
+    const BvTree T = bv_tree(verts, V, faces, F, const_cast<void *>(bvh));
+    const unsigned nb = (unsigned)((N + BV_CAST_THREADS - 1) / BV_CAST_THREADS);
+    const float max_sq = max_dist * max_dist;                        // fp32, rounded once (+inf for +inf or an overflow)
+    hipLaunchKernelGGL(bv_nearest_kernel, dim3(nb), dim3(BV_CAST_THREADS), 0, stream, T, points, (unsigned)N, max_sq, dist, tri, bary, counts, fault);
     return hipGetLastError();
 }

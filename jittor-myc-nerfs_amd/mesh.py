@@ -1003,3 +1003,150 @@ def ambient_occlusion(bvh: MeshBVH, normals, n_dirs: int = 64, bias: float = 1e-
         h, r_, nt, tt = (int(x) for x in counts.cpu().tolist())
         stats.update(rays_hit=h, rays_refused=r_, node_tests=nt, triangle_tests=tt)
     return out
+
+
+# ---- closest points and the distance between two meshes (csrc/tvr_mesh_bvh.hip bv_nearest_kernel, include/tvr.h tvr_mesh_bvh_nearest) -----------------------
+BVH_NEAREST_CHUNK = 1 << 24     # points per tvr_mesh_bvh_nearest call of closest_points (results do not depend on it)
+
+
+def closest_points(bvh: MeshBVH, points, max_dist: float = float("inf"), stats: dict = None):
+    """The closest point of a mesh to every point -> (dist [N] float32, tri [N] int32, bary [N,3] float32) on the device.
+
+    points [N,3] on the hierarchy's device.  dist is the distance to the nearest point of the surface, tri the triangle it lies on (ties in distance go to the smaller
+    index) and bary its weights there: the closest point is sum_k bary_k * v_k of that triangle.  A point farther than max_dist from every triangle, a point with a
+    non-finite component and every point of an empty mesh get +inf / -1 / zeros.  A point that is a vertex of the mesh gets exactly 0.0 and the smallest triangle index
+    of the vertex's fan.  The distance is unsigned.  The pair arithmetic is defined in include/tvr.h (Ericson's regions in the frame translated to the point);
+    results do not depend on the order or batching of the points and two runs give the same bits.  No CPU fallback.  `stats` (a dict) receives points_answered /
+    points_refused / node_tests / triangle_tests."""
+    b = _bvh_arg(bvh, "closest_points")
+    dev = b.device
+    p = _rays_on_device(points, dev, "closest_points", "points")
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise L.TvrError(f"closest_points takes points [N, 3]; got {tuple(p.shape)}")
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise L.TvrError(f"closest_points: max_dist = {max_dist} must be >= 0 (+inf = no limit)")
+    p = p.contiguous()
+    N, lib = int(p.shape[0]), L.lib()
+    dist = L.dev_empty((N,), torch.float32, dev, what="mesh bvh nearest dist")
+    tri = L.dev_empty((N,), torch.int32, dev, what="mesh bvh nearest tri")
+    bary = L.dev_empty((N, 3), torch.float32, dev, what="mesh bvh nearest bary")
+    counts = L.dev_empty((4,), torch.int64, dev, what="mesh bvh nearest counts")
+    total = torch.zeros(4, dtype=torch.int64, device=dev)
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh bvh fault flag").view(torch.int32)
+    for i0 in range(0, max(N, 1), BVH_NEAREST_CHUNK):
+        n = min(BVH_NEAREST_CHUNK, N - i0)
+        pc, dc, tc, bc = p[i0:i0 + n], dist[i0:i0 + n], tri[i0:i0 + n], bary[i0:i0 + n]
+        L.check(lib.tvr_mesh_bvh_nearest(_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), _ptr(pc), n, max_dist, _ptr(dc),
+                                         L.nbytes(dc), _ptr(tc), L.nbytes(tc), _ptr(bc), L.nbytes(bc), counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)),
+                "tvr_mesh_bvh_nearest")
+        total += counts
+    if int(flag.item()) != 0:
+        raise L.TvrError("tvr_mesh_bvh_nearest raised its fault flag: the blob does not belong to this mesh, or a face index lies outside the vertices (include/tvr.h)")
+    if stats is not None:
+        a, r_, nt, tt = (int(x) for x in total.cpu().tolist())
+        stats.update(points_answered=a, points_refused=r_, node_tests=nt, triangle_tests=tt)
+    return dist, tri, bary
+
+
+def subdivision_weights(subdiv: int) -> np.ndarray:
+    """The barycentric weights [n^2, 3] (float64) of the centroids of the n^2 sub-triangles of a triangle's regular n-fold subdivision: first the n (n + 1) / 2 upright
+    ones, rows j = 0 .. n-1 and i = 0 .. n-1-j within a row, at (v, w) = ((3 i + 1) / (3 n), (3 j + 1) / (3 n)); then the n (n - 1) / 2 inverted ones in the same order
+    at ((3 i + 2) / (3 n), (3 j + 2) / (3 n)).  Column 0 is 1 - v - w."""
+    n = int(subdiv)
+    if n < 1 or n > 64:
+        raise ValueError(f"subdiv = {subdiv!r}: the subdivisions per edge, an integer in 1 .. 64")
+    up = [((3 * i + 1) / (3.0 * n), (3 * j + 1) / (3.0 * n)) for j in range(n) for i in range(n - j)]
+    down = [((3 * i + 2) / (3.0 * n), (3 * j + 2) / (3.0 * n)) for j in range(n - 1) for i in range(n - 1 - j)]
+    vw = np.asarray(up + down, np.float64).reshape(-1, 2)
+    return np.concatenate([1.0 - vw.sum(1, keepdims=True), vw], 1)
+
+
+def surface_samples(verts: torch.Tensor, faces: torch.Tensor, subdiv: int = 2):
+    """Points spread over a mesh with the area each stands for -> (points [F n^2 + V, 3] float32, weights [F n^2 + V] float32), on the mesh's device (torch plumbing).
+
+    Per triangle, in face order, the centroids of the n^2 sub-triangles of its regular n-fold subdivision (n = subdiv, subdivision_weights' order), each weighted
+    area / n^2; then the V vertices with weight 0 — they count for a maximum only.  A zero-area triangle, and one with a non-finite vertex, has weight 0.  The output
+    is a function of its arguments alone."""
+    if not torch.is_tensor(verts) or not torch.is_tensor(faces) or verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("surface_samples takes verts [V, 3] and faces [F, 3] tensors")
+    if faces.device != verts.device:
+        raise ValueError(f"surface_samples: the faces are on {faces.device}, the vertices on {verts.device}")
+    bw = torch.from_numpy(subdivision_weights(subdiv).astype(np.float32)).to(verts.device)           # [n^2, 3]
+    v = verts.detach().to(torch.float32)
+    corners = v[faces.detach().long()]                                                               # [F, 3, 3]
+    pts = (bw[None, :, 0, None] * corners[:, None, 0] + bw[None, :, 1, None] * corners[:, None, 1]) + bw[None, :, 2, None] * corners[:, None, 2]
+    area = 0.5 * torch.linalg.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0], dim=-1).norm(dim=-1)
+    area = torch.where(torch.isfinite(area), area, torch.zeros_like(area)) / float(bw.shape[0])
+    weights = torch.cat([area[:, None].expand(-1, bw.shape[0]).reshape(-1), torch.zeros(v.shape[0], dtype=torch.float32, device=v.device)])
+    return torch.cat([pts.reshape(-1, 3), v]).contiguous(), weights.contiguous()
+
+
+def weighted_quantile(dist: torch.Tensor, weights: torch.Tensor, q) -> torch.Tensor:
+    """The smallest distance whose cumulative weight, after a sort by distance, reaches q x the total weight -> one value per entry of q (float64, on dist's device;
+    NaN when the total weight is 0).  Samples of weight 0 never decide a quantile."""
+    d, order = torch.sort(dist.to(torch.float64))
+    cum = torch.cumsum(weights.to(torch.float64)[order], 0)
+    if d.numel() == 0:
+        return torch.full((len(q),), float("nan"), dtype=torch.float64, device=dist.device)
+    target = torch.as_tensor(list(q), dtype=torch.float64, device=dist.device) * cum[-1]
+    idx = torch.searchsorted(cum, target).clamp(max=d.numel() - 1)                                  # the first index whose cumulative weight is >= the target
+    return torch.where(cum[-1] > 0, d[idx], torch.full_like(target, float("nan")))
+
+
+DISTANCE_STATISTICS = ("max", "mean", "rms", "median", "p95", "samples", "refused")
+
+
+def distance_statistics(dist: torch.Tensor, weights: torch.Tensor, unit: float = 1.0) -> torch.Tensor:
+    """DISTANCE_STATISTICS of one direction of mesh_distance -> [7] float64 on dist's device, no host read: dist / unit over the samples that were answered (finite
+    dist); mean and rms weighted by `weights`, median and p95 by weighted_quantile; samples = all, refused = those without an answer."""
+    ok = torch.isfinite(dist)                                        # (masked, not gathered: a boolean gather would read the count back)
+    d = torch.where(ok, dist.to(torch.float64) / float(unit), torch.zeros((), dtype=torch.float64, device=dist.device))
+    w = torch.where(ok, weights.to(torch.float64), torch.zeros((), dtype=torch.float64, device=dist.device))
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dist.device)
+    total = w.sum()
+    mx = torch.where(ok.any(), torch.where(ok, d, -torch.ones_like(d)).max(), nan) if d.numel() else nan
+    mean = torch.where(total > 0, (w * d).sum() / total, nan)
+    rms = torch.where(total > 0, torch.sqrt((w * d * d).sum() / total), nan)
+    qs = weighted_quantile(d, w, (0.5, 0.95))
+    n = torch.tensor([float(dist.numel())], dtype=torch.float64, device=dist.device)
+    return torch.cat([torch.stack([mx, mean, rms, qs[0], qs[1]]), n, n - ok.sum().to(torch.float64)])
+
+
+def mesh_distance(verts_a, faces_a, verts_b, faces_b, subdiv: int = 2, symmetric: bool = True, unit: float = 1.0, bvh_a: MeshBVH = None, bvh_b: MeshBVH = None,
+                  stats: dict = None) -> dict:
+    """How far two meshes are apart -> {"a_to_b": {max, mean, rms, median, p95, samples, refused}, and with symmetric also "b_to_a", "hausdorff", "chamfer"}.
+
+    a_to_b: the distances, divided by `unit`, from surface_samples(A, subdiv) to the surface of B (closest_points on B's hierarchy).  mean and rms are weighted by
+    area; median and p95 are the smallest distance whose cumulative area, after a sort by distance, reaches 0.5 and 0.95 of the total; max is over the samples and the
+    vertices; samples counts the queries, refused those that got no answer (non-finite coordinates, or an empty B) and are left out of the figures.  hausdorff is the
+    larger of the two max, chamfer the mean of the two mean.  Distances are unsigned and one-sided figures are not symmetric: a hole in B does not show in a_to_b.
+    bvh_a / bvh_b: hierarchies built over exactly these meshes (build_bvh), built here when absent (bvh_a is only needed with symmetric).  The statistics are computed
+    on the device and read once.  No CPU fallback.  `stats` (a dict) receives closest_points' counters summed over the directions."""
+    unit = float(unit)
+    if not unit > 0.0 or not np.isfinite(unit):
+        raise ValueError(f"mesh_distance: unit = {unit} must be positive and finite")
+    va, fa = _mesh_on_device(verts_a, faces_a, "mesh_distance")
+    vb, fb = _mesh_on_device(verts_b, faces_b, "mesh_distance")
+    if va.device != vb.device:
+        raise L.TvrError(f"mesh_distance: mesh A is on {va.device}, mesh B on {vb.device}")
+    sides = [("a_to_b", va, fa, _bvh_arg(bvh_b, "mesh_distance") if bvh_b is not None else build_bvh(vb, fb))]
+    if symmetric:
+        sides.append(("b_to_a", vb, fb, _bvh_arg(bvh_a, "mesh_distance") if bvh_a is not None else build_bvh(va, fa)))
+    rows, counters = [], {}
+    for _, v, f, target in sides:
+        pts, w = surface_samples(v, f, subdiv)
+        st = {}
+        rows.append(distance_statistics(closest_points(target, pts, stats=st)[0], w, unit))
+        for k, x in st.items():
+            counters[k] = counters.get(k, 0) + x
+    host = torch.stack(rows).cpu().tolist()                          # the one host read of the figures
+    out = {}
+    for (name, _, _, _), row in zip(sides, host):
+        out[name] = {k: (int(x) if k in ("samples", "refused") else float(x)) for k, x in zip(DISTANCE_STATISTICS, row)}
+    if symmetric:
+        out["hausdorff"] = max(out["a_to_b"]["max"], out["b_to_a"]["max"])
+        out["chamfer"] = 0.5 * (out["a_to_b"]["mean"] + out["b_to_a"]["mean"])
+    if stats is not None:
+        stats.update(counters)
+    return out

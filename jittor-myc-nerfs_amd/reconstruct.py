@@ -101,6 +101,9 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # the PLY's red green blue (--render_mesh 1 then draws it as vertex colours); --mesh_ao_radius R ends the rays after R export voxels (0 = unlimited); 0 = off
     p.add_argument("--mesh_ao", type=int, default=0)
     p.add_argument("--mesh_ao_radius", type=float, default=0.0)
+    # measure how far a mesh is from another (mesh.mesh_distance): REF.ply or REF.obj; with --export_mesh 1 the mesh just written is compared, without it --mesh_file
+    # (no checkpoint needed); writes <mesh minus extension>_distance.json in world units and, when a --ckpt is loaded, in export voxels; unset = off
+    p.add_argument("--mesh_compare", type=str, default=None)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     # (not a reference option) views of an exported mesh beside the rendered test views (mesh.render_mesh): with --render_only 1 --render_test 1, read --mesh_file
@@ -278,7 +281,58 @@ def export_mesh(args, device="cuda"):
     return path
 
 
-FAULT_POLL_EVERY = 16        # iterations between two reads of the training-fault accumulator (field.check_training_faults)
+def _read_mesh_geometry(path):
+    """(verts [V,3] float32, faces [F,3] int32) of a PLY that write_ply wrote or of the OBJ of --mesh_texture (its texture is not read)."""
+    from .mesh import read_ply_attributes
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"--mesh_compare: {path!r} does not exist")
+    if path.endswith(".obj"):
+        verts, faces = [], []
+        with open(path) as f:
+            for line in f:
+                tok = line.split()
+                if tok[:1] == ["v"]:
+                    verts.append([float(x) for x in tok[1:4]])
+                elif tok[:1] == ["f"]:
+                    if len(tok) != 4:
+                        raise ValueError(f"{path}: a face is not a triangle")
+                    faces.append([int(c.split("/")[0]) - 1 for c in tok[1:4]])
+        return np.asarray(verts, np.float32).reshape(-1, 3), np.asarray(faces, np.int32).reshape(-1, 3)
+    return read_ply_attributes(path)[:2]
+
+
+@torch.no_grad()
+def mesh_compare(args, path, device="cuda"):
+    """--mesh_compare REF: mesh.mesh_distance of the mesh at `path` (A) against REF (B), written to <path minus extension>_distance.json — the figures in world units,
+    both file names and the vertex and triangle counts; with a --ckpt also the same figures in export voxels, the unit being the smallest edge of
+    mesh_export_voxel(tensorf, --mesh_grid), which the file records (a mesh file does not say on which grid it was made).  Returns the path of the JSON."""
+    import json
+    from .mesh import build_bvh, mesh_distance
+    ref = args.mesh_compare
+    va, fa = _read_mesh_geometry(path)
+    vb, fb = _read_mesh_geometry(ref)
+    ta, tfa, tb, tfb = (torch.from_numpy(np.ascontiguousarray(x)).to(device) for x in (va, fa, vb, fb))
+    bvh_a, bvh_b = build_bvh(ta, tfa), build_bvh(tb, tfb)
+    report = {"mesh_file": path, "reference_file": ref, "vertices": int(len(va)), "triangles": int(len(fa)), "reference_vertices": int(len(vb)),
+              "reference_triangles": int(len(fb)), "a_is": "mesh_file", "b_is": "reference_file", "subdiv": 2,
+              "world": mesh_distance(ta, tfa, tb, tfb, bvh_a=bvh_a, bvh_b=bvh_b)}
+    if args.ckpt and os.path.exists(args.ckpt):
+        tensorf, _ = _build_from_ckpt(args, load_checkpoint(args.ckpt), device)
+        voxel = mesh_export_voxel(tensorf, getattr(args, "mesh_grid", None))
+        report["voxel"] = [float(x) for x in voxel]
+        report["voxel_unit"] = float(voxel.min())
+        report["voxel_from"] = "--mesh_grid" if getattr(args, "mesh_grid", None) else "the field's gridSize (pass the export's --mesh_grid if it was made on another grid)"
+        report["voxels"] = mesh_distance(ta, tfa, tb, tfb, unit=float(voxel.min()), bvh_a=bvh_a, bvh_b=bvh_b)
+    out = os.path.splitext(path)[0] + "_distance.json"
+    with open(out, "w") as fjson:
+        json.dump(report, fjson, indent=1)
+    w = report["world"]
+    print(f"distance of {path} to {ref}: hausdorff {w['hausdorff']:.6g}, chamfer {w['chamfer']:.6g}, to the reference mean {w['a_to_b']['mean']:.6g} / 95 % "
+          f"{w['a_to_b']['p95']:.6g} (world units)" + (f"; hausdorff {report['voxels']['hausdorff']:.3f} export voxels" if "voxels" in report else ""))
+    return out
+
+
+FAULT_POLL_EVERY = 16       # iterations between two reads of the training-fault accumulator (field.check_training_faults)
 
 
 def reconstruction(args, device="cuda", log=print, train_dataset=None, val_dataset=None):
@@ -451,8 +505,14 @@ def main(cmd: Optional[List[str]] = None):
     args = config_parser(cmd)
     if getattr(args, "render_mesh", 0) and not (args.render_only and args.render_test):
         raise SystemExit("--render_mesh 1 draws the mesh beside the test renders: it needs --render_only 1 --render_test 1 (and --ckpt); nothing was done")
+    if getattr(args, "mesh_compare", None) and not args.export_mesh:
+        if not getattr(args, "mesh_file", None):
+            raise SystemExit("--mesh_compare REF compares the mesh of --export_mesh 1, or the one --mesh_file names: neither was given; nothing was done")
+        return mesh_compare(args, args.mesh_file)
     if args.export_mesh:
         path = export_mesh(args)
+        if getattr(args, "mesh_compare", None):
+            mesh_compare(args, path)
         if not (args.render_only and (args.render_test or args.render_path)):
             return path
     if args.render_only and (args.render_test or args.render_path):
