@@ -1027,10 +1027,82 @@ int tvr_mesh_bvh_occlusion(const float *verts, int64_t n_vertices, const int32_t
  * Errors, all before any launch: TVR_ERR_INVALID for a NULL pointer where data is due, a negative count, a misaligned blob, a NaN or negative max_dist;
  *   TVR_ERR_UNSUPPORTED for n_vertices or n_points >= 2^31 and n_triangles above TVR_MESH_BVH_MAX_TRIANGLES; TVR_ERR_SCRATCH for an undersized blob or output.
  *   n_points == 0 and n_triangles == 0 are valid.
- * NOT built: a sign (it needs angle-weighted pseudo-normals at edges and vertices), k nearest, refitting a tree after its vertices moved. */
+ * The sign is tvr_mesh_bvh_signed's, below.  NOT built: k nearest, refitting a tree after its vertices moved. */
 int tvr_mesh_bvh_nearest(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const float *points,
                          int64_t n_points, float max_dist, float *dist, size_t dist_bytes, int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes,
                          int64_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
+
+/* The signed distance to a closed mesh: a table of pseudo-normals (csrc/tvr_mesh_pseudo.hip) and the closest-point query above with a sign (csrc/tvr_mesh_bvh.hip;
+ * mesh.build_pseudonormals / signed_distance / contains / signed_distance_grid).  ADDITIVE exports: TVR_VERSION is unchanged.  DESIGN.md §4.19.  Arithmetic as above:
+ * fp32, every operation rounded on its own, in the order written, divisions and square roots IEEE correctly rounded, the dot and cross products of tvr_mesh_bvh_nearest.
+ * THE TABLE (Baerentzen & Aanaes, "Signed distance computation using the angle weighted pseudonormal", 2005) over (verts, faces):
+ *   face_n [F][3]     n_f = (ab x ac) / len per component, ab = v1 - v0, ac = v2 - v0, len = sqrt((ab x ac) . (ab x ac)).  A face with a non-finite vertex coordinate, or
+ *                     whose len is not a finite number > 0 (zero area, underflow, overflow), gets (0, 0, 0) and is counted: degenerate_faces.
+ *   edge_n [F][3][3]  edge k of face f runs from corner (k+1)%3 to corner (k+2)%3 (tvr_mesh_raster's convention); a half-edge is h = 3 f + k.  The entry of (f, k) is
+ *                     the sum, starting from (0, 0, 0), of n_g over ALL half-edges (g, j) on the same undirected edge {smaller vertex index, larger vertex index}, in
+ *                     ascending h: both sides of an edge hold the same bits.  Per undirected edge, by the number m of half-edges on it: m == 1 open_edges, m > 2
+ *                     nonmanifold_edges, m == 2 and both half-edges leave the same vertex inconsistent_edges (two faces that run the edge in the same direction).
+ *                     Half-edges of degenerate faces count like any other (they add zeros); a face (a, b, a) puts two half-edges on {a, b} and one on {a, a}.
+ *   vert_n [V][3]     the sum, starting from (0, 0, 0), over the corners (f, k) that hold the vertex, in ascending 3 f + k, degenerate faces left out, of
+ *                     angle * n_f per component (one product, one sum), angle = atan2f(|e1 x e2|, e1 . e2) with e1 = v_(k+1)%3 - v_k, e2 = v_(k+2)%3 - v_k and
+ *                     |u| = sqrt(u . u).  NOT normalised: only its direction is used.  atan2f is the device library's, not correctly rounded: vert_n is the same
+ *                     bits on every run, but is specified as a direction (tests compare it with fp64 as an angle).  A vertex no face uses holds (0, 0, 0).
+ *   The mesh is CLOSED (as far as the table can tell) when all four counters are 0; only then do the signs below mean inside / outside.
+ *   No float atomics: every sum is formed by one thread in the stated order, so the blob is a function of (verts, faces) alone — the same bytes on every run (build
+ *   zeroes the padding).  The counters are integer sums.  256 B + 48 B per triangle + 12 B per vertex, each array rounded up to 256 B.
+ *   tvr_mesh_pseudonormals_keys writes two arrays of 3 F uint64 (keys_bytes is the size of EACH): corner_keys_out[c] = vertex << 32 | c for corner c = 3 f + k (unique),
+ *   edge_keys_out[h] = smaller vertex << 32 | larger vertex for half-edge h (the two sides of an edge share it); a vertex index outside 0 .. n_vertices-1 gives 2^31 - 1
+ *   in its place and raises the fault flag.  THE CALLER SORTS both ascending: the corner keys by any correct sort, the edge keys STABLY and with the permutation
+ *   (edge_order[i] = the half-edge whose key is sorted_edge_keys[i], int64, as torch.sort(stable=True) returns it).  tvr_mesh_pseudonormals_build checks: corner keys
+ *   strictly ascending, each naming a corner below 3 F exactly once and the vertex the faces hold there; edge keys ascending, equal keys in ascending edge_order, every
+ *   half-edge below 3 F exactly once under the key the faces give it; face indices inside 0 .. n_vertices-1.  If not: *fault_flag_dev = 1, the header's `bad` word is set,
+ *   the counters read 0 and no normal is to be trusted (the signed query refuses such a table).  The sums run over the sorted runs: the first entry of a run of equal
+ *   vertices / equal edge keys walks its run, so a vertex or an edge with k faces costs one thread k steps.  No host read anywhere.
+ *   counts_dev of build (int32[4], may be NULL): {degenerate_faces, open_edges, nonmanifold_edges, inconsistent_edges}.
+ *   tvr_mesh_pseudonormals_describe gives the blob's layout (byte offsets from its start, strides in bytes): header {uint32 magic, F, V, bad, degenerate_faces,
+ *   open_edges, nonmanifold_edges, inconsistent_edges}, face_n [F] x 12 B, edge_n [F] x 36 B (edge k at + 12 k), vert_n [V] x 12 B.
+ * THE SIGNED QUERY (tvr_mesh_bvh_signed): traversal, pair arithmetic, tie rule, pruning bound, max_dist and refusals are tvr_mesh_bvh_nearest's, unchanged; tri and bary
+ *   are bit-equal to its outputs and |sdist| to its dist.  For the winning triangle the pair is evaluated once more (the same expressions, the same bits), giving the
+ *   region r = 1 .. 7 that held and the closest point x in the frame translated to the query point p, so p - closest = -x.  The normal N by region: vert_n of corner A,
+ *   B, C for r = 1, 2, 4; edge_n[tri][2], [tri][1], [tri][0] for r = 3 (AB), 5 (AC), 6 (BC); face_n[tri] for r = 7.  s = -(N . x).
+ *   sdist = -dist if s < 0, else +dist; +0.0 where dist == 0; +inf where nearest gives +inf.  feature [n_points] int8 = r - 1 (0 .. 6: A, B, AB, C, AC, BC, face),
+ *   -1 without an answer.  A point with dist > 0 whose s is 0 or NaN, or whose N is zero or non-finite, is UNDECIDED: it is reported as +dist and counted.
+ *   tri, bary and feature may each be NULL and are then not written.
+ *   WHY A MISJUDGED REGION IS HARMLESS: rounding can assign a point that lies at the boundary between two regions of a triangle (or of two triangles that tie) to
+ *   either.  At the boundary between the face region and an edge or vertex region the closest point lies on that edge or vertex AND p - closest is perpendicular to the
+ *   face, i.e. parallel to n_f.  The edge's and the vertex's pseudo-normals are sums of normals of faces that all contain the closest point, n_f among them, and for a
+ *   closed mesh the angle-weighted theorem gives N . (p - closest) the sign of inside / outside for EVERY feature whose Voronoi cell contains p, the cells' common
+ *   boundary included: both choices of N agree in sign there.  The same holds between an edge's and a vertex's region.  Only |s| near 0 is at risk, which for a point
+ *   off the surface means p - closest nearly tangent to the pseudo-normal's plane; DESIGN.md §4.19 measures that margin.
+ *   LATTICE MODE: points == NULL and lattice != NULL.  n_points is then dims[0] * dims[1] * dims[2] (the argument is ignored; at most 2^31 - 1), point
+ *   i = (ix * dims[1] + iy) * dims[2] + iz has p.x = origin[0] + (float)ix * spacing[0] (one product, one sum), likewise y and z: the outputs are laid out as
+ *   tvr_mesh_count reads its volume, and marching cubes with the same origin and spacing puts the zero level set back where the mesh is.  No point array exists.
+ *   counts_dev (int64[5], may be NULL; zeroed by the call): {points answered, points refused, node tests, triangle tests, points undecided}; the second evaluation of
+ *   the winner is not counted as a test.  Index and blob checks as for the casts; a table whose header does not carry this mesh's F and V, or is marked bad, raises the
+ *   fault flag and nothing is answered.
+ * Errors, all before any launch: as for tvr_mesh_bvh_nearest, and TVR_ERR_INVALID for both or neither of points / lattice with points to answer, a negative lattice
+ *   dimension, a non-finite lattice origin or spacing, misaligned keys (8 B) or table (256 B); TVR_ERR_SCRATCH for undersized keys, scratch or outputs and for a table
+ *   whose size is not exactly tvr_mesh_pseudonormals_bytes(n_vertices, n_triangles) — a table of another mesh's size.  n_points == 0 and n_triangles == 0 are valid. */
+typedef struct {
+    size_t header, face_n, edge_n, vert_n, total;          /* byte offsets from the blob's start; total == tvr_mesh_pseudonormals_bytes */
+    size_t face_stride, edge_stride, vert_stride;          /* bytes per face / per face (three edges) / per vertex */
+} tvr_mesh_pseudonormals_layout;
+typedef struct {
+    float origin[3], spacing[3];
+    int32_t dims[3];
+} tvr_mesh_lattice;
+size_t tvr_mesh_pseudonormals_bytes(int64_t n_vertices, int64_t n_triangles);
+size_t tvr_mesh_pseudonormals_scratch_bytes(int64_t n_triangles);
+int tvr_mesh_pseudonormals_describe(int64_t n_vertices, int64_t n_triangles, tvr_mesh_pseudonormals_layout *out);
+int tvr_mesh_pseudonormals_keys(const int32_t *faces, int64_t n_vertices, int64_t n_triangles, uint64_t *corner_keys_out, uint64_t *edge_keys_out, size_t keys_bytes,
+                                uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_pseudonormals_build(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const uint64_t *sorted_corner_keys,
+                                 const uint64_t *sorted_edge_keys, const int64_t *edge_order, void *table, size_t table_bytes, void *scratch, size_t scratch_bytes,
+                                 int32_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_bvh_signed(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const void *table,
+                        size_t table_bytes, const float *points, int64_t n_points, const tvr_mesh_lattice *lattice, float max_dist, float *sdist, size_t sdist_bytes,
+                        int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes, int8_t *feature, size_t feature_bytes, int64_t *counts_dev /* [5] or NULL */,
+                        uint32_t *fault_flag_dev, void *stream);
 
 #ifdef __cplusplus
 }

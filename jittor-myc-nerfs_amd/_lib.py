@@ -95,6 +95,14 @@ class MeshBvhLayout(C.Structure):       # tvr_mesh_bvh_layout
     _fields_ = [(n, C.c_size_t) for n in ("header", "boxes", "children", "leaf_order", "total", "box_stride", "child_stride", "leaf_stride", "n_nodes", "n_internal")]
 
 
+class MeshPseudonormalsLayout(C.Structure):     # tvr_mesh_pseudonormals_layout
+    _fields_ = [(n, C.c_size_t) for n in ("header", "face_n", "edge_n", "vert_n", "total", "face_stride", "edge_stride", "vert_stride")]
+
+
+class MeshLattice(C.Structure):         # tvr_mesh_lattice
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_int32 * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/tvr.h and include/tvr_ngp.h declare
 SYMBOLS = {
     "tvr_version": (C.c_int, []),
@@ -244,6 +252,15 @@ SYMBOLS = {
                                          C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tvr_mesh_bvh_nearest": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_mesh_pseudonormals_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "tvr_mesh_pseudonormals_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "tvr_mesh_pseudonormals_describe": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(MeshPseudonormalsLayout)]),
+    "tvr_mesh_pseudonormals_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "tvr_mesh_pseudonormals_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_mesh_bvh_signed": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64,
+                                      C.POINTER(MeshLattice), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/tvr_ngp.h
     "tvr_ngp_update_bitfield": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tvr_ngp_sample_scratch_bytes": (C.c_size_t, [C.c_int64]),

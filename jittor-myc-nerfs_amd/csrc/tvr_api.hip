@@ -2535,3 +2535,117 @@ int tvr_mesh_bvh_nearest(const float *verts, int64_t n_vertices, const int32_t *
                                     fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- pseudo-normal table and the signed closest-point query (tvr_mesh_pseudo.hip, tvr_mesh_bvh.hip bv_signed_kernel) ------------------------------------------------------------
+static int pseudo_counts(const char *fn, int64_t n_vertices, int64_t n_triangles)
+{
+    const int rc = bvh_counts(fn, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (n_vertices < 0) return fail(TVR_ERR_INVALID, "%s: n_vertices = %lld is negative", fn, (long long)n_vertices);
+    if (n_vertices > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices = %lld: vertex indices are int32", fn, (long long)n_vertices);
+    return TVR_OK;
+}
+
+size_t tvr_mesh_pseudonormals_bytes(int64_t n_vertices, int64_t n_triangles)
+{
+    if (pseudo_counts(__func__, n_vertices, n_triangles) != TVR_OK) return 0;
+    return mesh_pseudo_bytes(n_vertices, n_triangles, nullptr);
+}
+
+size_t tvr_mesh_pseudonormals_scratch_bytes(int64_t n_triangles)
+{
+    if (bvh_counts(__func__, n_triangles) != TVR_OK) return 0;
+    return mesh_pseudo_scratch_bytes(n_triangles);
+}
+
+int tvr_mesh_pseudonormals_describe(int64_t n_vertices, int64_t n_triangles, tvr_mesh_pseudonormals_layout *out)
+{
+    if (!out) return fail(TVR_ERR_INVALID, "%s: out is NULL", __func__);
+    const int rc = pseudo_counts(__func__, n_vertices, n_triangles);
+    if (rc != TVR_OK) return rc;
+    MeshPseudoCarve c;
+    mesh_pseudo_bytes(n_vertices, n_triangles, &c);
+    out->header = c.header; out->face_n = c.face_n; out->edge_n = c.edge_n; out->vert_n = c.vert_n; out->total = c.total;
+    out->face_stride = 3 * sizeof(float); out->edge_stride = 9 * sizeof(float); out->vert_stride = 3 * sizeof(float);
+    return TVR_OK;
+}
+
+int tvr_mesh_pseudonormals_keys(const int32_t *faces, int64_t n_vertices, int64_t n_triangles, uint64_t *corner_keys_out, uint64_t *edge_keys_out, size_t keys_bytes,
+                                uint32_t *fault_flag_dev, void *stream)
+{
+    const int rc = pseudo_counts(__func__, n_vertices, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_triangles > 0 && (!faces || !corner_keys_out || !edge_keys_out))
+        return fail(TVR_ERR_INVALID, "%s: faces / corner_keys_out / edge_keys_out is NULL with %lld triangles", __func__, (long long)n_triangles);
+    if ((uintptr_t)corner_keys_out % 8 || (uintptr_t)edge_keys_out % 8) return fail(TVR_ERR_INVALID, "%s: corner_keys_out / edge_keys_out is not 8-byte aligned", __func__);
+    if (keys_bytes < (size_t)n_triangles * 3 * sizeof(uint64_t))
+        return fail(TVR_ERR_SCRATCH, "%s: each key array holds %zu B, 3 x %lld corners x uint64 need %zu B", __func__, keys_bytes, (long long)n_triangles,
+                    (size_t)n_triangles * 24);
+    HIP_TRY(launch_mesh_pseudo_keys(faces, n_vertices, n_triangles, (unsigned long long *)corner_keys_out, (unsigned long long *)edge_keys_out, fault_flag_dev,
+                                    (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_pseudonormals_build(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const uint64_t *sorted_corner_keys,
+                                 const uint64_t *sorted_edge_keys, const int64_t *edge_order, void *table, size_t table_bytes, void *scratch, size_t scratch_bytes,
+                                 int32_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (n_triangles > 0 && (!sorted_corner_keys || !sorted_edge_keys || !edge_order))
+        return fail(TVR_ERR_INVALID, "%s: sorted_corner_keys / sorted_edge_keys / edge_order is NULL with %lld triangles", __func__, (long long)n_triangles);
+    if ((uintptr_t)sorted_corner_keys % 8 || (uintptr_t)sorted_edge_keys % 8 || (uintptr_t)edge_order % 8)
+        return fail(TVR_ERR_INVALID, "%s: sorted_corner_keys / sorted_edge_keys / edge_order is not 8-byte aligned", __func__);
+    rc = bvh_buffer(__func__, "table", table, table_bytes, mesh_pseudo_bytes(n_vertices, n_triangles, nullptr), "tvr_mesh_pseudonormals_bytes");
+    if (rc != TVR_OK) return rc;
+    rc = bvh_buffer(__func__, "scratch", scratch, scratch_bytes, mesh_pseudo_scratch_bytes(n_triangles), "tvr_mesh_pseudonormals_scratch_bytes");
+    if (rc != TVR_OK) return rc;
+    HIP_TRY(launch_mesh_pseudo_build(verts, n_vertices, faces, n_triangles, (const unsigned long long *)sorted_corner_keys, (const unsigned long long *)sorted_edge_keys,
+                                     (const long long *)edge_order, table, scratch, (int *)counts_dev, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_bvh_signed(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const void *table,
+                        size_t table_bytes, const float *points, int64_t n_points, const tvr_mesh_lattice *lattice, float max_dist, float *sdist, size_t sdist_bytes,
+                        int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes, int8_t *feature, size_t feature_bytes, int64_t *counts_dev,
+                        uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (points && lattice) return fail(TVR_ERR_INVALID, "%s: both points and lattice are given", __func__);
+    if (lattice) {
+        for (int k = 0; k < 3; ++k) {
+            if (lattice->dims[k] < 0) return fail(TVR_ERR_INVALID, "%s: lattice dims[%d] = %d is negative", __func__, k, (int)lattice->dims[k]);
+            if (!std::isfinite(lattice->origin[k]) || !std::isfinite(lattice->spacing[k]))
+                return fail(TVR_ERR_INVALID, "%s: lattice origin[%d] = %g / spacing[%d] = %g is not finite", __func__, k, (double)lattice->origin[k], k,
+                            (double)lattice->spacing[k]);
+        }
+        const double total = (double)lattice->dims[0] * (double)lattice->dims[1] * (double)lattice->dims[2];
+        if (total > (double)INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: the lattice holds %.0f points: at most 2^31 - 1 per call", __func__, total);
+        n_points = (int64_t)lattice->dims[0] * lattice->dims[1] * lattice->dims[2];
+    }
+    if (n_points < 0) return fail(TVR_ERR_INVALID, "%s: n_points = %lld is negative", __func__, (long long)n_points);
+    if (n_points > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_points = %lld: at most 2^31 - 1 points per call", __func__, (long long)n_points);
+    if (std::isnan(max_dist) || max_dist < 0.0f) return fail(TVR_ERR_INVALID, "%s: max_dist = %g is NaN or negative", __func__, (double)max_dist);
+    rc = bvh_buffer(__func__, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+    if (rc != TVR_OK) return rc;
+    const size_t want = mesh_pseudo_bytes(n_vertices, n_triangles, nullptr);
+    rc = bvh_buffer(__func__, "table", table, table_bytes, want, "tvr_mesh_pseudonormals_bytes");
+    if (rc != TVR_OK) return rc;
+    if (table_bytes != want)
+        return fail(TVR_ERR_SCRATCH, "%s: table holds %zu B, the table of %lld vertices and %lld triangles is %zu B: it belongs to another mesh", __func__, table_bytes,
+                    (long long)n_vertices, (long long)n_triangles, want);
+    if (n_points > 0 && ((!points && !lattice) || !sdist)) return fail(TVR_ERR_INVALID, "%s: points (or lattice) / sdist is NULL with %lld points", __func__, (long long)n_points);
+    NEED("sdist [n_points]", sdist_bytes, n_points, 1);
+    if (tri) NEED("tri [n_points]", tri_bytes, n_points, 1);
+    if (bary) NEED("bary [n_points,3]", bary_bytes, n_points, 3);
+    if (feature && feature_bytes < (size_t)n_points)
+        return fail(TVR_ERR_SCRATCH, "%s: feature holds %zu B, the kernel writes %lld int8", __func__, feature_bytes, (long long)n_points);
+    HIP_TRY(launch_mesh_bvh_signed(verts, n_vertices, faces, n_triangles, bvh, table, points, lattice ? lattice->origin : nullptr, lattice ? lattice->spacing : nullptr,
+                                   lattice ? lattice->dims : nullptr, n_points, max_dist, sdist, tri, bary, (signed char *)feature, (unsigned long long *)counts_dev,
+                                   fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

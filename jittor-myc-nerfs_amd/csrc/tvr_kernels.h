@@ -309,3 +309,26 @@ hipError_t launch_mesh_bvh_nearest(const float *verts, long long n_vertices, con
 hipError_t launch_mesh_bvh_occlusion(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *points,
                                      const float *normals, long long n_points, const float *dirs, int n_dirs, float bias, float t_max, float *out, unsigned long long *counts,
                                      unsigned *fault, hipStream_t stream);
+
+// tvr_mesh_pseudo.hip: the pseudo-normal table of a mesh (include/tvr.h tvr_mesh_pseudonormals_*), read by tvr_mesh_bvh.hip's signed query.  The blob: a
+// header of MESH_PSEUDO_HEADER_BYTES, face_n [F][3], edge_n [F][3][3], vert_n [V][3] fp32, each array rounded up to 256 B.  The build's scratch: 256 B of header, one bit
+// per corner, one bit per half-edge.  The host has checked counts, pointers, sizes and alignment.
+#define MESH_PSEUDO_HEADER_BYTES 256
+#define MESH_PSEUDO_MAGIC 0x4e505654u
+struct MeshPseudoHeader {               // at the blob's start
+    unsigned magic, F, V, bad, degenerate_faces, open_edges, nonmanifold_edges, inconsistent_edges;
+};
+struct MeshPseudoCarve {
+    size_t header, face_n, edge_n, vert_n, total;
+};
+size_t mesh_pseudo_bytes(long long n_vertices, long long n_triangles, MeshPseudoCarve *carve);
+size_t mesh_pseudo_scratch_bytes(long long n_triangles);
+hipError_t launch_mesh_pseudo_keys(const int *faces, long long n_vertices, long long n_triangles, unsigned long long *corner_keys, unsigned long long *edge_keys,
+                                   unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_pseudo_build(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const unsigned long long *corner_keys,
+                                    const unsigned long long *edge_keys, const long long *edge_order, void *table, void *scratch, int *counts, unsigned *fault,
+                                    hipStream_t stream);
+// the signed query: points == nullptr selects the lattice (origin, spacing, dims; n_points = dims[0] * dims[1] * dims[2]); tri, bary and feature may be nullptr
+hipError_t launch_mesh_bvh_signed(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const void *table, const float *points,
+                                  const float *origin, const float *spacing, const int *dims, long long n_points, float max_dist, float *sdist, int *tri, float *bary,
+                                  signed char *feature, unsigned long long *counts, unsigned *fault, hipStream_t stream);

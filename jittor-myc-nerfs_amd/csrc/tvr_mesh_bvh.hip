@@ -11,6 +11,8 @@
 //   cast     one lane per ray, a 64-entry stack per lane in LDS, nearer child first; occlusion: one lane per point, its K rays in table order
 //   nearest  the closest point of the mesh to a point (mesh.closest_points / mesh_distance): the cast's walk with the boxes ordered and pruned by a
 //            padded lower bound of their squared distance; a (point, triangle) pair by Ericson's regions in the frame translated to the point
+//   signed   the same walk, then the sign from the pseudo-normal of the feature under the closest point (tvr_mesh_pseudo.hip's table; mesh.signed_distance,
+//            DESIGN.md §4.19); the points come from an array or from a lattice
 //
 // REFIT.  No workgroup hands data to another inside a launch.  `pass` [F-1] holds, per internal node, the number of the launch that computed its box (0 = not yet; leaves
 // count as pass 1).  Launch p = 2 .. 63 computes a node iff it has no box and both children carry a pass number in 1 .. p-1, i.e. were finished by an EARLIER launch:
@@ -527,8 +529,11 @@ __device__ __forceinline__ bool bv_near_box(const float *__restrict__ b, float p
 }
 
 // (point, triangle t): the definition of include/tvr.h tvr_mesh_bvh_nearest — Ericson's regions in the frame translated to p.  false when D is not finite.
-__device__ __forceinline__ bool bv_near_triangle(const BvTree &T, unsigned t, float px, float py, float pz, float &D, float w[3], unsigned *__restrict__ fault)
+// region: which of the seven held (1 .. 7); xo: the closest point in the translated frame (p - closest = -xo) — what the signed query reads; the walk drops both.
+__device__ __forceinline__ bool bv_near_pair(const BvTree &T, unsigned t, float px, float py, float pz, float &D, float w[3], int &region, float xo[3],
+                                             unsigned *__restrict__ fault)
 {
+    region = 0; xo[0] = xo[1] = xo[2] = 0.0f;
     const int *f = T.faces + (size_t)t * 3;
     const int v0 = f[0], v1 = f[1], v2 = f[2];
     if ((unsigned)v0 >= T.V || (unsigned)v1 >= T.V || (unsigned)v2 >= T.V) {
@@ -553,33 +558,41 @@ __device__ __forceinline__ bool bv_near_triangle(const BvTree &T, unsigned t, fl
     const float vc = bv_dot(ay * abz - az * aby, az * abx - ax * abz, ax * aby - ay * abx, nx, ny, nz);            // (a x ab) . n
     float x, y, z;
     if (d1 <= 0.0f && d2 <= 0.0f) {                                  // 1: vertex A
-        x = ax; y = ay; z = az;
+        x = ax; y = ay; z = az; region = 1;
         w[0] = 1.0f; w[1] = 0.0f; w[2] = 0.0f;
     } else if (d3 >= 0.0f && d4 <= d3) {                             // 2: vertex B
-        x = bx; y = by; z = bz;
+        x = bx; y = by; z = bz; region = 2;
         w[0] = 0.0f; w[1] = 1.0f; w[2] = 0.0f;
     } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {             // 3: edge AB
         const float v = d1 / (d1 - d3);
-        x = ax + v * abx; y = ay + v * aby; z = az + v * abz;
+        x = ax + v * abx; y = ay + v * aby; z = az + v * abz; region = 3;
         w[0] = 1.0f - v; w[1] = v; w[2] = 0.0f;
     } else if (d6 >= 0.0f && d5 <= d6) {                             // 4: vertex C
-        x = cx; y = cy; z = cz;
+        x = cx; y = cy; z = cz; region = 4;
         w[0] = 0.0f; w[1] = 0.0f; w[2] = 1.0f;
     } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {             // 5: edge AC
         const float u = d2 / (d2 - d6);
-        x = ax + u * acx; y = ay + u * acy; z = az + u * acz;
+        x = ax + u * acx; y = ay + u * acy; z = az + u * acz; region = 5;
         w[0] = 1.0f - u; w[1] = 0.0f; w[2] = u;
     } else if (va <= 0.0f && d4 - d3 >= 0.0f && d5 - d6 >= 0.0f) {   // 6: edge BC
         const float u = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        x = bx + u * bcx; y = by + u * bcy; z = bz + u * bcz;
+        x = bx + u * bcx; y = by + u * bcy; z = bz + u * bcz; region = 6;
         w[0] = 0.0f; w[1] = 1.0f - u; w[2] = u;
     } else {                                                         // 7: the face
         const float den = (va + vb) + vc, v = vb / den, u = vc / den;
-        x = (ax + v * abx) + u * acx; y = (ay + v * aby) + u * acy; z = (az + v * abz) + u * acz;
+        x = (ax + v * abx) + u * acx; y = (ay + v * aby) + u * acy; z = (az + v * abz) + u * acz; region = 7;
         w[0] = (1.0f - v) - u; w[1] = v; w[2] = u;
     }
+    xo[0] = x; xo[1] = y; xo[2] = z;
     D = bv_dot(x, y, z, x, y, z);
     return bv_finite(D);                                             // (a NaN is not finite: a zero-area triangle in region 7)
+}
+
+__device__ __forceinline__ bool bv_near_triangle(const BvTree &T, unsigned t, float px, float py, float pz, float &D, float w[3], unsigned *__restrict__ fault)
+{
+    int region;
+    float x[3];
+    return bv_near_pair(T, t, px, py, pz, D, w, region, x, fault);
 }
 
 // Walk the tree for one point.  H.D holds max_dist^2 on entry.  The shape of bv_walk: the nearer box first, the other pushed, a popped node tested again.
@@ -662,6 +675,89 @@ __global__ __launch_bounds__(BV_CAST_THREADS) void bv_nearest_kernel(BvTree T, c
         bary_out[(size_t)i * 3 + 2] = answered ? H.w2 : 0.0f;
     }
     bv_count(counts, answered, refused, node_tests, tri_tests);
+}
+
+// ---- signed distance (tvr_mesh_bvh_signed) ------------------------------------------------------------------------------------------------------------------
+struct BvNormals {                                   // the pseudo-normal table of tvr_mesh_pseudo.hip
+    const MeshPseudoHeader *h;
+    const float *face_n, *edge_n, *vert_n;           // [F][3], [F][3][3], [V][3]
+};
+
+struct BvLattice {                                   // points == nullptr: point i = (ix * ny + iy) * nz + iz sits at origin + index * spacing
+    float ox, oy, oz, sx, sy, sz;
+    unsigned ny, nz;
+};
+
+__device__ __forceinline__ bool bv_table_ok(const BvTree &T, const BvNormals &P, unsigned *__restrict__ fault)
+{
+    const bool ok = P.h->magic == MESH_PSEUDO_MAGIC && P.h->F == T.F && P.h->V == T.V && P.h->bad == 0u;
+    if (!ok && threadIdx.x == 0) *fault = 1u;
+    return ok;
+}
+
+// bv_nearest_kernel's walk, then the winner's pair once more for its region and closest point x (the same expressions: the same bits), the normal N of the feature
+// under x from the table, and the sign of s = -(N . x) = N . (p - closest).
+__global__ __launch_bounds__(BV_CAST_THREADS) void bv_signed_kernel(BvTree T, BvNormals P, const float *__restrict__ points, BvLattice G, unsigned N, float max_sq,
+                                                                    float *__restrict__ sdist_out, int *__restrict__ tri_out, float *__restrict__ bary_out,
+                                                                    signed char *__restrict__ feature_out, unsigned long long *__restrict__ counts,
+                                                                    unsigned *__restrict__ fault)
+{
+    __shared__ unsigned stack[BV_STACK * BV_CAST_THREADS];            // entry e of lane l at [e * BV_CAST_THREADS + l]
+    const bool blob_ok = bv_blob_ok(T, fault), table_ok = bv_table_ok(T, P, fault), ok = blob_ok && table_ok;
+    const unsigned i = blockIdx.x * BV_CAST_THREADS + threadIdx.x;
+    bool answered = false, refused = false, undecided = false;
+    unsigned node_tests = 0, tri_tests = 0;
+    if (i < N) {
+        float px, py, pz;
+        if (points) {
+            const float *p = points + (size_t)i * 3;
+            px = p[0]; py = p[1]; pz = p[2];
+        } else {
+            const unsigned plane = G.ny * G.nz, ix = i / plane, r = i - ix * plane, iy = r / G.nz, iz = r - iy * G.nz;
+            px = G.ox + (float)ix * G.sx; py = G.oy + (float)iy * G.sy; pz = G.oz + (float)iz * G.sz;
+        }
+        BvNear H;
+        H.D = max_sq; H.tri = 0xffffffffu; H.w0 = H.w1 = H.w2 = 0.0f;
+        refused = !(bv_finite(px) && bv_finite(py) && bv_finite(pz));
+        if (ok && !refused) bv_near_walk(T, px, py, pz, H, stack + threadIdx.x, BV_CAST_THREADS, node_tests, tri_tests, fault);
+        answered = H.tri != 0xffffffffu;
+        float dist = __uint_as_float(0x7f800000u);
+        int region = 0;
+        if (answered) {
+            float D, w[3], x[3];
+            bv_near_pair(T, H.tri, px, py, pz, D, w, region, x, fault);
+            dist = sqrtf(H.D);
+            const int *f = T.faces + (size_t)H.tri * 3;
+            const unsigned corner = region == 1 ? 0u : region == 2 ? 1u : 2u, v = (unsigned)f[corner];
+            const float *n = P.face_n + (size_t)H.tri * 3;                                        // 7: the face
+            if (region == 3) n = P.edge_n + ((size_t)H.tri * 3 + 2) * 3;                          // AB is edge 2 (from corner 0 to corner 1)
+            else if (region == 5) n = P.edge_n + ((size_t)H.tri * 3 + 1) * 3;                     // AC is edge 1
+            else if (region == 6) n = P.edge_n + ((size_t)H.tri * 3 + 0) * 3;                     // BC is edge 0
+            else if (region == 1 || region == 2 || region == 4) n = v < T.V ? P.vert_n + (size_t)v * 3 : nullptr;
+            float s = 0.0f;
+            bool usable = false;
+            if (n && region >= 1) {
+                const float nx = n[0], ny = n[1], nz = n[2];
+                usable = bv_finite(nx) && bv_finite(ny) && bv_finite(nz) && !(nx == 0.0f && ny == 0.0f && nz == 0.0f);
+                s = -bv_dot(nx, ny, nz, x[0], x[1], x[2]);
+            }
+            undecided = dist > 0.0f && !(usable && (s < 0.0f || s > 0.0f));
+            if (dist > 0.0f && usable && s < 0.0f) dist = -dist;
+        }
+        sdist_out[i] = dist;
+        if (tri_out) tri_out[i] = answered ? (int)H.tri : -1;
+        if (bary_out) {
+            bary_out[(size_t)i * 3 + 0] = answered ? H.w0 : 0.0f;
+            bary_out[(size_t)i * 3 + 1] = answered ? H.w1 : 0.0f;
+            bary_out[(size_t)i * 3 + 2] = answered ? H.w2 : 0.0f;
+        }
+        if (feature_out) feature_out[i] = (signed char)(answered ? region - 1 : -1);
+    }
+    bv_count(counts, answered, refused, node_tests, tri_tests);
+    if (counts) {
+        const u64 mu = __ballot(undecided);
+        if ((threadIdx.x & 63u) == 0 && mu) atomicAdd(counts + 4, (unsigned long long)__popcll(mu));
+    }
 }
 
 __global__ __launch_bounds__(BV_CAST_THREADS) void bv_occlusion_kernel(BvTree T, const float *__restrict__ points, const float *__restrict__ normals, unsigned M,
@@ -756,5 +852,32 @@ hipError_t launch_mesh_bvh_nearest(const float *verts, long long V, const int *f
     const unsigned nb = (unsigned)((N + BV_CAST_THREADS - 1) / BV_CAST_THREADS);
     const float max_sq = max_dist * max_dist;                        // fp32, rounded once (+inf for +inf or an overflow)
     hipLaunchKernelGGL(bv_nearest_kernel, dim3(nb), dim3(BV_CAST_THREADS), 0, stream, T, points, (unsigned)N, max_sq, dist, tri, bary, counts, fault);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_bvh_signed(const float *verts, long long V, const int *faces, long long F, const void *bvh, const void *table, const float *points,
+                                  const float *origin, const float *spacing, const int *dims, long long N, float max_dist, float *sdist, int *tri, float *bary,
+                                  signed char *feature, unsigned long long *counts, unsigned *fault, hipStream_t stream)
+{
+    if (counts) {
+        hipError_t e = hipMemsetAsync(counts, 0, 5 * sizeof(unsigned long long), stream);
+        if (e != hipSuccess) return e;
+    }
+    if (N <= 0) return hipSuccess;
+    const BvTree T = bv_tree(verts, V, faces, F, const_cast<void *>(bvh));
+    MeshPseudoCarve L;
+    mesh_pseudo_bytes(V, F, &L);
+    BvNormals P;
+    P.h = (const MeshPseudoHeader *)table;
+    P.face_n = (const float *)((const char *)table + L.face_n); P.edge_n = (const float *)((const char *)table + L.edge_n);
+    P.vert_n = (const float *)((const char *)table + L.vert_n);
+    BvLattice G = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1u, 1u};
+    if (!points) {
+        G.ox = origin[0]; G.oy = origin[1]; G.oz = origin[2]; G.sx = spacing[0]; G.sy = spacing[1]; G.sz = spacing[2];
+        G.ny = (unsigned)dims[1]; G.nz = (unsigned)dims[2];
+    }
+    const unsigned nb = (unsigned)((N + BV_CAST_THREADS - 1) / BV_CAST_THREADS);
+    const float max_sq = max_dist * max_dist;                        // fp32, rounded once (+inf for +inf or an overflow)
+    hipLaunchKernelGGL(bv_signed_kernel, dim3(nb), dim3(BV_CAST_THREADS), 0, stream, T, P, points, G, (unsigned)N, max_sq, sdist, tri, bary, feature, counts, fault);
     return hipGetLastError();
 }

@@ -835,6 +835,7 @@ class MeshBVH:
 
     def __init__(self, blob, verts, faces, height, triangles_skipped):
         self.blob, self.verts, self.faces, self.height, self.triangles_skipped = blob, verts, faces, int(height), int(triangles_skipped)
+        self.pseudonormals = None       # the MeshPseudonormals of this mesh once build_pseudonormals was asked for it (signed_distance needs it)
 
     @property
     def n_triangles(self) -> int:
@@ -1122,7 +1123,22 @@ def mesh_distance(verts_a, faces_a, verts_b, faces_b, subdiv: int = 2, symmetric
     vertices; samples counts the queries, refused those that got no answer (non-finite coordinates, or an empty B) and are left out of the figures.  hausdorff is the
     larger of the two max, chamfer the mean of the two mean.  Distances are unsigned and one-sided figures are not symmetric: a hole in B does not show in a_to_b.
     bvh_a / bvh_b: hierarchies built over exactly these meshes (build_bvh), built here when absent (bvh_a is only needed with symmetric).  The statistics are computed
-    on the device and read once.  No CPU fallback.  `stats` (a dict) receives closest_points' counters summed over the directions."""
+    on the device and read once.  No CPU fallback.  `stats` (a dict) receives closest_points' counters summed over the directions.
+    signed_mesh_distance adds the direction of the difference."""
+    return _mesh_distance(verts_a, faces_a, verts_b, faces_b, subdiv, symmetric, unit, bvh_a, bvh_b, stats, False)
+
+
+def signed_mesh_distance(verts_a, faces_a, verts_b, faces_b, subdiv: int = 2, symmetric: bool = True, unit: float = 1.0, bvh_a: MeshBVH = None, bvh_b: MeshBVH = None,
+                         stats: dict = None) -> dict:
+    """mesh_distance, and in which direction the meshes differ -> mesh_distance's dict (the same figures: the queries are signed_distance's, and |sdist| is
+    closest_points' dist bit for bit) in which every direction also carries SIGNED_STATISTICS — signed_mean, the area-weighted mean of the signed distance / unit
+    (positive: A lies outside B), and inside_fraction, the area-weighted share of A's samples inside B.  A direction whose target is not closed (build_pseudonormals)
+    carries None for both and "signed_reason" says why; the unsigned figures are reported all the same.  `stats` (a dict) receives signed_distance's counters summed
+    over the directions and "closedness": per direction the target's counters.  No CPU fallback."""
+    return _mesh_distance(verts_a, faces_a, verts_b, faces_b, subdiv, symmetric, unit, bvh_a, bvh_b, stats, True)
+
+
+def _mesh_distance(verts_a, faces_a, verts_b, faces_b, subdiv, symmetric, unit, bvh_a, bvh_b, stats, signed) -> dict:
     unit = float(unit)
     if not unit > 0.0 or not np.isfinite(unit):
         raise ValueError(f"mesh_distance: unit = {unit} must be positive and finite")
@@ -1133,20 +1149,202 @@ def mesh_distance(verts_a, faces_a, verts_b, faces_b, subdiv: int = 2, symmetric
     sides = [("a_to_b", va, fa, _bvh_arg(bvh_b, "mesh_distance") if bvh_b is not None else build_bvh(vb, fb))]
     if symmetric:
         sides.append(("b_to_a", vb, fb, _bvh_arg(bvh_a, "mesh_distance") if bvh_a is not None else build_bvh(va, fa)))
-    rows, counters = [], {}
-    for _, v, f, target in sides:
+    rows, counters, closedness = [], {}, {}
+    for name, v, f, target in sides:
         pts, w = surface_samples(v, f, subdiv)
         st = {}
-        rows.append(distance_statistics(closest_points(target, pts, stats=st)[0], w, unit))
+        if signed:
+            closedness[name] = {}
+            build_pseudonormals(target, stats=closedness[name])
+            sd = signed_distance(target, pts, strict=False, stats=st)[0]
+            rows.append(torch.cat([distance_statistics(sd.abs(), w, unit), signed_statistics(sd, w, unit)]))
+        else:
+            rows.append(distance_statistics(closest_points(target, pts, stats=st)[0], w, unit))
         for k, x in st.items():
             counters[k] = counters.get(k, 0) + x
     host = torch.stack(rows).cpu().tolist()                          # the one host read of the figures
     out = {}
     for (name, _, _, _), row in zip(sides, host):
         out[name] = {k: (int(x) if k in ("samples", "refused") else float(x)) for k, x in zip(DISTANCE_STATISTICS, row)}
+        if signed:
+            closed = closedness[name]["closed"]
+            out[name].update({k: (float(x) if closed else None) for k, x in zip(SIGNED_STATISTICS, row[len(DISTANCE_STATISTICS):])})
+            if not closed:
+                out[name]["signed_reason"] = "the target mesh is not closed: " + _closedness_text(closedness[name])
+    if signed:
+        counters["closedness"] = closedness
     if symmetric:
         out["hausdorff"] = max(out["a_to_b"]["max"], out["b_to_a"]["max"])
         out["chamfer"] = 0.5 * (out["a_to_b"]["mean"] + out["b_to_a"]["mean"])
     if stats is not None:
         stats.update(counters)
     return out
+
+
+# ---- signed distance: pseudo-normals and an inside test (csrc/tvr_mesh_pseudo.hip, csrc/tvr_mesh_bvh.hip bv_signed_kernel; include/tvr.h tvr_mesh_pseudonormals_* /
+# tvr_mesh_bvh_signed) ------------------------------------------------------------------------------------------------------------------------------------------
+BVH_SIGNED_CHUNK = 1 << 24      # points per tvr_mesh_bvh_signed call of signed_distance (results do not depend on it)
+CLOSEDNESS_COUNTERS = ("degenerate_faces", "open_edges", "nonmanifold_edges", "inconsistent_edges")
+SIGNED_STATISTICS = ("signed_mean", "inside_fraction")
+FEATURES = ("vertex A", "vertex B", "edge AB", "vertex C", "edge AC", "edge BC", "face")      # what signed_distance's `feature` 0 .. 6 names
+
+
+class MeshPseudonormals:
+    """What build_pseudonormals keeps on a MeshBVH: the table (uint8 blob on the device: face_n, edge_n, vert_n; pseudonormals_layout) and the mesh's closedness counters."""
+
+    def __init__(self, blob, counters: dict):
+        self.blob, self.counters = blob, dict(counters)
+
+    @property
+    def closed(self) -> bool:
+        return all(self.counters[k] == 0 for k in CLOSEDNESS_COUNTERS)
+
+
+def pseudonormals_layout(n_vertices: int, n_triangles: int) -> dict:
+    """tvr_mesh_pseudonormals_describe(V, F) as a dict (header / face_n / edge_n / vert_n / total offsets, face / edge / vert strides).  Host only."""
+    lay = L.MeshPseudonormalsLayout()
+    L.check(L.lib().tvr_mesh_pseudonormals_describe(int(n_vertices), int(n_triangles), C.byref(lay)), "tvr_mesh_pseudonormals_describe")
+    return {n: int(getattr(lay, n)) for n, _ in L.MeshPseudonormalsLayout._fields_}
+
+
+def _closedness_text(counters: dict) -> str:
+    return ", ".join(f"{k} = {counters[k]}" for k in CLOSEDNESS_COUNTERS)
+
+
+def build_pseudonormals(bvh: MeshBVH, stats: dict = None) -> MeshPseudonormals:
+    """The pseudo-normal table of a hierarchy's mesh, built once and kept as bvh.pseudonormals: per face its unit normal, per edge the sum of the normals of the faces
+    on it, per vertex the angle-weighted sum over its fan (Baerentzen & Aanaes) — the normals whose product with (point - closest point) has the sign of outside /
+    inside on a closed mesh, at edges and vertices too, where a face normal fails.
+
+    Two arrays of 64-bit keys from tvr_mesh_pseudonormals_keys (corner by vertex, half-edge by undirected edge) are sorted with torch.sort on the device (plumbing;
+    the second stably), then tvr_mesh_pseudonormals_build checks them and forms every sum in ascending face order in one thread: no float atomics, the same bytes on
+    every run.  `stats` (a dict) receives degenerate_faces / open_edges / nonmanifold_edges / inconsistent_edges, closed (all four are 0) and table_bytes.  No CPU
+    fallback."""
+    b = _bvh_arg(bvh, "build_pseudonormals")
+    if b.pseudonormals is None:
+        V, F, dev, lib = b.n_vertices, b.n_triangles, b.device, L.lib()
+        nblob, nscratch = lib.tvr_mesh_pseudonormals_bytes(V, F), lib.tvr_mesh_pseudonormals_scratch_bytes(F)
+        if nblob == 0 or nscratch == 0:
+            raise L.TvrError("build_pseudonormals: " + lib.tvr_last_error().decode(errors="replace"))
+        blob = L.dev_bytes(nblob, dev, what="mesh pseudonormals blob")
+        scratch = L.dev_bytes(nscratch, dev, what="mesh pseudonormals scratch")
+        ck = L.dev_empty((3 * F,), torch.int64, dev, what="mesh pseudonormals corner keys")
+        ek = L.dev_empty((3 * F,), torch.int64, dev, what="mesh pseudonormals edge keys")
+        counts = L.dev_empty((4,), torch.int32, dev, what="mesh pseudonormals counts")
+        flag = L.dev_bytes(4, dev, zero=True, what="mesh pseudonormals fault flag").view(torch.int32)
+        L.check(lib.tvr_mesh_pseudonormals_keys(_ptr(b.faces), V, F, _ptr(ck), _ptr(ek), L.nbytes(ck), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_pseudonormals_keys")
+        cks = torch.sort(ck)[0].contiguous()                         # keys stay below 2^63: the signed order is the unsigned one
+        eks, order = torch.sort(ek, stable=True)
+        eks, order = eks.contiguous(), order.contiguous()
+        L.check(lib.tvr_mesh_pseudonormals_build(_ptr(b.verts), V, _ptr(b.faces), F, _ptr(cks), _ptr(eks), _ptr(order), blob.data_ptr(), L.nbytes(blob), scratch.data_ptr(),
+                                                 L.nbytes(scratch), counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_pseudonormals_build")
+        if int(flag.item()) != 0:
+            raise L.TvrError(f"tvr_mesh_pseudonormals_build raised its fault flag: a face index lies outside 0 .. {V - 1}, or the keys were not sorted (include/tvr.h)")
+        b.pseudonormals = MeshPseudonormals(blob, dict(zip(CLOSEDNESS_COUNTERS, (int(x) for x in counts.cpu().tolist()))))
+    if stats is not None:
+        stats.update(b.pseudonormals.counters, closed=b.pseudonormals.closed, table_bytes=int(b.pseudonormals.blob.numel()))
+    return b.pseudonormals
+
+
+def _signed_table(b: MeshBVH, strict: bool, what: str) -> MeshPseudonormals:
+    table = build_pseudonormals(b)
+    if strict and not table.closed:
+        raise L.TvrError(f"{what}: the mesh is not closed ({_closedness_text(table.counters)}), so inside and outside are not defined; strict=False answers anyway, "
+                         f"without a promise about the signs")
+    return table
+
+
+def _signed_stats(stats, total):
+    if stats is not None:
+        a, r_, nt, tt, u = (int(x) for x in total.cpu().tolist())
+        stats.update(points_answered=a, points_refused=r_, node_tests=nt, triangle_tests=tt, points_undecided=u)
+
+
+_SIGNED_FAULT = ("tvr_mesh_bvh_signed raised its fault flag: the hierarchy or the pseudo-normal table does not belong to this mesh, or a face index lies outside the "
+                 "vertices (include/tvr.h)")
+
+
+def signed_distance(bvh: MeshBVH, points, max_dist: float = float("inf"), strict: bool = True, stats: dict = None):
+    """The signed distance of every point to a closed mesh -> (sdist [N] float32, tri [N] int32, bary [N,3] float32, feature [N] int8) on the device.
+
+    |sdist|, tri and bary are closest_points' answers, bit for bit; sdist is negative inside the mesh (the side the right-hand-rule normals point away from), +0.0 on
+    it, +inf where closest_points gives +inf.  feature says what the closest point lies on: FEATURES[feature] of triangle tri, -1 without an answer.  The sign is that
+    of N . (p - closest) with N the pseudo-normal of that feature (build_pseudonormals, built here when absent).  strict: a mesh that is not closed raises TvrError
+    naming the counters; strict=False answers anyway and the signs are then not promised.  A point whose sign the normal cannot decide (N . (p - closest) == 0 off the
+    surface, or a zero normal) is reported as +dist and counted.  Results do not depend on the order or batching of the points.  No CPU fallback.  `stats` (a dict)
+    receives points_answered / points_refused / node_tests / triangle_tests / points_undecided."""
+    b = _bvh_arg(bvh, "signed_distance")
+    dev = b.device
+    p = _rays_on_device(points, dev, "signed_distance", "points")
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise L.TvrError(f"signed_distance takes points [N, 3]; got {tuple(p.shape)}")
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise L.TvrError(f"signed_distance: max_dist = {max_dist} must be >= 0 (+inf = no limit)")
+    table = _signed_table(b, strict, "signed_distance")
+    p = p.contiguous()
+    N, lib = int(p.shape[0]), L.lib()
+    sdist = L.dev_empty((N,), torch.float32, dev, what="mesh bvh signed sdist")
+    tri = L.dev_empty((N,), torch.int32, dev, what="mesh bvh signed tri")
+    bary = L.dev_empty((N, 3), torch.float32, dev, what="mesh bvh signed bary")
+    feature = L.dev_empty((N,), torch.int8, dev, what="mesh bvh signed feature")
+    counts = L.dev_empty((5,), torch.int64, dev, what="mesh bvh signed counts")
+    total = torch.zeros(5, dtype=torch.int64, device=dev)
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh bvh fault flag").view(torch.int32)
+    for i0 in range(0, max(N, 1), BVH_SIGNED_CHUNK):
+        n = min(BVH_SIGNED_CHUNK, N - i0)
+        pc, sc, tc, bc, fc = p[i0:i0 + n], sdist[i0:i0 + n], tri[i0:i0 + n], bary[i0:i0 + n], feature[i0:i0 + n]
+        L.check(lib.tvr_mesh_bvh_signed(_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), table.blob.data_ptr(),
+                                        L.nbytes(table.blob), _ptr(pc), n, None, max_dist, _ptr(sc), L.nbytes(sc), _ptr(tc), L.nbytes(tc), _ptr(bc), L.nbytes(bc), _ptr(fc),
+                                        L.nbytes(fc), counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_bvh_signed")
+        total += counts
+    if int(flag.item()) != 0:
+        raise L.TvrError(_SIGNED_FAULT)
+    _signed_stats(stats, total)
+    return sdist, tri, bary, feature
+
+
+def contains(bvh: MeshBVH, points, strict: bool = True) -> torch.Tensor:
+    """Which points lie inside a closed mesh -> [N] bool on the device: signed_distance(bvh, points, strict=strict) < 0.  A point on the surface is not inside."""
+    return signed_distance(bvh, points, strict=strict)[0] < 0
+
+
+def signed_distance_grid(bvh: MeshBVH, dims, origin=(0, 0, 0), spacing=(1, 1, 1), max_dist: float = float("inf"), strict: bool = True, stats: dict = None) -> torch.Tensor:
+    """The signed distance field of a closed mesh on a lattice -> volume [nx, ny, nz] float32 on the device, laid out as marching_cubes reads its volume.
+
+    Grid point (i, j, k) sits at origin + (i, j, k) * spacing, formed in the kernel in fp32 (one product, one sum per axis): no point tensor is materialised, and the
+    values are bit-equal to signed_distance on the same points.  marching_cubes(-volume, 0.0, spacing, origin) (a grid point is inside iff value >= level) extracts the
+    mesh's surface again.  dims [3] with at most 2^31 - 1 grid points.  strict, max_dist, `stats` as for signed_distance.  No CPU fallback."""
+    b = _bvh_arg(bvh, "signed_distance_grid")
+    dev = b.device
+    dims = [int(x) for x in dims]
+    if len(dims) != 3 or min(dims) < 0 or dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
+        raise L.TvrError(f"signed_distance_grid takes dims [3] of non-negative sizes with at most 2^31 - 1 grid points; got {dims}")
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise L.TvrError(f"signed_distance_grid: max_dist = {max_dist} must be >= 0 (+inf = no limit)")
+    table = _signed_table(b, strict, "signed_distance_grid")
+    lat = L.MeshLattice()
+    lat.origin[:], lat.spacing[:], lat.dims[:] = [float(x) for x in origin], [float(x) for x in spacing], dims
+    vol = L.dev_empty(tuple(dims), torch.float32, dev, what="mesh bvh signed volume")
+    counts = L.dev_empty((5,), torch.int64, dev, what="mesh bvh signed counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh bvh fault flag").view(torch.int32)
+    L.check(L.lib().tvr_mesh_bvh_signed(_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), table.blob.data_ptr(),
+                                        L.nbytes(table.blob), None, 0, C.byref(lat), max_dist, _ptr(vol), L.nbytes(vol), None, 0, None, 0, None, 0, counts.data_ptr(),
+                                        flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_bvh_signed")
+    if int(flag.item()) != 0:
+        raise L.TvrError(_SIGNED_FAULT)
+    _signed_stats(stats, counts)
+    return vol
+
+
+def signed_statistics(sdist: torch.Tensor, weights: torch.Tensor, unit: float = 1.0) -> torch.Tensor:
+    """SIGNED_STATISTICS of one direction of signed_mesh_distance -> [2] float64 on sdist's device, no host read: over the samples that were answered (finite
+    sdist), weighted by `weights`, the mean of sdist / unit and the share of the weight whose sdist is negative; NaN when the total weight is 0."""
+    ok = torch.isfinite(sdist)
+    zero = torch.zeros((), dtype=torch.float64, device=sdist.device)
+    d = torch.where(ok, sdist.to(torch.float64) / float(unit), zero)
+    w = torch.where(ok, weights.to(torch.float64), zero)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=sdist.device)
+    total = w.sum()
+    return torch.stack([torch.where(total > 0, (w * d).sum() / total, nan), torch.where(total > 0, (w * (d < 0).to(torch.float64)).sum() / total, nan)])

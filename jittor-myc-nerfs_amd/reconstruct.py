@@ -104,6 +104,10 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # measure how far a mesh is from another (mesh.mesh_distance): REF.ply or REF.obj; with --export_mesh 1 the mesh just written is compared, without it --mesh_file
     # (no checkpoint needed); writes <mesh minus extension>_distance.json in world units and, when a --ckpt is loaded, in export voxels; unset = off
     p.add_argument("--mesh_compare", type=str, default=None)
+    # with --mesh_compare: 1 = also say in which direction the meshes differ (mesh.signed_mesh_distance): per direction signed_mean (positive: outside the target)
+    # and inside_fraction, and under "closedness" each target's degenerate / open / non-manifold / inconsistent counters; a target that is not closed gets null for
+    # both keys and "signed_reason"; 0 = the JSON as it always was
+    p.add_argument("--mesh_compare_signed", type=int, default=0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     # (not a reference option) views of an exported mesh beside the rendered test views (mesh.render_mesh): with --render_only 1 --render_test 1, read --mesh_file
@@ -307,28 +311,36 @@ def mesh_compare(args, path, device="cuda"):
     both file names and the vertex and triangle counts; with a --ckpt also the same figures in export voxels, the unit being the smallest edge of
     mesh_export_voxel(tensorf, --mesh_grid), which the file records (a mesh file does not say on which grid it was made).  Returns the path of the JSON."""
     import json
-    from .mesh import build_bvh, mesh_distance
+    from .mesh import CLOSEDNESS_COUNTERS, build_bvh, mesh_distance, signed_mesh_distance
     ref = args.mesh_compare
     va, fa = _read_mesh_geometry(path)
     vb, fb = _read_mesh_geometry(ref)
     ta, tfa, tb, tfb = (torch.from_numpy(np.ascontiguousarray(x)).to(device) for x in (va, fa, vb, fb))
     bvh_a, bvh_b = build_bvh(ta, tfa), build_bvh(tb, tfb)
+    signed, st = bool(getattr(args, "mesh_compare_signed", 0)), {}
+    distance = signed_mesh_distance if signed else mesh_distance
     report = {"mesh_file": path, "reference_file": ref, "vertices": int(len(va)), "triangles": int(len(fa)), "reference_vertices": int(len(vb)),
               "reference_triangles": int(len(fb)), "a_is": "mesh_file", "b_is": "reference_file", "subdiv": 2,
-              "world": mesh_distance(ta, tfa, tb, tfb, bvh_a=bvh_a, bvh_b=bvh_b)}
+              "world": distance(ta, tfa, tb, tfb, bvh_a=bvh_a, bvh_b=bvh_b, stats=st)}
+    if signed:                                                       # per direction the TARGET's counters: a_to_b is measured against the reference
+        report["closedness"] = {side: {k: c[k] for k in CLOSEDNESS_COUNTERS + ("closed",)} for side, c in st["closedness"].items()}
     if args.ckpt and os.path.exists(args.ckpt):
         tensorf, _ = _build_from_ckpt(args, load_checkpoint(args.ckpt), device)
         voxel = mesh_export_voxel(tensorf, getattr(args, "mesh_grid", None))
         report["voxel"] = [float(x) for x in voxel]
         report["voxel_unit"] = float(voxel.min())
         report["voxel_from"] = "--mesh_grid" if getattr(args, "mesh_grid", None) else "the field's gridSize (pass the export's --mesh_grid if it was made on another grid)"
-        report["voxels"] = mesh_distance(ta, tfa, tb, tfb, unit=float(voxel.min()), bvh_a=bvh_a, bvh_b=bvh_b)
+        report["voxels"] = distance(ta, tfa, tb, tfb, unit=float(voxel.min()), bvh_a=bvh_a, bvh_b=bvh_b)
     out = os.path.splitext(path)[0] + "_distance.json"
     with open(out, "w") as fjson:
         json.dump(report, fjson, indent=1)
     w = report["world"]
     print(f"distance of {path} to {ref}: hausdorff {w['hausdorff']:.6g}, chamfer {w['chamfer']:.6g}, to the reference mean {w['a_to_b']['mean']:.6g} / 95 % "
           f"{w['a_to_b']['p95']:.6g} (world units)" + (f"; hausdorff {report['voxels']['hausdorff']:.3f} export voxels" if "voxels" in report else ""))
+    if signed:
+        for side in ("a_to_b", "b_to_a"):
+            x = w[side]
+            print(f"  {side}: " + (x["signed_reason"] if x["signed_mean"] is None else f"signed mean {x['signed_mean']:.6g}, inside fraction {x['inside_fraction']:.4f}"))
     return out
 
 
