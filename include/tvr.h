@@ -1104,6 +1104,54 @@ int tvr_mesh_bvh_signed(const float *verts, int64_t n_vertices, const int32_t *f
                         int32_t *tri, size_t tri_bytes, float *bary, size_t bary_bytes, int8_t *feature, size_t feature_bytes, int64_t *counts_dev /* [5] or NULL */,
                         uint32_t *fault_flag_dev, void *stream);
 
+/* Inside / outside for ANY triangle soup: the generalized winding number (Jacobson, Kavan & Sorkine-Hornung 2013) by its hierarchical evaluation (Barill, Dickson,
+ * Schmidt, Levin & Jacobson 2018; dipole order only) on the hierarchy above (csrc/tvr_mesh_winding.hip; mesh.build_winding / winding_number / winding_contains /
+ * winding_number_grid / signed_distance_winding / remesh_watertight).  ADDITIVE exports: TVR_VERSION is unchanged.  DESIGN.md §4.20.  Arithmetic as above: fp32, every
+ * operation rounded on its own, in the order written, divisions and square roots IEEE correctly rounded, u . v = (u.x * v.x + u.y * v.y) + u.z * v.z and
+ * u x v = (u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x).
+ * w(q) = (1 / 4 pi) * sum over the triangles of the signed solid angle they subtend at q: 1 inside a closed outward-oriented shell, 0 outside, k inside k nested or
+ *   overlapping shells, and a smooth function in between for a soup with holes, doubled walls or unwelded corners.  Inside means w > 0.5.
+ * THE TABLE (tvr_mesh_winding_build) over a hierarchy's blob: one row of 8 fp32 per INTERNAL node i = 0 .. F-2, {A.x, A.y, A.z, c.x, c.y, c.z, r, a}.
+ *   Moments of a leaf, from its triangle (v0, v1, v2):  ab = v1 - v0, ac = v2 - v0;  A_t = 0.5f * (ab x ac) per component;  a_t = sqrt(A_t . A_t);
+ *   g_k = ((v0_k + v1_k) + v2_k) / 3.0f;  m_t,k = a_t * g_k.  A triangle the hierarchy skipped (a non-finite coordinate) has A_t = m_t = 0, a_t = 0.
+ *   Moments of an internal node: A = A(left child) + A(right child), m = m(left) + m(right), a = a(left) + a(right), per component, left = children[i][0].
+ *   Row: ok = a > 0 and a finite;  c_k = m_k / a if ok, else 0;  e_k = max(c_k - lo_k, hi_k - c_k) with (lo, hi) the node's box AS IT STANDS IN THE BLOB;
+ *   r = sqrt(e . e), the distance from c to the farthest corner of the box;  r = +inf if not ok or if r is not finite (such a node is never approximated).
+ *   The sums are formed bottom-up in the refit's discipline: 62 launches, launch p computes the nodes whose two children were finished by an EARLIER launch (a pass
+ *   number per node in scratch), so the kernel boundary is the only ordering and the order of every sum is the tree's; no float atomics.  m lives in scratch.  A root
+ *   left unfinished, or a blob that is not this mesh's hierarchy, sets the header's bad word and *fault_flag_dev = 1.  The table is a function of (verts, faces) alone:
+ *   the same bytes on every run (build zeroes the padding).  256 B + 32 B per internal node, rounded up to 256 B.  F <= 1: the header alone.
+ *   tvr_mesh_winding_describe: header {uint32 magic, F, bad, 5 reserved} at `header`, rows [n_rows] x row_stride (32) B at `rows`.
+ * THE QUERY (tvr_mesh_winding_query): one lane per point, the cast's 64-entry stack per lane in LDS, 128-lane workgroups, a guarded push, a step budget of 2F - 1.
+ *   Start at the root.  An INTERNAL node with row (A, c, r, a):  d = c - q per component;  d2 = d . d;  the node is ACCEPTED iff d2 > (beta * r) * (beta * r) (two fp32
+ *   products; false for a NaN).  Accepted: the term (d . A) / (d2 * sqrt(d2)) — the dipole A . d / |d|^3 — and the subtree is left.  Otherwise the LEFT child is visited
+ *   next and the right one pushed.  A LEAF with triangle (v0, v1, v2):  a = v0 - q, b = v1 - q, c = v2 - q;  la = sqrt(a . a), lb, lc likewise;
+ *   num = a . (b x c);  den = (((la * lb) * lc + (a . b) * lc) + (b . c) * la) + (c . a) * lb;  the term 2.0f * atan2f(num, den) (Van Oosterom & Strackee 1983; atan2f
+ *   is the device library's).  A skipped triangle adds nothing.  Every term is fp32; the terms are summed in visiting order in an fp64 accumulator, and
+ *   w = (float)(sum / 12.566370614359172).  beta in [1, +inf]: beta >= 1 keeps q outside the box of every accepted node (the ball of radius r about c holds the box);
+ *   beta = +inf accepts nothing and gives the exact sum.  First- and second-order terms are NOT built.
+ *   A point with a non-finite component is refused: w = NaN, and it is counted.  F == 0: w = 0.  A point ON the surface gets a finite value, not further specified.
+ *   Points come from `points` [n_points][3] or from `lattice` exactly as in tvr_mesh_bvh_signed (the grid point is formed in the kernel).  Results do not depend on the
+ *   order or batching of the points; two runs are bit-equal.
+ *   counts_dev (int64[5], may be NULL; zeroed by the call): {points answered, points refused, node visits (internal nodes whose row was tested), dipole terms,
+ *   triangle terms}.  Index and blob checks as for the casts; a table whose header does not carry this mesh's F, or is marked bad, raises the fault flag and every
+ *   point gets NaN.
+ * Errors, all before any launch: TVR_ERR_INVALID for a NULL pointer where data is due, a negative count, a misaligned blob, table or scratch (256 B), beta below 1 or NaN,
+ *   both or neither of points / lattice with points to answer, a negative lattice dimension, a non-finite lattice origin or spacing; TVR_ERR_UNSUPPORTED for counts beyond
+ *   the hierarchy's; TVR_ERR_SCRATCH for an undersized blob, scratch or output and for a table whose size is not exactly tvr_mesh_winding_bytes(n_triangles). */
+typedef struct {
+    size_t header, rows, total;                            /* byte offsets from the table's start; total == tvr_mesh_winding_bytes */
+    size_t row_stride, n_rows;                             /* 32 bytes per internal node; n_rows = max(n_triangles - 1, 0) */
+} tvr_mesh_winding_layout;
+size_t tvr_mesh_winding_bytes(int64_t n_triangles);
+size_t tvr_mesh_winding_scratch_bytes(int64_t n_triangles);
+int tvr_mesh_winding_describe(int64_t n_triangles, tvr_mesh_winding_layout *out);
+int tvr_mesh_winding_build(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, void *table,
+                           size_t table_bytes, void *scratch, size_t scratch_bytes, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_winding_query(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const void *table,
+                           size_t table_bytes, const float *points, int64_t n_points, const tvr_mesh_lattice *lattice, float beta, float *w, size_t w_bytes,
+                           int64_t *counts_dev /* [5] or NULL */, uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

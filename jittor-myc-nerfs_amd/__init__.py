@@ -14,5 +14,6 @@ from .mesh import atlas_points, atlas_shape, atlas_uv, read_obj, sample_texture,
 from .mesh import MeshBVH, ambient_occlusion, build_bvh, cast_rays, fibonacci_sphere  # noqa: F401
 from .mesh import closest_points, mesh_distance, surface_samples  # noqa: F401
 from .mesh import build_pseudonormals, contains, signed_distance, signed_distance_grid, signed_mesh_distance  # noqa: F401
+from .mesh import build_winding, remesh_watertight, signed_distance_winding, winding_contains, winding_number, winding_number_grid  # noqa: F401
 from .training import GradBucket, make_graphed_step, shard_batch  # noqa: F401
 from . import mesh, ngp, rays, synthetic  # noqa: F401

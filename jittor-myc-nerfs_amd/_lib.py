@@ -99,6 +99,10 @@ class MeshPseudonormalsLayout(C.Structure):     # tvr_mesh_pseudonormals_layout
     _fields_ = [(n, C.c_size_t) for n in ("header", "face_n", "edge_n", "vert_n", "total", "face_stride", "edge_stride", "vert_stride")]
 
 
+class MeshWindingLayout(C.Structure):   # tvr_mesh_winding_layout
+    _fields_ = [(n, C.c_size_t) for n in ("header", "rows", "total", "row_stride", "n_rows")]
+
+
 class MeshLattice(C.Structure):         # tvr_mesh_lattice
     _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_int32 * 3)]
 
@@ -261,6 +265,13 @@ SYMBOLS = {
     "tvr_mesh_bvh_signed": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64,
                                       C.POINTER(MeshLattice), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_mesh_winding_bytes": (C.c_size_t, [C.c_int64]),
+    "tvr_mesh_winding_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "tvr_mesh_winding_describe": (C.c_int, [C.c_int64, C.POINTER(MeshWindingLayout)]),
+    "tvr_mesh_winding_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]),
+    "tvr_mesh_winding_query": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64,
+                                         C.POINTER(MeshLattice), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/tvr_ngp.h
     "tvr_ngp_update_bitfield": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tvr_ngp_sample_scratch_bytes": (C.c_size_t, [C.c_int64]),

@@ -2649,3 +2649,82 @@ int tvr_mesh_bvh_signed(const float *verts, int64_t n_vertices, const int32_t *f
                                    fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- node moments beside the hierarchy and the winding-number query (tvr_mesh_winding.hip) ------------------------------------------------------------------------------------
+size_t tvr_mesh_winding_bytes(int64_t n_triangles)
+{
+    if (bvh_counts(__func__, n_triangles) != TVR_OK) return 0;
+    return mesh_winding_bytes(n_triangles, nullptr);
+}
+
+size_t tvr_mesh_winding_scratch_bytes(int64_t n_triangles)
+{
+    if (bvh_counts(__func__, n_triangles) != TVR_OK) return 0;
+    return mesh_winding_scratch_bytes(n_triangles);
+}
+
+int tvr_mesh_winding_describe(int64_t n_triangles, tvr_mesh_winding_layout *out)
+{
+    if (!out) return fail(TVR_ERR_INVALID, "%s: out is NULL", __func__);
+    const int rc = bvh_counts(__func__, n_triangles);
+    if (rc != TVR_OK) return rc;
+    MeshWindingCarve c;
+    mesh_winding_bytes(n_triangles, &c);
+    out->header = c.header; out->rows = c.rows; out->total = c.total;
+    out->row_stride = 8 * sizeof(float);
+    out->n_rows = n_triangles ? (size_t)n_triangles - 1 : 0;
+    return TVR_OK;
+}
+
+int tvr_mesh_winding_build(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, void *table,
+                           size_t table_bytes, void *scratch, size_t scratch_bytes, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    rc = bvh_buffer(__func__, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+    if (rc != TVR_OK) return rc;
+    rc = bvh_buffer(__func__, "table", table, table_bytes, mesh_winding_bytes(n_triangles, nullptr), "tvr_mesh_winding_bytes");
+    if (rc != TVR_OK) return rc;
+    rc = bvh_buffer(__func__, "scratch", scratch, scratch_bytes, mesh_winding_scratch_bytes(n_triangles), "tvr_mesh_winding_scratch_bytes");
+    if (rc != TVR_OK) return rc;
+    HIP_TRY(launch_mesh_winding_build(verts, n_vertices, faces, n_triangles, bvh, table, scratch, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_winding_query(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, const void *table,
+                           size_t table_bytes, const float *points, int64_t n_points, const tvr_mesh_lattice *lattice, float beta, float *w, size_t w_bytes,
+                           int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    int rc = bvh_mesh(__func__, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", __func__);
+    if (!(beta >= 1.0f)) return fail(TVR_ERR_INVALID, "%s: beta = %g must lie in 1 .. +inf (+inf = the exact sum)", __func__, (double)beta);
+    if (points && lattice) return fail(TVR_ERR_INVALID, "%s: both points and lattice are given", __func__);
+    if (lattice) {
+        for (int k = 0; k < 3; ++k) {
+            if (lattice->dims[k] < 0) return fail(TVR_ERR_INVALID, "%s: lattice dims[%d] = %d is negative", __func__, k, (int)lattice->dims[k]);
+            if (!std::isfinite(lattice->origin[k]) || !std::isfinite(lattice->spacing[k]))
+                return fail(TVR_ERR_INVALID, "%s: lattice origin[%d] = %g / spacing[%d] = %g is not finite", __func__, k, (double)lattice->origin[k], k,
+                            (double)lattice->spacing[k]);
+        }
+        const double total = (double)lattice->dims[0] * (double)lattice->dims[1] * (double)lattice->dims[2];
+        if (total > (double)INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: the lattice holds %.0f points: at most 2^31 - 1 per call", __func__, total);
+        n_points = (int64_t)lattice->dims[0] * lattice->dims[1] * lattice->dims[2];
+    }
+    if (n_points < 0) return fail(TVR_ERR_INVALID, "%s: n_points = %lld is negative", __func__, (long long)n_points);
+    if (n_points > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_points = %lld: at most 2^31 - 1 points per call", __func__, (long long)n_points);
+    rc = bvh_buffer(__func__, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+    if (rc != TVR_OK) return rc;
+    const size_t want = mesh_winding_bytes(n_triangles, nullptr);
+    rc = bvh_buffer(__func__, "table", table, table_bytes, want, "tvr_mesh_winding_bytes");
+    if (rc != TVR_OK) return rc;
+    if (table_bytes != want)
+        return fail(TVR_ERR_SCRATCH, "%s: table holds %zu B, the table of %lld triangles is %zu B: it belongs to another mesh", __func__, table_bytes,
+                    (long long)n_triangles, want);
+    if (n_points > 0 && ((!points && !lattice) || !w)) return fail(TVR_ERR_INVALID, "%s: points (or lattice) / w is NULL with %lld points", __func__, (long long)n_points);
+    NEED("w [n_points]", w_bytes, n_points, 1);
+    HIP_TRY(launch_mesh_winding_query(verts, n_vertices, faces, n_triangles, bvh, table, points, lattice ? lattice->origin : nullptr, lattice ? lattice->spacing : nullptr,
+                                      lattice ? lattice->dims : nullptr, n_points, beta, w, (unsigned long long *)counts_dev, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

@@ -332,3 +332,24 @@ hipError_t launch_mesh_pseudo_build(const float *verts, long long n_vertices, co
 hipError_t launch_mesh_bvh_signed(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const void *table, const float *points,
                                   const float *origin, const float *spacing, const int *dims, long long n_points, float max_dist, float *sdist, int *tri, float *bary,
                                   signed char *feature, unsigned long long *counts, unsigned *fault, hipStream_t stream);
+
+// tvr_mesh_winding.hip: the table of node moments beside a hierarchy and the winding-number query (include/tvr.h tvr_mesh_winding_*).  The blob: a header
+// of MESH_WINDING_HEADER_BYTES, then one row of 8 fp32 per internal node (A xyz, c xyz, r, a), rounded up to 256 B.  The build's scratch: one pass word and four fp32
+// (the unnormalised moment) per internal node.  The host has checked counts, pointers, sizes and alignment.
+#define MESH_WINDING_HEADER_BYTES 256
+#define MESH_WINDING_MAGIC 0x4e575654u
+struct MeshWindingHeader {              // at the blob's start
+    unsigned magic, F, bad, reserved[5];
+};
+struct MeshWindingCarve {
+    size_t header, rows, total;
+};
+size_t mesh_winding_bytes(long long n_triangles, MeshWindingCarve *carve);
+size_t mesh_winding_scratch_bytes(long long n_triangles);
+hipError_t launch_mesh_winding_build(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, void *table, void *scratch,
+                                     unsigned *fault, hipStream_t stream);
+// points == nullptr selects the lattice (origin, spacing, dims; n_points = dims[0] * dims[1] * dims[2])
+hipError_t launch_mesh_winding_query(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const void *table,
+                                     const float *points, const float *origin, const float *spacing, const int *dims, long long n_points, float beta, float *w,
+                                     unsigned long long *counts, unsigned *fault, hipStream_t stream);
+

@@ -13,6 +13,7 @@
 //            padded lower bound of their squared distance; a (point, triangle) pair by Ericson's regions in the frame translated to the point
 //   signed   the same walk, then the sign from the pseudo-normal of the feature under the closest point (tvr_mesh_pseudo.hip's table; mesh.signed_distance,
 //            DESIGN.md §4.19); the points come from an array or from a lattice
+//   (the winding numbers of DESIGN.md §4.20 walk the same blob from tvr_mesh_winding.hip; tvr_mesh_bvh_tree.h holds what the two files share)
 //
 // REFIT.  No workgroup hands data to another inside a launch.  `pass` [F-1] holds, per internal node, the number of the launch that computed its box (0 = not yet; leaves
 // count as pass 1).  Launch p = 2 .. 63 computes a node iff it has no box and both children carry a pass number in 1 .. p-1, i.e. were finished by an EARLIER launch:
@@ -22,31 +23,9 @@
 //
 // Every index read from the blob or the faces is compared with its bound before it is used (node < 2F-1, leaf < F, triangle < F, vertex < V) and every stack push with
 // the stack's size: no load or store leaves the caller's buffers whatever the blob, the keys and the faces hold.
-#include "tvr_kernels.h"
+#include "tvr_mesh_bvh_tree.h"          // the blob's header, BvTree, BvLattice, bv_finite, bv_dot, bv_tree, bv_blob_ok: shared with tvr_mesh_winding.hip
 
-#define BV_THREADS 256
-#define BV_CAST_THREADS 128
-#define BV_STACK 64
-#define BV_PASSES 62
 #define BV_PAD 3.0517578125e-05f        // 2^-15: the slab test's relative widening
-
-typedef unsigned long long u64;
-
-struct BvHeader {                       // MESH_BVH_HEADER_BYTES at the blob's start
-    unsigned magic, F, bad, height, skipped, reserved[3];
-    float lo[3], hi[3];                 // the root's box
-};
-#define BV_MAGIC 0x48564254u
-
-struct BvTree {
-    BvHeader *h;
-    float *box;                         // [2F-1][6]: internal nodes 0 .. F-2, then the leaves in key order
-    int *child;                         // [F-1][2]
-    int *leaf_tri;                      // [F]
-    unsigned F, V;
-    const float *verts;
-    const int *faces;
-};
 
 struct BvBuildScratch {
     unsigned *header;                   // [64]: word 0 bad, word 1 skipped triangles
@@ -54,10 +33,6 @@ struct BvBuildScratch {
     unsigned *seen;                     // [(F+31)/32] bits
 };
 
-static size_t bv_align(size_t v) { return (v + 255) / 256 * 256; }
-
-__device__ __forceinline__ bool bv_finite(float x) { return fabsf(x) <= 3.4028234664e38f; }
-__device__ __forceinline__ float bv_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 // order-preserving image of a float in the unsigned integers (for atomicMin / atomicMax)
 __device__ __forceinline__ unsigned bv_order(float x) { const unsigned u = __float_as_uint(x); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float bv_unorder(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
@@ -273,19 +248,6 @@ size_t mesh_bvh_scratch_bytes(long long F)
     return 256 + bv_align((n ? n - 1 : 0) * sizeof(unsigned)) + bv_align((n + 31) / 32 * sizeof(unsigned));
 }
 
-static BvTree bv_tree(const float *verts, long long V, const int *faces, long long F, void *bvh)
-{
-    MeshBvhCarve L;
-    mesh_bvh_bytes(F, &L);
-    BvTree T;
-    T.h = (BvHeader *)bvh;
-    T.box = (float *)((char *)bvh + L.box);
-    T.child = (int *)((char *)bvh + L.child);
-    T.leaf_tri = (int *)((char *)bvh + L.leaf_tri);
-    T.F = (unsigned)F; T.V = (unsigned)V; T.verts = verts; T.faces = faces;
-    return T;
-}
-
 hipError_t launch_mesh_bvh_keys(const float *verts, long long V, const int *faces, long long F, unsigned long long *keys, void *scratch, unsigned *fault, hipStream_t stream)
 {
     const unsigned fb = (unsigned)((F + BV_THREADS - 1) / BV_THREADS);
@@ -468,13 +430,6 @@ __device__ __forceinline__ void bv_count(unsigned long long *__restrict__ counts
         if (node_tests) atomicAdd(counts + 2, (unsigned long long)node_tests);
         if (tri_tests) atomicAdd(counts + 3, (unsigned long long)tri_tests);
     }
-}
-
-__device__ __forceinline__ bool bv_blob_ok(const BvTree &T, unsigned *__restrict__ fault)
-{
-    const bool ok = T.h->magic == BV_MAGIC && T.h->F == T.F && T.h->bad == 0u;
-    if (!ok && threadIdx.x == 0) *fault = 1u;
-    return ok;
 }
 
 template <bool ANY>
@@ -681,11 +636,6 @@ __global__ __launch_bounds__(BV_CAST_THREADS) void bv_nearest_kernel(BvTree T, c
 struct BvNormals {                                   // the pseudo-normal table of tvr_mesh_pseudo.hip
     const MeshPseudoHeader *h;
     const float *face_n, *edge_n, *vert_n;           // [F][3], [F][3][3], [V][3]
-};
-
-struct BvLattice {                                   // points == nullptr: point i = (ix * ny + iy) * nz + iz sits at origin + index * spacing
-    float ox, oy, oz, sx, sy, sz;
-    unsigned ny, nz;
 };
 
 __device__ __forceinline__ bool bv_table_ok(const BvTree &T, const BvNormals &P, unsigned *__restrict__ fault)

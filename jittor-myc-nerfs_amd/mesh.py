@@ -836,6 +836,7 @@ class MeshBVH:
     def __init__(self, blob, verts, faces, height, triangles_skipped):
         self.blob, self.verts, self.faces, self.height, self.triangles_skipped = blob, verts, faces, int(height), int(triangles_skipped)
         self.pseudonormals = None       # the MeshPseudonormals of this mesh once build_pseudonormals was asked for it (signed_distance needs it)
+        self.winding = None             # the MeshWinding of this hierarchy once build_winding was asked for it (winding_number needs it)
 
     @property
     def n_triangles(self) -> int:
@@ -1348,3 +1349,185 @@ def signed_statistics(sdist: torch.Tensor, weights: torch.Tensor, unit: float = 
     nan = torch.full((), float("nan"), dtype=torch.float64, device=sdist.device)
     total = w.sum()
     return torch.stack([torch.where(total > 0, (w * d).sum() / total, nan), torch.where(total > 0, (w * (d < 0).to(torch.float64)).sum() / total, nan)])
+
+
+# ---- winding numbers: inside / outside for any soup, and a watertight remesh (csrc/tvr_mesh_winding.hip; include/tvr.h tvr_mesh_winding_*) -------------------
+BVH_WINDING_CHUNK = 1 << 24     # points per tvr_mesh_winding_query call of winding_number (results do not depend on it)
+WINDING_COUNTS = ("points_answered", "points_refused", "node_visits", "dipole_terms", "triangle_terms")
+
+
+class MeshWinding:
+    """What build_winding keeps on a MeshBVH: the table of node moments (uint8 blob on the device; winding_layout)."""
+
+    def __init__(self, blob):
+        self.blob = blob
+
+
+def winding_layout(n_triangles: int) -> dict:
+    """tvr_mesh_winding_describe(F) as a dict (header / rows / total offsets, row_stride, n_rows).  Host only."""
+    lay = L.MeshWindingLayout()
+    L.check(L.lib().tvr_mesh_winding_describe(int(n_triangles), C.byref(lay)), "tvr_mesh_winding_describe")
+    return {n: int(getattr(lay, n)) for n, _ in L.MeshWindingLayout._fields_}
+
+
+def build_winding(bvh: MeshBVH, stats: dict = None) -> MeshWinding:
+    """The table of node moments of a hierarchy, built once and kept as bvh.winding: per internal node the summed area vector of the triangles below it, their
+    area-weighted centroid, the radius about it that holds the node's box, and the summed area — what lets winding_number replace a far subtree by one dipole.
+
+    The sums are formed bottom-up, (left child) + (right child), in kernel-separated passes as the hierarchy's boxes are: no float atomics, the same bytes on every
+    run.  `stats` (a dict) receives internal_nodes and table_bytes.  No CPU fallback."""
+    b = _bvh_arg(bvh, "build_winding")
+    if b.winding is None:
+        V, F, dev, lib = b.n_vertices, b.n_triangles, b.device, L.lib()
+        nblob, nscratch = lib.tvr_mesh_winding_bytes(F), lib.tvr_mesh_winding_scratch_bytes(F)
+        if nblob == 0 or nscratch == 0:
+            raise L.TvrError("build_winding: " + lib.tvr_last_error().decode(errors="replace"))
+        blob = L.dev_bytes(nblob, dev, what="mesh winding table")
+        scratch = L.dev_bytes(nscratch, dev, what="mesh winding scratch")
+        flag = L.dev_bytes(4, dev, zero=True, what="mesh winding fault flag").view(torch.int32)
+        L.check(lib.tvr_mesh_winding_build(_ptr(b.verts), V, _ptr(b.faces), F, b.blob.data_ptr(), L.nbytes(b.blob), blob.data_ptr(), L.nbytes(blob), scratch.data_ptr(),
+                                           L.nbytes(scratch), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_winding_build")
+        if int(flag.item()) != 0:
+            raise L.TvrError("tvr_mesh_winding_build raised its fault flag: the blob is not this mesh's hierarchy, or the passes did not reach the root (include/tvr.h)")
+        b.winding = MeshWinding(blob)
+    if stats is not None:
+        stats.update(internal_nodes=max(b.n_triangles - 1, 0), table_bytes=int(b.winding.blob.numel()))
+    return b.winding
+
+
+def _winding_beta(beta, what: str) -> float:
+    beta = float(beta)
+    if not beta >= 1.0:
+        raise L.TvrError(f"{what}: beta = {beta} must lie in 1 .. +inf (+inf = the exact sum)")
+    return beta
+
+
+def _winding_stats(stats, total):
+    if stats is not None:
+        stats.update(zip(WINDING_COUNTS, (int(x) for x in total.cpu().tolist())))
+
+
+_WINDING_FAULT = ("tvr_mesh_winding_query raised its fault flag: the hierarchy or the winding table does not belong to this mesh, or a face index lies outside the "
+                  "vertices (include/tvr.h)")
+
+
+def winding_number(bvh: MeshBVH, points, beta: float = 2.0, stats: dict = None) -> torch.Tensor:
+    """The generalized winding number of a mesh at every point -> w [N] float32 on the device: 1 inside a closed outward-oriented shell, 0 outside, k inside k
+    overlapping shells, and a smooth value in between where the soup has holes — defined for ANY triangle soup (open, non-manifold, self-intersecting, unwelded),
+    where signed_distance refuses or answers wrongly.
+
+    One walk of the hierarchy per point: a subtree whose centroid is farther than beta x its radius is replaced by one dipole (build_winding's table, built here when
+    absent), a leaf adds its triangle's exact solid angle.  beta in [1, inf]: larger is more accurate and slower, inf is the exact sum (DESIGN.md §4.20 has the
+    measured error).  A point with a non-finite component gets NaN and is counted.  Results do not depend on the order or batching of the points.  No CPU fallback.
+    `stats` (a dict) receives points_answered / points_refused / node_visits / dipole_terms / triangle_terms."""
+    b = _bvh_arg(bvh, "winding_number")
+    dev = b.device
+    p = _rays_on_device(points, dev, "winding_number", "points")
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise L.TvrError(f"winding_number takes points [N, 3]; got {tuple(p.shape)}")
+    beta = _winding_beta(beta, "winding_number")
+    table = build_winding(b)
+    p = p.contiguous()
+    N, lib = int(p.shape[0]), L.lib()
+    w = L.dev_empty((N,), torch.float32, dev, what="mesh winding numbers")
+    counts = L.dev_empty((5,), torch.int64, dev, what="mesh winding counts")
+    total = torch.zeros(5, dtype=torch.int64, device=dev)
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh winding fault flag").view(torch.int32)
+    for i0 in range(0, max(N, 1), BVH_WINDING_CHUNK):
+        n = min(BVH_WINDING_CHUNK, N - i0)
+        pc, wc = p[i0:i0 + n], w[i0:i0 + n]
+        L.check(lib.tvr_mesh_winding_query(_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), table.blob.data_ptr(),
+                                           L.nbytes(table.blob), _ptr(pc), n, None, beta, _ptr(wc), L.nbytes(wc), counts.data_ptr() if stats is not None else None,
+                                           flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_winding_query")
+        if stats is not None:
+            total += counts
+    if int(flag.item()) != 0:
+        raise L.TvrError(_WINDING_FAULT)
+    _winding_stats(stats, total)
+    return w
+
+
+def winding_contains(bvh: MeshBVH, points, beta: float = 2.0) -> torch.Tensor:
+    """Which points lie inside a mesh, whatever its defects -> [N] bool on the device: winding_number(bvh, points, beta) > 0.5.  A refused point is not inside."""
+    return winding_number(bvh, points, beta) > 0.5
+
+
+def winding_number_grid(bvh: MeshBVH, dims, origin=(0, 0, 0), spacing=(1, 1, 1), beta: float = 2.0, stats: dict = None) -> torch.Tensor:
+    """The winding-number field of a mesh on a lattice -> volume [nx, ny, nz] float32 on the device, laid out as marching_cubes reads its volume.
+
+    Grid point (i, j, k) sits at origin + (i, j, k) * spacing, formed in the kernel in fp32 (one product, one sum per axis): no point tensor is materialised, and the
+    values are bit-equal to winding_number on the same points.  marching_cubes(volume, 0.5, spacing, origin) extracts one closed, outward-oriented surface.  dims [3]
+    with at most 2^31 - 1 grid points.  beta, `stats` as for winding_number.  No CPU fallback."""
+    b = _bvh_arg(bvh, "winding_number_grid")
+    dev = b.device
+    dims = [int(x) for x in dims]
+    if len(dims) != 3 or min(dims) < 0 or dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
+        raise L.TvrError(f"winding_number_grid takes dims [3] of non-negative sizes with at most 2^31 - 1 grid points; got {dims}")
+    beta = _winding_beta(beta, "winding_number_grid")
+    table = build_winding(b)
+    lat = L.MeshLattice()
+    lat.origin[:], lat.spacing[:], lat.dims[:] = [float(x) for x in origin], [float(x) for x in spacing], dims
+    vol = L.dev_empty(tuple(dims), torch.float32, dev, what="mesh winding volume")
+    counts = L.dev_empty((5,), torch.int64, dev, what="mesh winding counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh winding fault flag").view(torch.int32)
+    L.check(L.lib().tvr_mesh_winding_query(_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), table.blob.data_ptr(),
+                                           L.nbytes(table.blob), None, 0, C.byref(lat), beta, _ptr(vol), L.nbytes(vol), counts.data_ptr() if stats is not None else None,
+                                           flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_winding_query")
+    if int(flag.item()) != 0:
+        raise L.TvrError(_WINDING_FAULT)
+    _winding_stats(stats, counts)
+    return vol
+
+
+def signed_distance_winding(bvh: MeshBVH, points, max_dist: float = float("inf"), beta: float = 2.0, stats: dict = None):
+    """The signed distance of every point to a mesh that need not be closed -> (sdist [N] float32, tri [N] int32, bary [N,3] float32) on the device.
+
+    |sdist|, tri and bary are closest_points' answers, bit for bit; sdist is negative where winding_contains says inside, +0.0 on the surface, +inf where closest_points
+    gives +inf.  Unlike signed_distance the sign does not come from the closest feature's normal, so it holds for overlapping shells, soups and meshes with holes.
+    `stats` (a dict) receives closest_points' counts and node_visits / dipole_terms / triangle_terms of the winding walk.  No CPU fallback."""
+    b = _bvh_arg(bvh, "signed_distance_winding")
+    beta = _winding_beta(beta, "signed_distance_winding")
+    near, wind = ({}, {}) if stats is not None else (None, None)
+    dist, tri, bary = closest_points(b, points, max_dist, stats=near)
+    inside = winding_number(b, points, beta, stats=wind) > 0.5
+    if stats is not None:
+        stats.update(near, node_visits=wind["node_visits"], dipole_terms=wind["dipole_terms"], triangle_terms=wind["triangle_terms"])
+    return torch.where(inside & (dist > 0) & torch.isfinite(dist), -dist, dist), tri, bary       # (+inf beyond max_dist stays +inf)
+
+
+def remesh_watertight(verts, faces, resolution: int = 256, voxel: float = None, pad: int = 2, beta: float = 2.0, level: float = 0.5, stats: dict = None):
+    """Any triangle soup -> (verts [V,3] float32, faces [F,3] int32) of ONE closed, outward-oriented surface, on the device: the `level` set of the soup's winding
+    number field, extracted by marching_cubes.  Overlapping components are unioned, internal walls disappear, small holes are bridged, unwelded corners are welded.
+
+    The lattice is the bounding box of the soup's finite vertices, grown by `pad` cubic voxels on every side; `voxel` defaults to the longest box edge / `resolution`.
+    Every vertex of the result lies within one voxel of the input surface wherever the field jumps across it.  `stats` (a dict) receives dims, voxel, origin, the
+    closedness counters of the input and of the result (input / result: build_pseudonormals' counters and closed) and the result's component count.  No CPU fallback."""
+    v, f = _mesh_on_device(verts, faces, "remesh_watertight")
+    beta = _winding_beta(beta, "remesh_watertight")
+    pad = int(pad)
+    if pad < 1:
+        raise L.TvrError(f"remesh_watertight: pad = {pad} must be at least 1 (the surface must not touch the lattice's border)")
+    fin = v[torch.isfinite(v).all(1)]
+    if f.shape[0] == 0 or fin.shape[0] == 0:
+        raise L.TvrError("remesh_watertight: the mesh has no triangle or no finite vertex")
+    lo, hi = fin.min(0)[0].double().cpu().numpy(), fin.max(0)[0].double().cpu().numpy()
+    if voxel is None:
+        if int(resolution) < 1:
+            raise L.TvrError(f"remesh_watertight: resolution = {resolution} must be at least 1")
+        voxel = float((hi - lo).max()) / int(resolution)
+    voxel = float(voxel)
+    if not (voxel > 0.0 and np.isfinite(voxel)):
+        raise L.TvrError(f"remesh_watertight: voxel = {voxel} must be a finite number > 0 (a mesh without extent has no surface to extract)")
+    origin = [float(x) for x in lo - pad * voxel]
+    dims = [int(np.ceil(float(e) / voxel)) + 1 + 2 * pad for e in hi - lo]
+    bvh = build_bvh(v, f)
+    vol = winding_number_grid(bvh, dims, origin, (voxel,) * 3, beta)
+    ov, of = marching_cubes(vol, float(level), (voxel,) * 3, origin)
+    if stats is not None:
+        cin, cout = {}, {}
+        build_pseudonormals(bvh, stats=cin)
+        build_pseudonormals(build_bvh(ov, of), stats=cout)
+        keep = CLOSEDNESS_COUNTERS + ("closed",)
+        stats.update(dims=dims, voxel=voxel, origin=origin, input={k: cin[k] for k in keep}, result={k: cout[k] for k in keep},
+                     components=mesh_components(of, int(ov.shape[0]))[2] if int(ov.shape[0]) else 0)
+    return ov, of

@@ -108,6 +108,12 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # and inside_fraction, and under "closedness" each target's degenerate / open / non-manifold / inconsistent counters; a target that is not closed gets null for
     # both keys and "signed_reason"; 0 = the JSON as it always was
     p.add_argument("--mesh_compare_signed", type=int, default=0)
+    # make a mesh watertight (mesh.remesh_watertight): R > 0 = the 0.5 level set of the mesh's winding-number field on a lattice of R voxels along the longest edge of its
+    # bounding box — one closed, outward-oriented surface whatever the input's holes, overlaps and unwelded corners; with --export_mesh 1 the mesh just written is taken,
+    # without it --mesh_file (no checkpoint needed); writes <mesh minus extension>_watertight.ply and _watertight.json; --mesh_watertight_beta B is the accuracy of the
+    # winding walk (>= 1, inf = exact); 0 = off
+    p.add_argument("--mesh_watertight", type=int, default=0)
+    p.add_argument("--mesh_watertight_beta", type=float, default=2.0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     # (not a reference option) views of an exported mesh beside the rendered test views (mesh.render_mesh): with --render_only 1 --render_test 1, read --mesh_file
@@ -344,6 +350,34 @@ def mesh_compare(args, path, device="cuda"):
     return out
 
 
+@torch.no_grad()
+def mesh_watertight(args, path, device="cuda"):
+    """--mesh_watertight R: mesh.remesh_watertight of the mesh at `path` on R voxels along its longest box edge -> <path minus extension>_watertight.ply, and
+    <path minus extension>_watertight.json with the lattice (dims, voxel, origin), the closedness counters of the input and of the result, the result's component
+    count and mesh.mesh_distance of the result (A) against the input (B) in world units and in voxels of the remesh.  Returns the path of the JSON."""
+    import json
+    from .mesh import mesh_distance, remesh_watertight, write_ply
+    v, f = _read_mesh_geometry(path)
+    tv, tf = (torch.from_numpy(np.ascontiguousarray(x)).to(device) for x in (v, f))
+    st = {}
+    ov, of = remesh_watertight(tv, tf, resolution=int(args.mesh_watertight), beta=float(args.mesh_watertight_beta), stats=st)
+    base = os.path.splitext(path)[0]
+    write_ply(base + "_watertight.ply", ov, of)
+    report = {"mesh_file": path, "watertight_file": base + "_watertight.ply", "vertices": int(len(v)), "triangles": int(len(f)), "watertight_vertices": int(ov.shape[0]),
+              "watertight_triangles": int(of.shape[0]), "resolution": int(args.mesh_watertight), "beta": float(args.mesh_watertight_beta), "level": 0.5, **st,
+              "a_is": "watertight_file", "b_is": "mesh_file", "subdiv": 2}
+    if int(of.shape[0]):
+        report["world"] = mesh_distance(ov, of, tv, tf)
+        report["voxels"] = mesh_distance(ov, of, tv, tf, unit=st["voxel"])
+    out = base + "_watertight.json"
+    with open(out, "w") as fjson:
+        json.dump(report, fjson, indent=1)
+    print(f"watertight remesh of {path}: {report['watertight_triangles']} triangles on {st['dims']} grid points, voxel {st['voxel']:.6g}, "
+          f"{st['components']} component(s), closed: {st['result']['closed']} (the input: {st['input']['closed']})"
+          + (f"; hausdorff to the input {report['voxels']['hausdorff']:.3f} voxels" if "voxels" in report else ""))
+    return out
+
+
 FAULT_POLL_EVERY = 16       # iterations between two reads of the training-fault accumulator (field.check_training_faults)
 
 
@@ -520,11 +554,20 @@ def main(cmd: Optional[List[str]] = None):
     if getattr(args, "mesh_compare", None) and not args.export_mesh:
         if not getattr(args, "mesh_file", None):
             raise SystemExit("--mesh_compare REF compares the mesh of --export_mesh 1, or the one --mesh_file names: neither was given; nothing was done")
-        return mesh_compare(args, args.mesh_file)
+        out = mesh_compare(args, args.mesh_file)
+        if getattr(args, "mesh_watertight", 0):
+            mesh_watertight(args, args.mesh_file)
+        return out
+    if getattr(args, "mesh_watertight", 0) and not args.export_mesh:
+        if not getattr(args, "mesh_file", None):
+            raise SystemExit("--mesh_watertight R remeshes the mesh of --export_mesh 1, or the one --mesh_file names: neither was given; nothing was done")
+        return mesh_watertight(args, args.mesh_file)
     if args.export_mesh:
         path = export_mesh(args)
         if getattr(args, "mesh_compare", None):
             mesh_compare(args, path)
+        if getattr(args, "mesh_watertight", 0):
+            mesh_watertight(args, path)
         if not (args.render_only and (args.render_test or args.render_path)):
             return path
     if args.render_only and (args.render_test or args.render_path):
