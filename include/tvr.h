@@ -1152,6 +1152,53 @@ int tvr_mesh_winding_query(const float *verts, int64_t n_vertices, const int32_t
                            size_t table_bytes, const float *points, int64_t n_points, const tvr_mesh_lattice *lattice, float beta, float *w, size_t w_bytes,
                            int64_t *counts_dev /* [5] or NULL */, uint32_t *fault_flag_dev, void *stream);
 
+/* Which triangles cut through which: the triangle-pair query on the hierarchy above (csrc/tvr_mesh_crossings.hip; mesh.self_intersections / mesh_intersections /
+ * mesh_check).  ADDITIVE exports: TVR_VERSION is unchanged.  DESIGN.md §4.21.  Arithmetic as above: fp32, every operation rounded on its own (no fused multiply-add), in
+ * the order written, divisions IEEE correctly rounded, the dot and cross products of tvr_mesh_bvh_cast.
+ * SEGMENT: side k of a triangle runs between corner (k+1)%3 and corner (k+2)%3, oriented from the smaller vertex index u to the larger v:  o = verts[u],
+ *   d = verts[v] - verts[u] per axis.  (The orientation depends on the indices alone, so the two triangles on an edge test the same segment.)
+ * (SEGMENT, TRIANGLE) PIERCING: the (RAY, TRIANGLE) pair of tvr_mesh_bvh_cast applied to (o, d) with t_min = 0, t_max = 1, cull off — so 0 < t <= 1 — the ownership rule
+ *   and everything else as they stand there.  The piercing point is (o.x + t * d.x, o.y + t * d.y, o.z + t * d.z).  LIMIT: a segment that lies in the triangle's plane
+ *   has det == 0 and never pierces, so COPLANAR OVERLAP IS NOT DETECTED; nothing is promised for a segment exactly through a vertex of the triangle.
+ * SHARING: a segment is never tested against a triangle one of whose corners has the same POSITION as one of the segment's end points (all three coordinates compare
+ *   equal).  By position, not by index: neighbours in a welded mesh, in an unwelded soup and across duplicated vertices are treated alike.  Consequence: pairs that share
+ *   an edge, and duplicate faces, are never reported; a pair that shares one vertex is tested with the sides that do not touch it.
+ * PAIR: triangles a and b CROSS iff at least one of six tests pierces, in this fixed order: sides 0, 1, 2 of a against b, then sides 0, 1, 2 of b against a.  n_pierce
+ *   is how many of the six pierce; points[0], points[1] are the first two piercing points in test order, points[1] = points[0] when n_pierce == 1.  In general position
+ *   n_pierce == 2 and the two points are the ends of the intersection segment.  A triangle with a non-finite corner, or with an index out of range, crosses nothing.
+ * SELF QUERY (mode TVR_MESH_CROSSINGS_SELF): all unordered pairs i < j of the hierarchy's mesh, a = i, b = j; verts_q / faces_q are not read and the n_*_q ignored.
+ * TWO-MESH QUERY (mode TVR_MESH_CROSSINGS_MESH): all pairs (q, a), q a triangle of the query mesh (verts_q, faces_q), a a triangle of the hierarchy's mesh; in the test
+ *   order above a = q's triangle and b = the tree's.  Sharing applies by position all the same.  Below, Nq is the number of query triangles (n_triangles in a self query).
+ * TRAVERSAL: one lane per query triangle, the cast's 64-entry stack per lane in LDS, 128-lane workgroups, a guarded push, a step budget of 2F - 1.  A node is entered iff
+ *   its box overlaps the query triangle's box (exact min / max of its corners), both widened: g_k = qlo_k - hi_k, h_k = lo_k - qhi_k per axis; m = the largest of |g|, |h|
+ *   over the axes; pad = m * 2^-15; overlap iff every g_k <= pad and h_k <= pad (and the node's box is not empty).  Both children overlapping: the left one first, the
+ *   right one pushed.  In a self query the lane of triangle i evaluates a leaf j only when j > i.  The padding is a stated margin for pairs the fp32 test reports although
+ *   the exact triangles miss each other by a rounding error, not a proof; what is tested is set-equality with a brute-force restatement of the definition.
+ * TWO PASSES, because the output's size is not known in advance (as tvr_mesh_count / _emit):
+ *   tvr_mesh_crossings_count writes count_out [Nq] int32 (how many triangles query triangle i crosses) and total_dev [1] int64 (their sum), and zeroes and fills
+ *   counts_dev (int64[4], may be NULL): {pairs, query triangles refused (a non-finite corner or an index out of range), node tests, triangle-pair tests}.  THE CALLER reads
+ *   the total and forms offsets [Nq+1] int64, the exclusive scan of count_out with the total at the end.
+ *   tvr_mesh_crossings_emit repeats the walk and writes row offsets[i] + k for the k-th pair query triangle i finds: pairs [n_pairs][2] int32 = (i, j), n_pierce [n_pairs]
+ *   int32, and points [n_pairs][2][3] fp32 unless points is NULL.  Within one query triangle the rows are in walk order, which is the same on every run; THE CALLER SORTS
+ *   the rows by the 64-bit key i << 32 | j (unique, so every correct sort gives the same order): pairs ascend by (first index, second index) and the output is the same
+ *   bytes on every run.  A lane whose walk does not find exactly offsets[i+1] - offsets[i] pairs, or whose offsets do not lie in 0 .. n_pairs in ascending order, raises
+ *   the fault flag and writes nothing outside its rows.  No float atomics; no atomics on the output order (the counters are integer sums, one atomic per wave).
+ *   Index and blob checks as for the casts: an inconsistent blob (wrong magic, F, or bad != 0) raises the fault flag and nothing is reported; no load or store leaves
+ *   the caller's buffers whatever the blob, the offsets and the faces hold.
+ * Errors, all before any launch, tvr_last_error() names the argument: TVR_ERR_INVALID for a NULL pointer where data is due, a negative count, a mode outside 0 / 1, a
+ *   misaligned blob (256 B) or offsets (8 B); TVR_ERR_UNSUPPORTED for n_vertices(_q) >= 2^31, n_triangles(_q) above TVR_MESH_BVH_MAX_TRIANGLES or n_pairs >= 2^31;
+ *   TVR_ERR_SCRATCH for an undersized blob, count_out, offsets or output.  n_triangles == 0 and n_triangles_q == 0 are valid (no pair), so is n_pairs == 0.
+ * NOT built: coplanar overlap, the intersection curve as connected polylines, repairing what is found. */
+#define TVR_MESH_CROSSINGS_SELF 0
+#define TVR_MESH_CROSSINGS_MESH 1
+int tvr_mesh_crossings_count(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, int32_t mode,
+                             const float *verts_q, int64_t n_vertices_q, const int32_t *faces_q, int64_t n_triangles_q, int32_t *count_out, size_t count_bytes,
+                             int64_t *total_dev, int64_t *counts_dev /* [4] or NULL */, uint32_t *fault_flag_dev, void *stream);
+int tvr_mesh_crossings_emit(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, int32_t mode,
+                            const float *verts_q, int64_t n_vertices_q, const int32_t *faces_q, int64_t n_triangles_q, const int64_t *offsets, size_t offsets_bytes,
+                            int64_t n_pairs, int32_t *pairs, size_t pairs_bytes, int32_t *n_pierce, size_t n_pierce_bytes, float *points /* or NULL */,
+                            size_t points_bytes, uint32_t *fault_flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,5 +15,6 @@ from .mesh import MeshBVH, ambient_occlusion, build_bvh, cast_rays, fibonacci_sp
 from .mesh import closest_points, mesh_distance, surface_samples  # noqa: F401
 from .mesh import build_pseudonormals, contains, signed_distance, signed_distance_grid, signed_mesh_distance  # noqa: F401
 from .mesh import build_winding, remesh_watertight, signed_distance_winding, winding_contains, winding_number, winding_number_grid  # noqa: F401
+from .mesh import crossing_faces, mesh_check, mesh_intersections, self_intersections, write_obj_segments  # noqa: F401
 from .training import GradBucket, make_graphed_step, shard_batch  # noqa: F401
 from . import mesh, ngp, rays, synthetic  # noqa: F401

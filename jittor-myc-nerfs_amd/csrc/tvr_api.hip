@@ -2728,3 +2728,65 @@ int tvr_mesh_winding_query(const float *verts, int64_t n_vertices, const int32_t
                                       lattice ? lattice->dims : nullptr, n_points, beta, w, (unsigned long long *)counts_dev, fault_flag_dev, (hipStream_t)stream));
     return TVR_OK;
 }
+
+// ---- the triangle-pair query on the hierarchy (tvr_mesh_crossings.hip) ----------------------------------------------------------------------------------------------------------
+// what both passes check: the hierarchy's mesh and blob, the mode, the query mesh
+static int crossings_args(const char *fn, const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, int32_t mode,
+                          const float *verts_q, int64_t n_vertices_q, const int32_t *faces_q, int64_t n_triangles_q, const uint32_t *fault_flag_dev)
+{
+    int rc = bvh_mesh(fn, verts, n_vertices, faces, n_triangles);
+    if (rc != TVR_OK) return rc;
+    if (!fault_flag_dev) return fail(TVR_ERR_INVALID, "%s: fault_flag_dev is NULL", fn);
+    if (mode != TVR_MESH_CROSSINGS_SELF && mode != TVR_MESH_CROSSINGS_MESH)
+        return fail(TVR_ERR_INVALID, "%s: mode = %d is neither 0 (self query) nor 1 (two-mesh query)", fn, (int)mode);
+    if (mode == TVR_MESH_CROSSINGS_MESH) {
+        if (n_triangles_q < 0 || n_vertices_q < 0)
+            return fail(TVR_ERR_INVALID, "%s: n_triangles_q = %lld / n_vertices_q = %lld is negative", fn, (long long)n_triangles_q, (long long)n_vertices_q);
+        if (n_triangles_q > TVR_MESH_BVH_MAX_TRIANGLES)
+            return fail(TVR_ERR_UNSUPPORTED, "%s: n_triangles_q = %lld: at most TVR_MESH_BVH_MAX_TRIANGLES = %d", fn, (long long)n_triangles_q, TVR_MESH_BVH_MAX_TRIANGLES);
+        if (n_vertices_q > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_vertices_q = %lld: vertex indices are int32", fn, (long long)n_vertices_q);
+        if (n_triangles_q > 0 && (!faces_q || !verts_q)) return fail(TVR_ERR_INVALID, "%s: faces_q / verts_q is NULL with %lld query triangles", fn, (long long)n_triangles_q);
+    }
+    return bvh_buffer(fn, "bvh", bvh, bvh_bytes, mesh_bvh_bytes(n_triangles, nullptr), "tvr_mesh_bvh_bytes");
+}
+
+int tvr_mesh_crossings_count(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, int32_t mode,
+                             const float *verts_q, int64_t n_vertices_q, const int32_t *faces_q, int64_t n_triangles_q, int32_t *count_out, size_t count_bytes,
+                             int64_t *total_dev, int64_t *counts_dev, uint32_t *fault_flag_dev, void *stream)
+{
+    const int rc = crossings_args(__func__, verts, n_vertices, faces, n_triangles, bvh, bvh_bytes, mode, verts_q, n_vertices_q, faces_q, n_triangles_q, fault_flag_dev);
+    if (rc != TVR_OK) return rc;
+    const int self = mode == TVR_MESH_CROSSINGS_SELF;
+    const int64_t nq = self ? n_triangles : n_triangles_q;
+    if (!total_dev) return fail(TVR_ERR_INVALID, "%s: total_dev is NULL", __func__);
+    if (nq > 0 && !count_out) return fail(TVR_ERR_INVALID, "%s: count_out is NULL with %lld query triangles", __func__, (long long)nq);
+    if (count_bytes < (size_t)nq * sizeof(int32_t))
+        return fail(TVR_ERR_SCRATCH, "%s: count_out holds %zu B, %lld query triangles x int32 need %zu B", __func__, count_bytes, (long long)nq, (size_t)nq * 4);
+    HIP_TRY(launch_mesh_crossings_count(verts, n_vertices, faces, n_triangles, bvh, verts_q, n_vertices_q, faces_q, n_triangles_q, self, count_out,
+                                        (unsigned long long *)total_dev, (unsigned long long *)counts_dev, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}
+
+int tvr_mesh_crossings_emit(const float *verts, int64_t n_vertices, const int32_t *faces, int64_t n_triangles, const void *bvh, size_t bvh_bytes, int32_t mode,
+                            const float *verts_q, int64_t n_vertices_q, const int32_t *faces_q, int64_t n_triangles_q, const int64_t *offsets, size_t offsets_bytes,
+                            int64_t n_pairs, int32_t *pairs, size_t pairs_bytes, int32_t *n_pierce, size_t n_pierce_bytes, float *points, size_t points_bytes,
+                            uint32_t *fault_flag_dev, void *stream)
+{
+    const int rc = crossings_args(__func__, verts, n_vertices, faces, n_triangles, bvh, bvh_bytes, mode, verts_q, n_vertices_q, faces_q, n_triangles_q, fault_flag_dev);
+    if (rc != TVR_OK) return rc;
+    const int self = mode == TVR_MESH_CROSSINGS_SELF;
+    const int64_t nq = self ? n_triangles : n_triangles_q;
+    if (n_pairs < 0) return fail(TVR_ERR_INVALID, "%s: n_pairs = %lld is negative", __func__, (long long)n_pairs);
+    if (n_pairs > INT32_MAX) return fail(TVR_ERR_UNSUPPORTED, "%s: n_pairs = %lld: at most 2^31 - 1 pairs per call", __func__, (long long)n_pairs);
+    if (nq > 0 && !offsets) return fail(TVR_ERR_INVALID, "%s: offsets is NULL with %lld query triangles", __func__, (long long)nq);
+    if ((uintptr_t)offsets % 8) return fail(TVR_ERR_INVALID, "%s: offsets is not 8-byte aligned", __func__);
+    if (nq > 0 && offsets_bytes < ((size_t)nq + 1) * sizeof(int64_t))
+        return fail(TVR_ERR_SCRATCH, "%s: offsets holds %zu B, %lld query triangles + 1 x int64 need %zu B", __func__, offsets_bytes, (long long)nq, ((size_t)nq + 1) * 8);
+    if (n_pairs > 0 && (!pairs || !n_pierce)) return fail(TVR_ERR_INVALID, "%s: pairs / n_pierce is NULL with %lld pairs", __func__, (long long)n_pairs);
+    NEED("pairs [n_pairs,2]", pairs_bytes, n_pairs, 2);
+    NEED("n_pierce [n_pairs]", n_pierce_bytes, n_pairs, 1);
+    if (points) NEED("points [n_pairs,2,3]", points_bytes, n_pairs, 6);
+    HIP_TRY(launch_mesh_crossings_emit(verts, n_vertices, faces, n_triangles, bvh, verts_q, n_vertices_q, faces_q, n_triangles_q, self, (const long long *)offsets, n_pairs,
+                                       pairs, n_pierce, points, fault_flag_dev, (hipStream_t)stream));
+    return TVR_OK;
+}

@@ -353,3 +353,13 @@ hipError_t launch_mesh_winding_query(const float *verts, long long n_vertices, c
                                      const float *points, const float *origin, const float *spacing, const int *dims, long long n_points, float beta, float *w,
                                      unsigned long long *counts, unsigned *fault, hipStream_t stream);
 
+// tvr_mesh_crossings.hip: the triangle-pair query on a hierarchy (include/tvr.h tvr_mesh_crossings_*).  self != 0: the hierarchy's own mesh is the query
+// (pairs i < j) and verts_q / faces_q are not read.  count: count_out [Fq], total [1], counts [4] or nullptr.  emit: offsets [Fq+1], pairs [n_pairs][2],
+// n_pierce [n_pairs], points [n_pairs][2][3] or nullptr.  The host has checked counts, pointers, sizes and alignment.
+hipError_t launch_mesh_crossings_count(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *verts_q,
+                                       long long n_vertices_q, const int *faces_q, long long n_triangles_q, int self, int *count_out, unsigned long long *total,
+                                       unsigned long long *counts, unsigned *fault, hipStream_t stream);
+hipError_t launch_mesh_crossings_emit(const float *verts, long long n_vertices, const int *faces, long long n_triangles, const void *bvh, const float *verts_q,
+                                      long long n_vertices_q, const int *faces_q, long long n_triangles_q, int self, const long long *offsets, long long n_pairs,
+                                      int *pairs, int *n_pierce, float *points, unsigned *fault, hipStream_t stream);
+

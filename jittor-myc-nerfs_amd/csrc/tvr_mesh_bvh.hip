@@ -1,7 +1,7 @@
 // tvr_mesh_bvh.hip — a linear bounding-volume hierarchy over the triangles of an indexed mesh and the ray queries that walk it: closest hit, any hit, and the
 // cosine-weighted openness of points on the mesh (mesh.build_bvh / cast_rays / ambient_occlusion, TensorBase.export_mesh(ao=), reconstruct --mesh_ao).  include/tvr.h
 // tvr_mesh_bvh_* holds the definition; DESIGN.md §4.17 the reasoning.  A (ray, triangle) pair is judged by the rasteriser's expressions (tvr_mesh_raster.hip rs_setup /
-// rs_pixel) with the camera rotation taken as the identity and the camera centre at the ray's origin; they are restated in bv_triangle below, fp contraction is off, and
+// rs_pixel) with the camera rotation taken as the identity and the camera centre at the ray's origin; they are restated in bv_triangle (tvr_mesh_bvh_tree.h), fp contraction is off, and
 // tests/test_gpu_mesh_bvh.py ties the two files together.
 //
 //   keys     bbox_init, bbox (finite extent of the triangles that count: a wave-level min / max, then one atomic per wave and component on order-preserving integer
@@ -13,7 +13,8 @@
 //            padded lower bound of their squared distance; a (point, triangle) pair by Ericson's regions in the frame translated to the point
 //   signed   the same walk, then the sign from the pseudo-normal of the feature under the closest point (tvr_mesh_pseudo.hip's table; mesh.signed_distance,
 //            DESIGN.md §4.19); the points come from an array or from a lattice
-//   (the winding numbers of DESIGN.md §4.20 walk the same blob from tvr_mesh_winding.hip; tvr_mesh_bvh_tree.h holds what the two files share)
+//   (the winding numbers of DESIGN.md §4.20 walk the same blob from tvr_mesh_winding.hip, the triangle pairs of §4.21 from tvr_mesh_crossings.hip; tvr_mesh_bvh_tree.h
+//   holds what the files share, bv_triangle and bv_ray — the (ray, triangle) pair — among it)
 //
 // REFIT.  No workgroup hands data to another inside a launch.  `pass` [F-1] holds, per internal node, the number of the launch that computed its box (0 = not yet; leaves
 // count as pass 1).  Launch p = 2 .. 63 computes a node iff it has no box and both children carry a pass number in 1 .. p-1, i.e. were finished by an EARLIER launch:
@@ -23,9 +24,7 @@
 //
 // Every index read from the blob or the faces is compared with its bound before it is used (node < 2F-1, leaf < F, triangle < F, vertex < V) and every stack push with
 // the stack's size: no load or store leaves the caller's buffers whatever the blob, the keys and the faces hold.
-#include "tvr_mesh_bvh_tree.h"          // the blob's header, BvTree, BvLattice, bv_finite, bv_dot, bv_tree, bv_blob_ok: shared with tvr_mesh_winding.hip
-
-#define BV_PAD 3.0517578125e-05f        // 2^-15: the slab test's relative widening
+#include "tvr_mesh_bvh_tree.h"          // the blob's header, BvTree, BvLattice, BvRay, BV_PAD, bv_finite, bv_dot, bv_tree, bv_blob_ok, bv_triangle, bv_ray: shared
 
 struct BvBuildScratch {
     unsigned *header;                   // [64]: word 0 bad, word 1 skipped triangles
@@ -286,12 +285,6 @@ hipError_t launch_mesh_bvh_build(const float *verts, long long V, const int *fac
 }
 
 // ---- traversal ------------------------------------------------------------------------------------------------------------------------------------------------------------
-struct BvRay {
-    float ox, oy, oz, dx, dy, dz, ix, iy, iz;       // origin, direction, 1 / direction
-    float t_min;
-    int cull;
-};
-
 struct BvHit {
     float t;                                         // the bound: t_max before a hit, the best t after
     unsigned tri;                                    // 0xffffffff before a hit
@@ -309,51 +302,6 @@ __device__ __forceinline__ bool bv_slab(const float *__restrict__ b, const BvRay
     tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
     const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
     return tn <= tf && tf >= r.t_min && !(tn > best) && lx <= hx;        // (an empty box has lo = +inf, hi = -inf: lx <= hx is false)
-}
-
-// (ray, triangle t): the definition of include/tvr.h, i.e. tvr_mesh_raster.hip's rs_setup / rs_pixel with R = identity, o = the ray's origin, dir = the ray's direction
-__device__ __forceinline__ bool bv_triangle(const BvTree &T, unsigned t, const BvRay &r, float t_max, float E[3], float &tt, unsigned *__restrict__ fault)
-{
-    const int *f = T.faces + (size_t)t * 3;
-    const int v0 = f[0], v1 = f[1], v2 = f[2];
-    if ((unsigned)v0 >= T.V || (unsigned)v1 >= T.V || (unsigned)v2 >= T.V) {
-        *fault = 1u;
-        return false;
-    }
-    const float *p0 = T.verts + (size_t)v0 * 3, *p1 = T.verts + (size_t)v1 * 3, *p2 = T.verts + (size_t)v2 * 3;
-    const float q0x = p0[0] - r.ox, q0y = p0[1] - r.oy, q0z = p0[2] - r.oz;
-    const float q1x = p1[0] - r.ox, q1y = p1[1] - r.oy, q1z = p1[2] - r.oz;
-    const float q2x = p2[0] - r.ox, q2y = p2[1] - r.oy, q2z = p2[2] - r.oz;
-    const float n0x = q1y * q2z - q1z * q2y, n0y = q1z * q2x - q1x * q2z, n0z = q1x * q2y - q1y * q2x;
-    const float n1x = q2y * q0z - q2z * q0y, n1y = q2z * q0x - q2x * q0z, n1z = q2x * q0y - q2y * q0x;
-    const float n2x = q0y * q1z - q0z * q1y, n2y = q0z * q1x - q0x * q1z, n2z = q0x * q1y - q0y * q1x;
-    const float det = bv_dot(q0x, q0y, q0z, n0x, n0y, n0z);
-    const bool finite = bv_finite(q0x) && bv_finite(q0y) && bv_finite(q0z) && bv_finite(q1x) && bv_finite(q1y) && bv_finite(q1z) && bv_finite(q2x) && bv_finite(q2y) &&
-                        bv_finite(q2z);
-    if (!finite || !(det > 0.0f || det < 0.0f)) return false;
-    if (r.cull && det > 0.0f) return false;
-    const float sg = det > 0.0f ? 1.0f : -1.0f;
-    const bool neg = det < 0.0f;
-    const bool own0 = (v1 < v2) != neg, own1 = (v2 < v0) != neg, own2 = (v0 < v1) != neg;
-    E[0] = sg * bv_dot(r.dx, r.dy, r.dz, n0x, n0y, n0z);
-    E[1] = sg * bv_dot(r.dx, r.dy, r.dz, n1x, n1y, n1z);
-    E[2] = sg * bv_dot(r.dx, r.dy, r.dz, n2x, n2y, n2z);
-    const bool in = (E[0] > 0.0f || (E[0] == 0.0f && own0)) && (E[1] > 0.0f || (E[1] == 0.0f && own1)) && (E[2] > 0.0f || (E[2] == 0.0f && own2));
-    if (!in) return false;
-    const float ax = q1x - q0x, ay = q1y - q0y, az = q1z - q0z, bx = q2x - q0x, by = q2y - q0y, bz = q2z - q0z;
-    const float pnx = ay * bz - az * by, pny = az * bx - ax * bz, pnz = ax * by - ay * bx;
-    const float pq = bv_dot(pnx, pny, pnz, q0x, q0y, q0z);
-    tt = pq / bv_dot(r.dx, r.dy, r.dz, pnx, pny, pnz);
-    return bv_finite(tt) && tt > r.t_min && tt <= t_max;
-}
-
-// false for a ray that never hits: a non-finite component, or d == 0
-__device__ __forceinline__ bool bv_ray(BvRay &r, float ox, float oy, float oz, float dx, float dy, float dz, float t_min, int cull)
-{
-    r.ox = ox; r.oy = oy; r.oz = oz; r.dx = dx; r.dy = dy; r.dz = dz; r.t_min = t_min; r.cull = cull;
-    r.ix = 1.0f / dx; r.iy = 1.0f / dy; r.iz = 1.0f / dz;
-    const bool fin = bv_finite(ox) && bv_finite(oy) && bv_finite(oz) && bv_finite(dx) && bv_finite(dy) && bv_finite(dz);
-    return fin && !(dx == 0.0f && dy == 0.0f && dz == 0.0f);
 }
 
 // Walk the tree for one ray.  stack: this lane's BV_STACK entries, `stride` words apart.  H.t holds t_max on entry.  Returns whether anything was hit.

@@ -168,17 +168,6 @@ __device__ __forceinline__ float wn_solid_angle(const BvTree &T, unsigned t, flo
     return 2.0f * atan2f(num, den);
 }
 
-__device__ __forceinline__ u64 wn_wave_sum(u64 x)
-{
-    unsigned lo = (unsigned)x, hi = (unsigned)(x >> 32);
-    for (int o = 32; o; o >>= 1) {
-        const unsigned l2 = (unsigned)__shfl_xor((int)lo, o, 64), h2 = (unsigned)__shfl_xor((int)hi, o, 64);
-        const u64 sum = (((u64)hi << 32) | lo) + (((u64)h2 << 32) | l2);
-        lo = (unsigned)sum; hi = (unsigned)(sum >> 32);
-    }
-    return ((u64)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(BV_CAST_THREADS) void wn_query_kernel(BvTree T, WnTable W, const float *__restrict__ points, BvLattice G, unsigned N, float beta,
                                                                    float *__restrict__ w_out, unsigned long long *__restrict__ counts, unsigned *__restrict__ fault)
 {
@@ -253,7 +242,7 @@ __global__ __launch_bounds__(BV_CAST_THREADS) void wn_query_kernel(BvTree T, WnT
     }
     if (counts) {
         const u64 ma = __ballot(answered), mr = __ballot(refused);
-        node_visits = wn_wave_sum(node_visits); dipole_terms = wn_wave_sum(dipole_terms); tri_terms = wn_wave_sum(tri_terms);
+        node_visits = bv_wave_sum(node_visits); dipole_terms = bv_wave_sum(dipole_terms); tri_terms = bv_wave_sum(tri_terms);
         if ((threadIdx.x & 63u) == 0) {
             if (ma) atomicAdd(counts + 0, (unsigned long long)__popcll(ma));
             if (mr) atomicAdd(counts + 1, (unsigned long long)__popcll(mr));

@@ -1531,3 +1531,129 @@ def remesh_watertight(verts, faces, resolution: int = 256, voxel: float = None, 
         stats.update(dims=dims, voxel=voxel, origin=origin, input={k: cin[k] for k in keep}, result={k: cout[k] for k in keep},
                      components=mesh_components(of, int(ov.shape[0]))[2] if int(ov.shape[0]) else 0)
     return ov, of
+
+
+# ---- which triangles cut through which: the triangle-pair query (csrc/tvr_mesh_crossings.hip; include/tvr.h tvr_mesh_crossings_*) ---------------------------
+CROSSINGS_COUNTS = ("pairs", "triangles_refused", "node_tests", "pair_tests")
+_CROSSINGS_FAULT = ("tvr_mesh_crossings raised its fault flag: the hierarchy does not belong to this mesh, or a face index of the hierarchy's mesh lies outside the "
+                    "vertices (include/tvr.h)")
+
+
+def _crossings_mesh(b: MeshBVH, query):
+    """the arguments both passes share (include/tvr.h tvr_mesh_crossings_*), and the number of query triangles; query: None (self) or (verts_q, faces_q) on the device"""
+    if query is None:
+        return (_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), 0, None, 0, None, 0), b.n_triangles
+    vq, fq = query
+    return (_ptr(b.verts), b.n_vertices, _ptr(b.faces), b.n_triangles, b.blob.data_ptr(), L.nbytes(b.blob), 1, _ptr(vq), int(vq.shape[0]), _ptr(fq), int(fq.shape[0])), \
+        int(fq.shape[0])
+
+
+def crossings_count(bvh: MeshBVH, query=None, stats: dict = None):
+    """First pass (tvr_mesh_crossings_count): (per_triangle [Nq] int32 — how many triangles each query triangle crosses —, n_pairs).  Reads the total from the device once."""
+    dev, lib = bvh.device, L.lib()
+    mesh, Nq = _crossings_mesh(bvh, query)
+    per = L.dev_empty((Nq,), torch.int32, dev, what="mesh crossings counts per triangle")
+    total = L.dev_empty((1,), torch.int64, dev, what="mesh crossings total")
+    counts = L.dev_empty((4,), torch.int64, dev, what="mesh crossings counts")
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh crossings fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_crossings_count(*mesh, _ptr(per), L.nbytes(per), total.data_ptr(), counts.data_ptr(), flag.data_ptr(), _stream_ptr(dev)), "tvr_mesh_crossings_count")
+    if int(flag.item()) != 0:
+        raise L.TvrError(_CROSSINGS_FAULT)
+    if stats is not None:
+        stats.update(zip(CROSSINGS_COUNTS, (int(x) for x in counts.cpu().tolist())))
+    return per, int(total.item())
+
+
+def crossings_emit(bvh: MeshBVH, per_triangle: torch.Tensor, n_pairs: int, query=None, points: bool = False):
+    """Second pass (tvr_mesh_crossings_emit) into buffers of exactly the counted size: (pairs [P,2] int32, n_pierce [P] int32, points [P,2,3] float32 or None), the rows
+    of one query triangle together and in walk order — not yet sorted.  Counts that are not the ones crossings_count found raise TvrError."""
+    dev, lib, P = bvh.device, L.lib(), int(n_pairs)
+    mesh, Nq = _crossings_mesh(bvh, query)
+    offsets = torch.zeros(Nq + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(per_triangle, 0, dtype=torch.int64)
+    pairs = L.dev_empty((P, 2), torch.int32, dev, what="mesh crossings pairs")
+    n_pierce = L.dev_empty((P,), torch.int32, dev, what="mesh crossings n_pierce")
+    pts = L.dev_empty((P, 2, 3), torch.float32, dev, what="mesh crossings points") if points else None
+    flag = L.dev_bytes(4, dev, zero=True, what="mesh crossings fault flag").view(torch.int32)
+    L.check(lib.tvr_mesh_crossings_emit(*mesh, offsets.data_ptr(), L.nbytes(offsets), P, _ptr(pairs), L.nbytes(pairs), _ptr(n_pierce), L.nbytes(n_pierce),
+                                        None if pts is None else _ptr(pts), 0 if pts is None else L.nbytes(pts), flag.data_ptr(), _stream_ptr(dev)),
+            "tvr_mesh_crossings_emit")
+    if int(flag.item()) != 0:
+        raise L.TvrError(_CROSSINGS_FAULT + "; or the two passes disagree")
+    return pairs, n_pierce, pts
+
+
+def _crossings(b: MeshBVH, query, points: bool, stats, what: str):
+    """Both passes and the caller's job after them: the sort of the rows by (first, second)."""
+    per, P = crossings_count(b, query, stats)
+    if P > 2 ** 31 - 1:
+        raise L.TvrError(f"{what}: {P} crossing pairs; at most 2^31 - 1 are written by one call")
+    pairs, n_pierce, pts = crossings_emit(b, per, P, query, points)
+    order = torch.sort((pairs[:, 0].to(torch.int64) << 32) | pairs[:, 1].to(torch.int64))[1]      # the keys are unique: every correct sort gives this order
+    out = (pairs[order].contiguous(), n_pierce[order].contiguous())
+    return out + (pts[order].contiguous(),) if points else out
+
+
+def self_intersections(bvh: MeshBVH, points: bool = False, stats: dict = None):
+    """Which triangles of a mesh cut through which -> (pairs [P,2] int32, n_pierce [P] int32[, points [P,2,3] float32]) on the device.
+
+    pairs holds every i < j whose triangles cross, ascending by (i, j).  Two triangles cross iff a side of one pierces the other (six segment-triangle tests per pair,
+    each the casts' own ray-triangle test over 0 < t <= 1); n_pierce says how many of the six do — 2 in general position — and points (with points=True) holds the first
+    two piercing points, the ends of the pair's intersection segment.  A side is never tested against a triangle that has a corner at the POSITION of one of the side's
+    ends, so neighbours do not report rounding noise, welded or not; pairs that share an edge and duplicate faces are therefore never reported.  NOT detected: coplanar
+    overlap (a segment in a triangle's plane never pierces).  A triangle with a non-finite corner crosses nothing and is counted.  The same bytes on every run.  No CPU
+    fallback.  `stats` (a dict) receives pairs / triangles_refused / node_tests / pair_tests."""
+    return _crossings(_bvh_arg(bvh, "self_intersections"), None, points, stats, "self_intersections")
+
+
+def mesh_intersections(bvh: MeshBVH, verts_q, faces_q, points: bool = False, stats: dict = None):
+    """Which triangles of a second mesh cut through which triangles of a hierarchy's mesh -> (pairs [P,2] int32, n_pierce [P] int32[, points [P,2,3] float32]): the
+    collision test between two meshes.
+
+    pairs holds every (q, a), q a triangle of (verts_q, faces_q) and a a triangle of bvh's mesh, ascending by (q, a).  The pair test, n_pierce, points, the sharing rule
+    (by position, so a query mesh that reuses the hierarchy's vertices behaves as one mesh would) and `stats` are self_intersections'.  A query triangle with a non-finite
+    corner or an index outside verts_q crosses nothing and is counted.  Permuting faces_q permutes the rows and nothing else.  No CPU fallback."""
+    b = _bvh_arg(bvh, "mesh_intersections")
+    vq, fq = _mesh_on_device(verts_q, faces_q, "mesh_intersections")
+    if fq.device != b.device:
+        raise L.TvrError(f"mesh_intersections: the query mesh is on {fq.device}, the hierarchy on {b.device}")
+    return _crossings(b, (vq, fq), points, stats, "mesh_intersections")
+
+
+def crossing_faces(pairs, n_faces: int, column: int = None) -> torch.Tensor:
+    """The triangles involved in crossings -> [n_faces] bool on pairs' device.  column = None: both columns (a self query); 0 / 1: that column alone (the query mesh's
+    triangles / the hierarchy's, in a two-mesh query)."""
+    mask = torch.zeros(int(n_faces), dtype=torch.bool, device=pairs.device)
+    idx = pairs.reshape(-1) if column is None else pairs[:, int(column)]
+    mask[idx.to(torch.int64)] = True
+    return mask
+
+
+def mesh_check(verts, faces, bvh: MeshBVH = None) -> dict:
+    """Is a mesh usable for printing, simulation, boolean operations?  -> a dict of plain ints and floats: vertices, triangles; build_pseudonormals' counters
+    degenerate_faces / open_edges / nonmanifold_edges / inconsistent_edges and closed (the topological half); components (mesh_components); and the geometric half from
+    self_intersections: crossing_pairs, crossing_faces (triangles involved), crossing_length (the summed length |points[1] - points[0]| of the pairs' intersection
+    segments, in the mesh's units, float64) and n_pierce_histogram {n_pierce: pairs}.  bvh: the mesh's hierarchy, when the caller has one.  No CPU fallback."""
+    b = build_bvh(verts, faces) if bvh is None else _bvh_arg(bvh, "mesh_check")
+    closed = {}
+    build_pseudonormals(b, stats=closed)
+    pairs, n_pierce, pts = self_intersections(b, points=True)
+    seg = (pts[:, 1].double() - pts[:, 0].double())
+    values, counts = torch.unique(n_pierce, return_counts=True)
+    report = {"vertices": b.n_vertices, "triangles": b.n_triangles}
+    report.update({k: int(closed[k]) for k in CLOSEDNESS_COUNTERS}, closed=bool(closed["closed"]))
+    report.update(components=int(mesh_components(b.faces, b.n_vertices)[2]) if b.n_vertices else 0, crossing_pairs=int(pairs.shape[0]),
+                  crossing_faces=int(crossing_faces(pairs, b.n_triangles).sum().item()), crossing_length=float(seg.pow(2).sum(1).sqrt().sum().item()),
+                  n_pierce_histogram={int(v): int(c) for v, c in zip(values.cpu().tolist(), counts.cpu().tolist())})
+    return report
+
+
+def write_obj_segments(path, points) -> None:
+    """Line segments as a Wavefront OBJ of `v` and `l` records only — what a viewer shows as curves: points [P,2,3] (self_intersections' piercing points), segment p
+    joins vertices 2p+1 and 2p+2.  Coordinates are written with 9 significant digits, which round-trip float32."""
+    p = _host(points, np.float32).reshape(-1, 2, 3)
+    with open(path, "w") as f:
+        for a in p.reshape(-1, 3):
+            f.write(f"v {a[0]:.9g} {a[1]:.9g} {a[2]:.9g}\n")
+        for i in range(len(p)):
+            f.write(f"l {2 * i + 1} {2 * i + 2}\n")

@@ -114,6 +114,12 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     # winding walk (>= 1, inf = exact); 0 = off
     p.add_argument("--mesh_watertight", type=int, default=0)
     p.add_argument("--mesh_watertight_beta", type=float, default=2.0)
+    # say whether a mesh is usable for printing, simulation or boolean operations (mesh.mesh_check): 1 = counts, closedness counters, components and the triangle pairs
+    # that cut through each other (mesh.self_intersections); with --export_mesh 1 the mesh just written is checked, without it --mesh_file (no checkpoint needed);
+    # writes <mesh minus extension>_check.json, lengths in world units and, when a --ckpt is loaded, in export voxels; --mesh_check_curves 1 also writes the pairs'
+    # intersection segments as <mesh minus extension>_crossings.obj (v and l records); 0 = off
+    p.add_argument("--mesh_check", type=int, default=0)
+    p.add_argument("--mesh_check_curves", type=int, default=0)
     # (not a reference option) normal maps beside the colour images of render_test / render_path: normal/{idx:03d}.png (TensorBase.render_normals, evaluation.normal_map_to_rgb8)
     p.add_argument("--render_normals", type=int, default=0)
     # (not a reference option) views of an exported mesh beside the rendered test views (mesh.render_mesh): with --render_only 1 --render_test 1, read --mesh_file
@@ -378,6 +384,38 @@ def mesh_watertight(args, path, device="cuda"):
     return out
 
 
+@torch.no_grad()
+def mesh_check_report(args, path, device="cuda"):
+    """--mesh_check 1: mesh.mesh_check of the mesh at `path`, written to <path minus extension>_check.json — the file name, the counts, the closedness counters, the
+    component count and the crossings (pairs, triangles involved, the summed length of the intersection segments, the histogram of n_pierce); crossing_length is in world
+    units; with a --ckpt also crossing_length_voxels, the unit being the smallest edge of mesh_export_voxel(tensorf, --mesh_grid), which the file records as
+    _distance.json does.  --mesh_check_curves 1 also writes <path minus extension>_crossings.obj.  Returns the path of the JSON."""
+    import json
+    from .mesh import build_bvh, mesh_check, self_intersections, write_obj_segments
+    v, f = _read_mesh_geometry(path)
+    tv, tf = (torch.from_numpy(np.ascontiguousarray(x)).to(device) for x in (v, f))
+    bvh = build_bvh(tv, tf)
+    report = {"mesh_file": path, **mesh_check(tv, tf, bvh=bvh), "crossing_length_unit": "world"}
+    base = os.path.splitext(path)[0]
+    if getattr(args, "mesh_check_curves", 0):
+        report["crossings_file"] = base + "_crossings.obj"
+        write_obj_segments(report["crossings_file"], self_intersections(bvh, points=True)[2])
+    if args.ckpt and os.path.exists(args.ckpt):
+        tensorf, _ = _build_from_ckpt(args, load_checkpoint(args.ckpt), device)
+        voxel = mesh_export_voxel(tensorf, getattr(args, "mesh_grid", None))
+        report["voxel"] = [float(x) for x in voxel]
+        report["voxel_unit"] = float(voxel.min())
+        report["voxel_from"] = "--mesh_grid" if getattr(args, "mesh_grid", None) else "the field's gridSize (pass the export's --mesh_grid if it was made on another grid)"
+        report["crossing_length_voxels"] = report["crossing_length"] / float(voxel.min())
+    out = base + "_check.json"
+    with open(out, "w") as fjson:
+        json.dump(report, fjson, indent=1)
+    print(f"check of {path}: {report['triangles']} triangles, {report['components']} component(s), closed: {report['closed']}, {report['crossing_pairs']} crossing pairs "
+          f"on {report['crossing_faces']} triangles, intersection length {report['crossing_length']:.6g} (world units)"
+          + (f" = {report['crossing_length_voxels']:.3f} export voxels" if "crossing_length_voxels" in report else ""))
+    return out
+
+
 FAULT_POLL_EVERY = 16       # iterations between two reads of the training-fault accumulator (field.check_training_faults)
 
 
@@ -557,17 +595,28 @@ def main(cmd: Optional[List[str]] = None):
         out = mesh_compare(args, args.mesh_file)
         if getattr(args, "mesh_watertight", 0):
             mesh_watertight(args, args.mesh_file)
+        if getattr(args, "mesh_check", 0):
+            mesh_check_report(args, args.mesh_file)
         return out
     if getattr(args, "mesh_watertight", 0) and not args.export_mesh:
         if not getattr(args, "mesh_file", None):
             raise SystemExit("--mesh_watertight R remeshes the mesh of --export_mesh 1, or the one --mesh_file names: neither was given; nothing was done")
-        return mesh_watertight(args, args.mesh_file)
+        out = mesh_watertight(args, args.mesh_file)
+        if getattr(args, "mesh_check", 0):
+            mesh_check_report(args, args.mesh_file)
+        return out
+    if getattr(args, "mesh_check", 0) and not args.export_mesh:
+        if not getattr(args, "mesh_file", None):
+            raise SystemExit("--mesh_check 1 checks the mesh of --export_mesh 1, or the one --mesh_file names: neither was given; nothing was done")
+        return mesh_check_report(args, args.mesh_file)
     if args.export_mesh:
         path = export_mesh(args)
         if getattr(args, "mesh_compare", None):
             mesh_compare(args, path)
         if getattr(args, "mesh_watertight", 0):
             mesh_watertight(args, path)
+        if getattr(args, "mesh_check", 0):
+            mesh_check_report(args, path)
         if not (args.render_only and (args.render_test or args.render_path)):
             return path
     if args.render_only and (args.render_test or args.render_path):
