@@ -45,11 +45,14 @@ __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const Scene
 // The march of a scene with a baked density volume (tvr_scene_set_density_volume): the same body, the density feature from vol_density (tvr_march_body.h) — 32 B per
 // sample through L1 instead of 768 B and 384 B of LDS, seven lerps instead of three 16-channel bilinear / linear products and two quad reductions.  No line image in LDS:
 // a group needs its header and 6 B per sample and wave; the launch shape and why: tvr_march_body.h (MARCH_VOL_*), DESIGN.md 4.1.
-template <bool DENSE>
+// PLAIN (only with !DENSE): the instantiation the frames of a plain scene run — no alpha volume, no explicit depths, no lam6, a volume below 4 GiB (launch_march_vol
+// checks); those paths are absent from it at compile time and vol_density32 addresses the volume with 32-bit offsets (tvr_march_body.h).
+template <bool DENSE, bool PLAIN>
 __global__ __launch_bounds__(64 * MARCH_VOL_WAVES, DENSE ? MARCH_VOL_OCC - 1 : MARCH_VOL_OCC) void march_vol_kernel(const SceneDev sc, const float *__restrict__ dvol, const float *__restrict__ rays,
                                                                          const int n_rays, const int S, const int s_cap, const MarchSampling sm, const float eps_T,
                                                                          MarchOut mo, const tvr_dense_out dn)
 {
+    static_assert(!(PLAIN && DENSE), "the plain form has no dense outputs");
     constexpr bool LDSL = false, CP = false, VOL = true;
     const CpDev cp = {};
 #include "tvr_march_body.inc"
@@ -277,11 +280,14 @@ static hipError_t launch_march_vol(const SceneDev &sc, const float *dvol, const 
     if (grid < 1) grid = 1;
     tvr_dense_out none = {};
     const tvr_dense_out &dn = dense ? *dense : none;
-    hipError_t rc = dense ? hipFuncSetAttribute((const void *)march_vol_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                          : hipFuncSetAttribute((const void *)march_vol_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const unsigned long long vol_bytes = 4ull * (unsigned long long)(sc.grid[0] + 1) * (unsigned long long)(sc.grid[1] + 1) * (unsigned long long)(sc.grid[2] + 1);
+    const bool plain = !dense && sc.avol == nullptr && sm.zv == nullptr && mo.lam6 == nullptr && vol_bytes < (1ull << 32);
+    const void *fn = dense ? (const void *)march_vol_kernel<true, false> : (plain ? (const void *)march_vol_kernel<false, true> : (const void *)march_vol_kernel<false, false>);
+    hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (rc != hipSuccess) return rc;
-    if (dense) hipLaunchKernelGGL((march_vol_kernel<true>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
-    else hipLaunchKernelGGL((march_vol_kernel<false>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
+    if (dense) hipLaunchKernelGGL((march_vol_kernel<true, false>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
+    else if (plain) hipLaunchKernelGGL((march_vol_kernel<false, true>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
+    else hipLaunchKernelGGL((march_vol_kernel<false, false>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
     return hipGetLastError();
 }
 

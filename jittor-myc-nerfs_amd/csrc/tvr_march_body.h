@@ -27,6 +27,9 @@
 // concurrently and share their lines in L1 — compiled for 64 registers (the launch bound asks for 8 waves per SIMD to get that cap, not to run them); why the frame
 // prefers it is not established.  LDS is the header and 6 B per sample and wave (49 KB at 512 samples, where the factored kernel holds 107 KB).  The
 // DENSE form (debugging surface, 70 registers) is compiled for one wave fewer rather than spill to scratch.
+// After the trim (profiles/march_trim.txt) the plain form holds 39 registers and the shape was measured again on the frame in pieces: 1 x 16 waves 12.76 - 12.77 ms,
+// 1 x 8 13.5, 2 x 8 13.3, 2 x 16 14.1.  The launch bound now matters for the SCALAR file: bound (1024, 7) gives the plain form 96 SGPRs and no spill, and the frame
+// 13.95 ms instead of 12.5 — the ten values that spill under (1024, 8) are all outside the chunk loop and stay spilled.
 #ifndef MARCH_VOL_WAVES
 #define MARCH_VOL_WAVES 16                // waves per group
 #endif
@@ -102,4 +105,126 @@ __device__ __forceinline__ float vol_density(const float *__restrict__ D, int gx
     const float c10 = __builtin_fmaf(wx, p10.b - p10.a, p10.a), c11 = __builtin_fmaf(wx, p11.b - p11.a, p11.a);
     const float c0 = __builtin_fmaf(wy, c01 - c00, c00), c1 = __builtin_fmaf(wy, c11 - c10, c10);
     return __builtin_fmaf(wz, c1 - c0, c0);
+}
+
+// The plain form of the volume march (march_vol_kernel<false, true>: no alpha volume, no explicit depths, no lam6, a volume below 4 GiB — launch_march_vol checks) is
+// compiled without those paths; kernels that do not name PLAIN themselves (march_kernel, cp_march_kernel) see this `false`.
+constexpr bool PLAIN = false;
+
+// What a march touches once per ray — the ray and jitter arrays in front of the chunk loop, the outputs behind it — costs the chunk loop scalar registers for nothing:
+// kernel arguments are loaded at the kernel's entry and stay live (march_vol_kernel<false> kept 100 of them in spilled lanes, 40 v_readlane_b32 inside the chunk loop).
+// The plain form reads these pointers from the kernel-argument segment where it uses them: MarchVolArgs restates march_vol_kernel's parameter list (arguments are
+// laid out like the members of a struct), and the empty asm keeps the loads from being hoisted back out of the ray loop.  Every other kernel takes its arguments.
+struct MarchVolArgs {
+    SceneDev sc;
+    const float *dvol, *rays;
+    int n_rays, S, s_cap;
+    MarchSampling sm;
+    float eps_T;
+    MarchOut mo;
+    tvr_dense_out dn;
+};
+template <bool ON_DEMAND, typename T>
+__device__ __forceinline__ T march_arg_now(const T &arg, unsigned offset)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (ON_DEMAND) {
+        const __attribute__((address_space(4))) unsigned char *ka = (const __attribute__((address_space(4))) unsigned char *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        return *(const __attribute__((address_space(4))) T *)(ka + offset);
+    }
+#endif
+    return arg;
+}
+
+// vol_density for a volume below 4 GiB: the same four loads and seven lerps, addressed as vm_term_lds addresses its planes — ONE opaque 32-bit byte offset per sample
+// against four wave-uniform row bases r00 = D, r01 = D + sy, r10 = D + sz, r11 = D + sz + sy (global_load_dwordx2 v, v_off, s[base]); no 64-bit VALU.  The row number
+// iz (gy + 1) + iy has both factors below 2^24 (grid <= 4096); its product with gx + 1 is a full 32-bit multiply, since a flat volume's row count may pass 2^24.
+__device__ __forceinline__ float vol_density32(const unsigned char *r00, const unsigned char *r01, const unsigned char *r10, const unsigned char *r11, unsigned gx1,
+                                               unsigned gy1, int ix, int iy, int iz, float wx, float wy, float wz)
+{
+    const unsigned row = __umul24((unsigned)iz, gy1) + (unsigned)iy;
+    unsigned o = (row * gx1 + (unsigned)ix) << 2;
+    asm volatile("" : "+v"(o));                                                           // opaque: hipcc otherwise widens the sums back into 64-bit arithmetic
+    const vol_pair p00 = *(const vol_pair *)(r00 + (size_t)o), p01 = *(const vol_pair *)(r01 + (size_t)o);
+    const vol_pair p10 = *(const vol_pair *)(r10 + (size_t)o), p11 = *(const vol_pair *)(r11 + (size_t)o);
+    const float c00 = __builtin_fmaf(wx, p00.b - p00.a, p00.a), c01 = __builtin_fmaf(wx, p01.b - p01.a, p01.a);
+    const float c10 = __builtin_fmaf(wx, p10.b - p10.a, p10.a), c11 = __builtin_fmaf(wx, p11.b - p11.a, p11.a);
+    const float c0 = __builtin_fmaf(wy, c01 - c00, c00), c1 = __builtin_fmaf(wy, c11 - c10, c10);
+    return __builtin_fmaf(wz, c1 - c0, c0);
+}
+
+// exp and softplus of the volume marches (all three forms, so that one scene has one evaluator).  The arguments are bounded where they are used — softplus takes the
+// branch below only for x <= 20, and -sigma * dist <= 0, where underflow to 0 is the right answer — so OCML's range clamps and its double-float log1pf (some 110
+// instructions) are not needed:
+//   march_expf   OCML's own expf without the clamps: p = x log2(e), the fma-compensated low part, v_exp_f32 of the reduced argument, v_ldexp_f32 — the same bits as
+//                expf for every finite x <= 88.7
+//   march_softplus   log1p(t), t = e^x in (0, e^20]: u = 1 + t, d = u - 1 (exact), log(u) (t / d) — the rounding of 1 + t cancels in the quotient; v_log_f32, and
+//                v_rcp_f32 with one residual step for t / d.  d == 0 (x < -16.6): log1p(t) = t to fp32.  x > 20 as softplus_f.
+#ifndef MARCH_VOL_LEAN
+#define MARCH_VOL_LEAN 1                  // 0: the volume marches call expf / softplus_f like every other kernel (the stage that changes no bit)
+#endif
+__device__ __forceinline__ float march_expf(float x)
+{
+    const float p = x * 0x1.715476p+0f;
+    const float r = __builtin_rintf(p);
+    float lo = __builtin_fmaf(x, 0x1.715476p+0f, -p);
+    lo = __builtin_fmaf(x, 0x1.4ae0bep-26f, lo);
+    return __builtin_ldexpf(__builtin_amdgcn_exp2f((p - r) + lo), (int)r);
+}
+__device__ __forceinline__ float march_softplus(float x)
+{
+    if (x > 20.0f) return x;
+    const float t = march_expf(x);
+    const float u = 1.0f + t, d = u - 1.0f;
+    const float rc = __builtin_amdgcn_rcpf(d);
+    float q = t * rc;
+    q = __builtin_fmaf(__builtin_fmaf(-d, q, t), rc, q);
+    const float lg = __builtin_amdgcn_logf(u) * 0x1.62e430p-1f;
+    return d == 0.0f ? t : lg * q;
+}
+
+// The transmittance scan of the volume marches: x[l] <- x[l] * x[l - off] for off = 1, 2, 4, 8, 16, 32 and the lanes l >= off (Hillis-Steele) — the recurrence, the
+// operands and their order of the __shfl_up form the factored marches keep, so every product has the same bits — with the data moved inside the register file instead
+// of through eight ds_bpermute_b32 round trips.  A lane below `off` multiplies by 1.0f (exact: fp32 denormals are kept) instead of being skipped.
+//   off 1 - 8   v_mov_b32_dpp wave_shr:1, off times: it carries across the 16-lane rows, which row_shr does not; lane 0 keeps `old` = 1.0f
+//   off 16      v_permlane16_swap(x, x) = {r0 r0 r2 r2 | r1 r1 r3 r3} (rows r0 .. r3 of x), v_permlane32_swap of the two = {r0 r0 r1 r1 | r2 r2 r3 r3}: rows 1, 2
+//               take the latter's first word, row 3 the former's (r2), row 0 keeps 1.0f (row-masked moves)   (profiles/r05_permlane_semantics.txt)
+//   off 32      v_permlane32_swap(x, x) = {lo lo | hi hi}: the upper half takes the first
+// excl = the scan shifted up one lane (lane 0: 1.0f); last = lane 63's value (v_readlane_b32).
+#define MARCH_DPP_WAVE_SHR1 0x138
+#define MARCH_DPP_SAME 0xE4                 // quad_perm:[0,1,2,3]
+template <int CTRL, int ROWS>
+__device__ __forceinline__ float march_dpp_mov(float old, float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROWS, 0xF, false));
+}
+// v shifted up N lanes, 1.0f in the lanes below N: the first move puts 1.0f into lane 0, the others run in place, where lane 0 keeps what it holds
+template <int N>
+__device__ __forceinline__ float march_up(float v)
+{
+    float t = march_dpp_mov<MARCH_DPP_WAVE_SHR1, 0xF>(1.0f, v);
+#pragma unroll
+    for (int i = 1; i < N; ++i) t = march_dpp_mov<MARCH_DPP_WAVE_SHR1, 0xF>(t, t);
+    return t;
+}
+__device__ __forceinline__ void scan_mul_dpp(float &x, float &excl, float &last)
+{
+    x = x * march_up<1>(x);
+    x = x * march_up<2>(x);
+    x = x * march_up<4>(x);
+    x = x * march_up<8>(x);
+    {
+        const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        const auto s = __builtin_amdgcn_permlane32_swap(q[0], q[1], false, false);        // {r0 r0 r1 r1 | r2 r2 r3 r3}
+        float t = march_dpp_mov<MARCH_DPP_SAME, 0x6>(1.0f, __uint_as_float(s[0]));
+        t = march_dpp_mov<MARCH_DPP_SAME, 0x8>(t, __uint_as_float(q[0]));
+        x = x * t;
+    }
+    {
+        const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        x = x * march_dpp_mov<MARCH_DPP_SAME, 0xC>(1.0f, __uint_as_float(h[0]));
+    }
+    excl = march_up<1>(x);
+    last = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
 }

@@ -37,9 +37,15 @@
     if (mo.stats && threadIdx.x == 0) mo.stats[32 + 8 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
     const int sub = lane & 3;
+    // PLAIN: the four corner rows of the baked volume as wave-uniform bases (tvr_march_body.h: vol_density32); formed once per launch
+    const unsigned char *vrow[4] = {nullptr, nullptr, nullptr, nullptr};
+    if constexpr (PLAIN) {
+        const size_t vsy = (size_t)(sc.grid[0] + 1) * 4, vsz = vsy * (size_t)(sc.grid[1] + 1);
+        vrow[0] = (const unsigned char *)dvol; vrow[1] = vrow[0] + vsy; vrow[2] = vrow[0] + vsz; vrow[3] = vrow[2] + vsy;
+    }
     // clock probe (stats only): shader-clock and 100 MHz reference ticks over this workgroup's lifetime
     unsigned long long clk0 = 0ull, ref0 = 0ull;
-    if (mo.stats && threadIdx.x == 0) { clk0 = __builtin_amdgcn_s_memtime(); ref0 = __builtin_amdgcn_s_memrealtime(); }
+    if (march_arg_now<PLAIN>(mo.stats, offsetof(MarchVolArgs, mo.stats)) && threadIdx.x == 0) { clk0 = __builtin_amdgcn_s_memtime(); ref0 = __builtin_amdgcn_s_memrealtime(); }
 
     // Tiles are taken in order from ONE global counter, so the groups sweep the image together and the queue is in ~raster order (measured: march 7.9 vs 8.8 ms and
     // shade 15.25 vs 15.65 ms against per-XCD contiguous bands), and a launch with few tiles per group has no tail.
@@ -74,7 +80,7 @@
                     // (launches of fewer than 8 tiles per group keep whole tiles: there the 16 concurrent neighbours' shared texels matter more than the tail)
                     if ((long long)n_rays >= 8LL * MARCH_TILE * (long long)gridDim.x && (long long)last_start + 2LL * MARCH_TILE * (long long)gridDim.x >= (long long)n_rays)
                         len = MARCH_TAIL;
-                    t = atomicAdd(mo.counter + MARCH_CTR_WORD, len);
+                    t = atomicAdd(march_arg_now<PLAIN>(mo.counter, offsetof(MarchVolArgs, mo.counter)) + MARCH_CTR_WORD, len);
                     const unsigned long long genw = (unsigned long long)(k + 1u) | (len == MARCH_TAIL ? 0x80000000ull : 0ull);
 #ifdef TVR_FAULT_INJECT_MARCH                          // test build only (tests/test_gpu_faults.py): the publisher of local tile 3 of group 0 skips a generation
                     if (blockIdx.x == 0 && k == 3u) __hip_atomic_store(&slots[slot], ((unsigned long long)(k + 1u + MARCH_SLOTS) << 32) | t, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -96,7 +102,7 @@
                     __builtin_amdgcn_s_sleep(1);
                 }
                 if (fault) {
-                    if (lane == 0) atomicOr(mo.counter + 2, fault);
+                    if (lane == 0) atomicOr(march_arg_now<PLAIN>(mo.counter, offsetof(MarchVolArgs, mo.counter)) + 2, fault);
                     break;
                 }
                 ray_start = (int)(unsigned)v;
@@ -108,16 +114,19 @@
         last_start = ray_start;
         const int ray = ray_start + (int)(ci % MARCH_TILE);
         if (ray >= n_rays) continue;
+        // (PLAIN reads what it needs once per ray from the kernel-argument segment, here and behind the chunk loop: tvr_march_body.h, march_arg_now)
+        const float *__restrict__ const rays_r = march_arg_now<PLAIN>(rays, offsetof(MarchVolArgs, rays));
+        const float *const jit_r = march_arg_now<PLAIN>(sm.jitter, offsetof(MarchVolArgs, sm.jitter));
         float o[3], d[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            o[k] = rays[(size_t)ray * 6 + k];
-            d[k] = rays[(size_t)ray * 6 + 3 + k];
+            o[k] = rays_r[(size_t)ray * 6 + k];
+            d[k] = rays_r[(size_t)ray * 6 + 3 + k];
         }
         const float tmin = ray_tmin(sc, o, d);
-        const bool has_jit = sm.jitter != nullptr;
-        const float u = has_jit ? sm.jitter[ray] : 0.0f;
-        const float *__restrict__ zrow = sm.zv ? sm.zv + (size_t)ray * S : nullptr;     // explicit depths (wave-uniform choice)
+        const bool has_jit = jit_r != nullptr;
+        const float u = has_jit ? jit_r[ray] : 0.0f;
+        const float *__restrict__ zrow = (!PLAIN && sm.zv) ? sm.zv + (size_t)ray * S : nullptr;     // explicit depths (wave-uniform choice)
         float lam6 = 1.0f;
         int n6 = 0;                                        // samples whose (1 - alpha + 1e-6) factor lam6 already holds
 
@@ -144,7 +153,7 @@
                 bbox = bbox & !((sc.lo[k] > p[k]) | (p[k] > sc.hi[k]));   // :358
             }
             bool valid = bbox;
-            if (sc.avol != nullptr) {
+            if (!PLAIN && sc.avol != nullptr) {
                 if (bbox) valid = sc.abits ? alpha_positive(sc, p) : (alpha_lookup(sc, p) > 0.0f);  // :491-496
             }
             int i0[3];
@@ -157,6 +166,7 @@
                 i0[k] = (int)fl;
                 w[k] = f[k] - fl;
             }
+            if constexpr (PLAIN) asm volatile("" : "+v"(i0[0]), "+v"(i0[1]), "+v"(i0[2]), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]));   // one computation per sample: not rematerialised in the valid branch
             const unsigned long long mb = __ballot(bbox), mv = __ballot(valid);
             if (DENSE) {
                 const size_t q = (size_t)ray * S + j;
@@ -190,6 +200,9 @@
             float sf = 0.0f;
             if constexpr (VOL) {
                 // baked volume (tvr_march_body.h: vol_density): lane per sample, the trilinear interpolation of the cell's eight corner values
+                if constexpr (PLAIN) {
+                    if (valid) sf = vol_density32(vrow[0], vrow[1], vrow[2], vrow[3], (unsigned)(sc.grid[0] + 1), (unsigned)(sc.grid[1] + 1), i0[0], i0[1], i0[2], w[0], w[1], w[2]);
+                } else
                 if (valid) sf = vol_density(dvol, sc.grid[0] + 1, sc.grid[1] + 1, i0[0], i0[1], i0[2], w[0], w[1], w[2]);
             } else {
                 // factored form: 4 sub-steps, quad-per-sample gather
@@ -222,26 +235,34 @@
             }
 
             float sigma = 0.0f;
+            constexpr bool LEAN = VOL && MARCH_VOL_LEAN;          // the volume marches' own exp / softplus (tvr_march_body.h)
+            if constexpr (LEAN) {
+                if (valid) sigma = (sc.act == 0) ? march_softplus(sf + sc.shift) : fmaxf(sf, 0.0f);
+            } else
             if (valid) sigma = (sc.act == 0) ? softplus_f(sf + sc.shift) : fmaxf(sf, 0.0f);   // :444-448
             float dist = (j < S - 1) ? (z1 - z) : 0.0f;           // :488
             dist = dist * sc.scale;                               // :511
-            const float alpha = 1.0f - expf(-sigma * dist);       // :19
+            const float alpha = 1.0f - (LEAN ? march_expf(-sigma * dist) : expf(-sigma * dist));       // :19
             const float fT = (1.0f - alpha) + 1e-10f;             // :21
-            if (mo.lam6) {                                        // nerfplusplus.py:277: cumprod(1 - alpha + TINY_NUMBER), TINY_NUMBER = 1e-6
+            if (!PLAIN && mo.lam6) {                              // nerfplusplus.py:277: cumprod(1 - alpha + TINY_NUMBER), TINY_NUMBER = 1e-6
                 float f6 = inr ? (1.0f - alpha) + 1e-6f : 1.0f;
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) f6 = f6 * __shfl_xor(f6, off);
                 lam6 = lam6 * f6;
                 n6 += min(64, S - c * 64);
             }
-            float incl = fT;
+            float incl = fT, excl, last;
+            if constexpr (VOL) {
+                scan_mul_dpp(incl, excl, last);                    // the same products in the same order, moved by DPP / permlane swaps instead of through LDS
+            } else {
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const float t = __shfl_up(incl, off);
-                if (lane >= off) incl = incl * t;
+                for (int off = 1; off < 64; off <<= 1) {
+                    const float t = __shfl_up(incl, off);
+                    if (lane >= off) incl = incl * t;
+                }
+                excl = __shfl_up(incl, 1);
+                if (lane == 0) excl = 1.0f;
             }
-            float excl = __shfl_up(incl, 1);
-            if (lane == 0) excl = 1.0f;
             const float Tj = T * excl;
             const float wgt = alpha * Tj;                          // :23
             acc_l += wgt;
@@ -253,7 +274,8 @@
                 if (app) { bufw[pos] = wgt; bufj[pos] = (unsigned short)j; }
                 napp += __popcll(ma);
             }
-            T = T * __shfl(incl, 63);
+            if constexpr (VOL) T = T * last;
+            else T = T * __shfl(incl, 63);
             if (DENSE && inr) {
                 const size_t q = (size_t)ray * S + j;
                 if (dn.sigma_feature) dn.sigma_feature[q] = valid ? sf : 0.f;
@@ -288,16 +310,17 @@
 
         const float acc = wave_sum(acc_l);
         const float dep = wave_sum(dep_l);
+        const MarchOut mt = march_arg_now<PLAIN>(mo, offsetof(MarchVolArgs, mo));
         unsigned base = 0;
-        if (lane == 0 && napp > 0) base = atomicAdd(mo.counter, (unsigned)napp);
+        if (lane == 0 && napp > 0) base = atomicAdd(mt.counter, (unsigned)napp);
         base = __shfl(base, 0);
         if (lane == 0) {
-            mo.ray_off[ray] = base;
-            mo.ray_cnt[ray] = (unsigned)napp;
-            mo.acc[ray] = acc;
-            mo.depth[ray] = dep + (1.0f - acc) * d[2];            // :531 (rays[..., -1] is d_z)
+            mt.ray_off[ray] = base;
+            mt.ray_cnt[ray] = (unsigned)napp;
+            mt.acc[ray] = acc;
+            mt.depth[ray] = dep + (1.0f - acc) * d[2];            // :531 (rays[..., -1] is d_z)
             // samples of skipped chunks / behind an early exit have alpha = 0: each factor is fp32(1 + 1e-6) = 1 + 8 ulp, log = 9.5367386e-7
-            if (mo.lam6) mo.lam6[ray] = lam6 * expf((float)(S - n6) * 9.5367386e-7f);
+            if (!PLAIN && mt.lam6) mt.lam6[ray] = lam6 * expf((float)(S - n6) * 9.5367386e-7f);
             if (DENSE) {
                 if (dn.bg_weight) dn.bg_weight[ray] = T;
                 if (dn.acc) dn.acc[ray] = acc;
@@ -315,9 +338,9 @@
             qv.y = ((o[1] + d[1] * z) - sc.lo[1]) * sc.inv[1] - 1.0f;
             qv.z = ((o[2] + d[2] * z) - sc.lo[2]) * sc.inv[2] - 1.0f;
             qv.w = bufw[i];
-            mo.q_pos[base + i] = qv;
-            mo.q_ray[base + i] = (unsigned)ray;
-            if (mo.q_j) mo.q_j[base + i] = ej;
+            mt.q_pos[base + i] = qv;
+            mt.q_ray[base + i] = (unsigned)ray;
+            if (mt.q_j) mt.q_j[base + i] = ej;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
@@ -330,7 +353,8 @@
         atomicAdd((unsigned long long *)&mo.stats[32 + 8 * blockIdx.x + 5], tl_rays);
     }
 #endif
-    if (mo.stats) {                                      // (wave-uniform: every wave of the group reaches this barrier exactly once)
+    unsigned long long *const stats_r = march_arg_now<PLAIN>(mo.stats, offsetof(MarchVolArgs, mo.stats));
+    if (stats_r) {                                       // (wave-uniform: every wave of the group reaches this barrier exactly once)
         if (lane == 0) {
             atomicAdd(&gstat[0], st_eval);
             atomicAdd(&gstat[1], st_bbox);
@@ -338,10 +362,10 @@
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            atomicAdd((unsigned long long *)&mo.stats[TVR_STAT_SAMPLES_EVAL], gstat[0]);
-            atomicAdd((unsigned long long *)&mo.stats[TVR_STAT_SAMPLES_BBOX], gstat[1]);
-            atomicAdd((unsigned long long *)&mo.stats[TVR_STAT_RAYS_TERMINATED], gstat[2]);
-            atomicAdd((unsigned long long *)&mo.stats[TVR_STAT_MARCH_CLK], __builtin_amdgcn_s_memtime() - clk0);
-            atomicAdd((unsigned long long *)&mo.stats[TVR_STAT_MARCH_REF], __builtin_amdgcn_s_memrealtime() - ref0);
+            atomicAdd((unsigned long long *)&stats_r[TVR_STAT_SAMPLES_EVAL], gstat[0]);
+            atomicAdd((unsigned long long *)&stats_r[TVR_STAT_SAMPLES_BBOX], gstat[1]);
+            atomicAdd((unsigned long long *)&stats_r[TVR_STAT_RAYS_TERMINATED], gstat[2]);
+            atomicAdd((unsigned long long *)&stats_r[TVR_STAT_MARCH_CLK], __builtin_amdgcn_s_memtime() - clk0);
+            atomicAdd((unsigned long long *)&stats_r[TVR_STAT_MARCH_REF], __builtin_amdgcn_s_memrealtime() - ref0);
         }
     }
