@@ -126,10 +126,35 @@ int tvr_scene_update(tvr_scene *scene, const tvr_scene_params *params, void *str
  * stats, jitter, eps_T, prof and pieces as ever; no host read), tvr_density_feature, tvr_density_gradient, tvr_app_feature, tvr_mlp_render, tvr_filter_rays.
  * REFUSE it with TVR_ERR_UNSUPPORTED before any launch (the message says "CP"): tvr_render_z and every *_ref call, tvr_march_forward(_z) / _backward(_z), tvr_app_h_forward /
  * _backward, tvr_grad_scratch_bytes and tvr_train_work_bytes (they return 0), tvr_mlp_train_forward, tvr_train_forward / _backward, tvr_train_work_describe,
- * tvr_scene_set_arith with a mode other than TVR_ARITH_F32, tvr_scene_validate_arith: CP scenes are inference-only and compute in the default arithmetic.
+ * tvr_scene_set_arith with a mode other than TVR_ARITH_F32, tvr_scene_validate_arith: through THESE entry points CP scenes are inference-only, and they compute in the
+ * default arithmetic.  CP scenes train through the tvr_cp_* calls below (CP TRAINING), which are entry points of their own.
  * Arithmetic: the lines, their products and the basis product are plain fp32 (FMAs); the network behind them is tvr_mlp_render's (fp16 hi / lo split, range rule below). */
 size_t tvr_cp_scene_packed_bytes(const tvr_scene_desc *desc);
 int tvr_cp_scene_create(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out);
+/* CP TRAINING (csrc/tvr_cp_train.hip): the gradients of the CP march and of the CP features, through entry points of their OWN — the refusals listed above stand as
+ * they are, and these calls refuse a scene that is not a CP scene with TVR_ERR_UNSUPPORTED.  ADDITIVE exports: TVR_VERSION is unchanged.
+ *   tvr_cp_grad_scratch_bytes   the packed gradient images: three density lines [L_i + 1][rd], three appearance lines [L_i + 1][ra], basis_mat [27][ra] (rd / ra: the
+ *                               components rounded up to 16 / 4), each block 256-B aligned.  0 for a NULL or non-CP scene.
+ *   tvr_cp_march_forward        tvr_march_forward's contract on a CP scene: the plain tvr_scratch_describe layout, the same argument checks, header words and fault flag,
+ *                               the ray-ordered queue for n_rays <= 65536.  Queue positions, weights, acc and depth are the bits tvr_render computes on the same rays.
+ *   tvr_cp_march_backward       tvr_march_backward's contract: grad_w [queue length] in queue order, grad_acc [n_rays]; writes out->density_line[0..2] ([1, R_sigma, L_i, 1]).
+ *                               The kernel recomputes the forward march bit for bit (same rays, jitter and eps_T as the forward call; fwd_scratch intact).
+ *   tvr_cp_app_backward         entries xyz_norm [m,3] and grad_features [m,27] (the gradient of tvr_app_feature's output, which is the forward of this call and accepts
+ *                               a CP scene); writes out->app_line[0..2] ([1, R_app, L_i, 1]) and out->basis_mat ([27, R_app]).  m == 0: TVR_OK, zeroed gradients.
+ * Each backward call zeroes the images it owns, accumulates, and OVERWRITES the tensors it names in `out` (reference layouts: no pad texel, no pad channel — nothing
+ * of the padding reaches them); the other members of `out` are not read.  NULL, short or misaligned buffers are refused before any launch.
+ * Sums across rays / entries are float atomics (one per lane and retired line tap, 64 consecutive floats per wave-instruction; the basis columns once per 256 entries):
+ * results are reproducible to ROUNDING, not bit for bit — two runs on the same inputs differ in the last bits of sums whose terms arrive in another order.
+ * Not offered for CP: explicit depths, lam6, the fused step (tvr_train_*), the MFMA network kernels (tvr_mlp_train_*), the reduced arithmetics. */
+typedef struct { float *density_line[3], *app_line[3], *basis_mat; } tvr_cp_grads;
+size_t tvr_cp_grad_scratch_bytes(const tvr_scene *scene);
+int tvr_cp_march_forward(tvr_scene *scene, const float *rays, int64_t n_rays, int32_t n_samples, const float *jitter, float eps_T, float *depth_out, void *scratch,
+                         size_t scratch_bytes, void *stream);
+int tvr_cp_march_backward(tvr_scene *scene, const float *rays, int64_t n_rays, int32_t n_samples, const float *jitter, float eps_T, const void *fwd_scratch,
+                          size_t fwd_scratch_bytes, const float *grad_w, const float *grad_acc, void *grad_scratch, size_t grad_scratch_bytes, const tvr_cp_grads *out,
+                          void *stream);
+int tvr_cp_app_backward(tvr_scene *scene, const float *xyz_norm, int64_t m, const float *grad_features, size_t grad_features_bytes, void *grad_scratch,
+                        size_t grad_scratch_bytes, const tvr_cp_grads *out, void *stream);
 /* CONCURRENCY: a scene's packed images are shared by every call that names the scene.  Any number of tvr_render(_z) calls may be in flight on different streams at once as
  * long as each has its own scratch and output buffers (they only READ the scene; render.py::FrameStream keeps two frames in flight this way).  Whatever WRITES the scene's
  * device state — tvr_scene_update, tvr_scene_set_alpha, tvr_scene_validate_arith, the first TVR_ARITH_F16 render after an update (it converts the fp16 copies), the first

@@ -39,6 +39,10 @@ class VmGrads(C.Structure):
     _fields_ = [("density_plane", C.c_void_p * 3), ("density_line", C.c_void_p * 3), ("app_plane", C.c_void_p * 3), ("app_line", C.c_void_p * 3)]
 
 
+class CpGrads(C.Structure):              # tvr_cp_grads
+    _fields_ = [("density_line", C.c_void_p * 3), ("app_line", C.c_void_p * 3), ("basis_mat", C.c_void_p)]
+
+
 class TrainWeights(C.Structure):         # tvr_train_weights
     _fields_ = [("W1", C.c_void_p), ("W2", C.c_void_p), ("W3", C.c_void_p), ("basis", C.c_void_p), ("heads_W", C.c_void_p * 4)]
 
@@ -116,6 +120,11 @@ SYMBOLS = {
     "tvr_scene_update": (C.c_int, [C.c_void_p, C.POINTER(SceneParams), C.c_void_p]),
     "tvr_cp_scene_packed_bytes": (C.c_size_t, [C.POINTER(SceneDesc)]),
     "tvr_cp_scene_create": (C.c_int, [C.POINTER(SceneDesc), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "tvr_cp_grad_scratch_bytes": (C.c_size_t, [C.c_void_p]),
+    "tvr_cp_march_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tvr_cp_march_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CpGrads), C.c_void_p]),
+    "tvr_cp_app_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(CpGrads), C.c_void_p]),
     "tvr_alpha_bits_bytes": (C.c_size_t, [C.POINTER(C.c_int32 * 3)]),
     "tvr_scene_set_alpha": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_float * 6),
                                       C.POINTER(C.c_float * 3), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -2,6 +2,8 @@
 
   * _MarchFn      tvr_march_forward(_z) / tvr_march_backward(_z)   sample_ray .. raw2alpha (tensorBase.py:487-513) w.r.t. the density factors
   * _AppHFn       tvr_app_h_forward / tvr_app_h_backward           the plane*line products of compute_appfeature (tensoRF.py:235-241)
+  * _CpMarchFn    tvr_cp_march_forward / tvr_cp_march_backward     _MarchFn for a CP field (cp.TensorCP with cp_training on) w.r.t. the three density lines
+  * _CpAppFn      tvr_app_feature / tvr_cp_app_backward            TensorCP.compute_appfeature (tensoRF.py:362-376) w.r.t. the three appearance lines and basis_mat
   * _PEConcatFn   tvr_pe_concat (+ backward)                        the MLP input of MLPRender_Fea(_Ref).execute (tensorBase.py:76-82)
   * _LinearFn     library GEMMs forward / dX, tvr_gemm_tn for dW    the Linears of REFTensoRF / NerfPlusPlus (and of shapes the fused kernels are not built for)
   * _MlpTrainFn   tvr_mlp_train_forward / tvr_mlp_train_backward    basis_mat + MLPRender_Fea of TensorVMSplit (tensoRF.py:244, tensorBase.py:76-86): the
@@ -405,6 +407,88 @@ class _MarchFn(torch.autograd.Function):
                                              gs.data_ptr(), gs.numel(), C.byref(out), _stream_ptr(model.device)), "tvr_march_backward_z")
         model._sig = None       # an optimizer step follows; whatever renders next (training or evaluation) re-packs the scene first
         return (None, None, None, None, None, None, *grads)
+
+
+class _CpMarchFn(torch.autograd.Function):
+    """_MarchFn for a CP scene (cp.TensorCP with cp_training on): tvr_cp_march_forward / tvr_cp_march_backward.  Differentiable outputs: the weights of the appearance
+    samples (queue order) and acc_map, w.r.t. the three density lines.  No explicit depths and no lam6: those are NerfPlusPlus's."""
+
+    @staticmethod
+    def forward(ctx, model, rays, jitter, S, eps_T, *density_lines):
+        lib = L.lib()
+        sc = model._ensure_scene(force=True)          # a training step: the optimizer has just written the parameters
+        n = rays.shape[0]
+        lay = L.ScratchLayout()
+        L.check(lib.tvr_scratch_describe(n, S, C.byref(lay)), "tvr_scratch_describe")
+        scratch = L.dev_bytes(lay.total, model.device, what="tvr_cp_march_forward scratch")   # owned by this call: backward needs it intact
+        depth = torch.empty(n, dtype=torch.float32, device=model.device)
+        L.check(lib.tvr_cp_march_forward(sc, rays.data_ptr(), n, S, None if jitter is None else jitter.data_ptr(), float(eps_T), depth.data_ptr(),
+                                         scratch.data_ptr(), scratch.numel(), _stream_ptr(model.device)), "tvr_cp_march_forward")
+        hdr = scratch[lay.counter:lay.counter + 16].view(torch.int32).tolist()           # host sync: the queue length sizes what follows
+        if hdr[2] != 0:
+            raise L.TvrError(f"tvr_cp_march_forward: the march kernel raised its fault flag ({hdr[2]}): a wave gave up waiting for its tile number "
+                             f"(include/tvr.h, tvr_scratch_layout); the queue of this call is incomplete")
+        M = int(hdr[0])
+        q_pos = scratch[lay.q_pos:lay.q_pos + M * 16].view(torch.float32).view(M, 4)
+        w = q_pos[:, 3].clone()
+        xyz = q_pos[:, :3].contiguous()
+        ray_id = scratch[lay.q_ray:lay.q_ray + M * 4].view(torch.int32).long()
+        acc = scratch[lay.acc:lay.acc + n * 4].view(torch.float32).clone()
+        ctx.model, ctx.rays, ctx.jitter, ctx.S, ctx.eps_T, ctx.scratch, ctx.M = model, rays, jitter, S, eps_T, scratch, M
+        ctx.shapes = [p.shape for p in density_lines]
+        ctx.mark_non_differentiable(xyz, ray_id, depth)
+        return w, acc, xyz, ray_id, depth
+
+    @staticmethod
+    def backward(ctx, gw, gacc, _gx, _gr, _gd):
+        model, lib = ctx.model, L.lib()
+        sc = model._ensure_scene(settle=False)
+        grads = [torch.empty(sh, dtype=torch.float32, device=model.device) for sh in ctx.shapes]
+        out = L.CpGrads()
+        for i in range(3):
+            out.density_line[i] = grads[i].data_ptr()
+        gs = model._get_cp_grad_scratch()
+        n = ctx.rays.shape[0]
+        # an empty queue (M == 0) hands autograd a [0] gradient whose data_ptr() is NULL: density then learns through acc_map alone (_MarchFn)
+        gw = torch.zeros(max(ctx.M, 1), device=model.device) if (gw is None or ctx.M == 0) else gw.contiguous().float()
+        gacc = torch.zeros(n, device=model.device) if gacc is None else gacc.contiguous().float()
+        L.check(lib.tvr_cp_march_backward(sc, ctx.rays.data_ptr(), n, ctx.S, None if ctx.jitter is None else ctx.jitter.data_ptr(), float(ctx.eps_T),
+                                          ctx.scratch.data_ptr(), ctx.scratch.numel(), gw.data_ptr(), gacc.data_ptr(), gs.data_ptr(), gs.numel(), C.byref(out),
+                                          _stream_ptr(model.device)), "tvr_cp_march_backward")
+        model._sig = None       # an optimizer step follows; whatever renders next (training or evaluation) re-packs the scene first
+        return (None, None, None, None, None, *grads)
+
+
+class _CpAppFn(torch.autograd.Function):
+    """features [M,27] = basis_mat(A0 * A1 * A2) at the queue positions of a CP scene (tvr_app_feature) and, backward, the gradients of the three appearance lines and
+    of basis_mat (tvr_cp_app_backward).  The positions carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, model, xyz, *app_params):
+        sc = model._ensure_scene(settle=False)
+        m = xyz.shape[0]
+        feats = torch.empty((m, 27), dtype=torch.float32, device=model.device)
+        if m > 0:
+            L.check(L.lib().tvr_app_feature(sc, xyz.data_ptr(), m, feats.data_ptr(), L.nbytes(feats), _stream_ptr(model.device)), "tvr_app_feature")
+        ctx.model, ctx.xyz = model, xyz
+        ctx.shapes = [p.shape for p in app_params]
+        return feats
+
+    @staticmethod
+    def backward(ctx, dF):
+        model = ctx.model
+        sc = model._ensure_scene(settle=False)
+        grads = [torch.empty(sh, dtype=torch.float32, device=model.device) for sh in ctx.shapes]
+        out = L.CpGrads()
+        for i in range(3):
+            out.app_line[i] = grads[i].data_ptr()
+        out.basis_mat = grads[3].data_ptr()
+        gs = model._get_cp_grad_scratch()
+        m = ctx.xyz.shape[0]
+        dF = dF.contiguous().float()
+        L.check(L.lib().tvr_cp_app_backward(sc, ctx.xyz.data_ptr() if m else None, m, dF.data_ptr() if m else None, L.nbytes(dF), gs.data_ptr(), gs.numel(),
+                                            C.byref(out), _stream_ptr(model.device)), "tvr_cp_app_backward")
+        return (None, None, *grads)
 
 
 class _AppHFn(torch.autograd.Function):

@@ -4,15 +4,23 @@
 
 behind TensorBase's march, MLPRender_Fea and compositing.  Constructed, loaded (our checkpoints and the reference's `.th` files), queried, masked, filtered, shrunk,
 upsampled and RENDERED through the HIP path (tvr_cp_scene_create, csrc/tvr_cp.hip); up to 96 density and 288 appearance components (configs/*.txt: n_lamb_sigma = [96],
-n_lamb_sh = [288]).  Training is not built: there are no backward kernels for the CP march and features yet."""
+n_lamb_sh = [288]).
+
+Training is OPT-IN: `model.cp_training = True` (reconstruct.py: --cp_training 1).  render_rays_autograd is then TensorBase's eager chain on the CP backward kernels
+(csrc/tvr_cp_train.hip): tvr_cp_march_forward / _backward for the density lines (autograd_ops._CpMarchFn), tvr_app_feature / tvr_cp_app_backward for the appearance lines
+and basis_mat (_CpAppFn), the network through MLPRender_Fea.forward_autograd (_LinearFn), compositing as an index_add_.  The line and basis gradients are summed with
+float atomics: two runs agree to rounding, not bit for bit.  Not built for CP: the fused two-call step and its hipGraph capture, the MFMA network kernels, the reduced
+arithmetics, the data-parallel helper.  With the default, cp_training = False, a CP model refuses to train exactly as before."""
 from __future__ import annotations
 
 import torch
 
+from . import _lib as L
+from .autograd_ops import _CpAppFn, _CpMarchFn, _f32c
 from .field import AlphaGridMask, TensorBase
 
-_NO_TRAINING = ("CP training is not built: TensorCP renders and answers field queries through the HIP kernels, "
-                "but there are no backward kernels for the CP march and features yet")
+_NO_TRAINING = ("CP training is not built into the default path: TensorCP renders and answers field queries through the HIP kernels, and trains only after "
+                "the opt-in `model.cp_training = True` (reconstruct.py: --cp_training 1), which routes render_rays_autograd through the CP backward kernels")
 
 
 class TensorCP(TensorBase):
@@ -44,9 +52,31 @@ class TensorCP(TensorBase):
 
     # compute_densityfeature (:345-360) and compute_appfeature (:362-376) are TensorBase's entry points: tvr_density_feature / tvr_app_feature on the CP scene handle.
 
-    # ---- what a CP scene does not have -----------------------------------------------------------------------------------------------------------
+    # ---- training: opt-in -------------------------------------------------------------------------------------------------------------------------
+    cp_training = False           # True: render_rays_autograd runs the CP backward kernels; False: it refuses, as it always did
+
     def render_rays_autograd(self, rays_chunk, white_bg=True, N_samples=-1, jitter=None):
-        raise NotImplementedError(_NO_TRAINING)
+        """TensorBase.execute with gradients (train.py:225-261) for the CP field: TensorBase.render_rays_autograd's eager chain with the CP march and feature Functions."""
+        if not self.cp_training:
+            raise NotImplementedError(_NO_TRAINING)
+        rays = _f32c(rays_chunk, self.device)
+        S = int(N_samples) if N_samples > 0 else self.nSamples
+        eps_T = self.eps_T if self.eps_T is not None else float(self.rayMarch_weight_thres)
+        w, acc, xyz, ray_id, depth = _CpMarchFn.apply(self, rays, jitter, S, eps_T, *self.density_line)
+        features = _CpAppFn.apply(self, xyz, *self.app_line, self.basis_mat.weight)           # tensoRF.py:362-376
+        rgb = self.renderModule.forward_autograd(rays[ray_id, 3:6], features)                 # tensorBase.py:517
+        rgb_map = torch.zeros((rays.shape[0], 3), device=self.device).index_add_(0, ray_id, w[:, None] * rgb)   # :521
+        if white_bg:
+            rgb_map = rgb_map + (1.0 - acc[:, None])                                          # :524
+        return rgb_map.clamp(0, 1), depth                                                     # :527
+
+    def _get_cp_grad_scratch(self) -> torch.Tensor:
+        nbytes = L.lib().tvr_cp_grad_scratch_bytes(self._ensure_scene(settle=False))
+        if getattr(self, "_cp_grad_scratch", None) is None or self._cp_grad_scratch.numel() < nbytes:
+            self._cp_grad_scratch = L.dev_bytes(nbytes, self.device, what="tvr_cp_grad_scratch")
+        return self._cp_grad_scratch
+
+    # ---- what a CP scene does not have -----------------------------------------------------------------------------------------------------------
 
     def _fused_step_ok(self) -> bool:
         return False

@@ -116,7 +116,7 @@ static PackedLayout cp_packed_layout(const tvr_scene_desc &d)
 }
 
 struct tvr_scene {
-    bool cp;                   // a CP scene (tvr_cp_scene_create): dev.dline / dev.aline hold the CP lines, `cpd` the rest; default arithmetic only, inference only
+    bool cp;                   // a CP scene (tvr_cp_scene_create): dev.dline / dev.aline hold the CP lines, `cpd` the rest; default arithmetic only; trains through tvr_cp_* only
     CpDev cpd;
     tvr_scene_desc desc;
     PackedLayout lay;
@@ -1241,6 +1241,112 @@ static int app_h_backward_impl(tvr_scene *s, const float *xyz, int xyz_stride, i
     }
     return TVR_OK;
 }
+
+// ---- CP training (include/tvr.h, CP TRAINING; csrc/tvr_cp_train.hip): entry points of their own beside the refusals above ----
+static int cp_required(const tvr_scene *s, const char *fn)
+{
+    if (!s) return fail(TVR_ERR_INVALID, "%s: scene is NULL", fn);
+    if (!s->cp) return fail(TVR_ERR_UNSUPPORTED, "%s: the scene is not a CP scene (tvr_cp_scene_create); TensorVMSplit / REFTensoRF scenes train through tvr_march_forward / "
+                                                 "_backward, tvr_app_h_* and tvr_train_*", fn);
+    return TVR_OK;
+}
+
+// the gradient images mirror the packed CP layout: dline[i] / aline[i] blocks, then the basis block ([27][ra] here), which ends where the network images begin
+struct CpGradImages { float *dline[3], *aline[3], *basis; };
+static CpGradImages cp_carve_grads(const tvr_scene *s, char *g)
+{
+    CpGradImages G;
+    for (int i = 0; i < 3; ++i) {
+        G.dline[i] = (float *)(g + s->lay.dline[i]);
+        G.aline[i] = (float *)(g + s->lay.aline[i]);
+    }
+    G.basis = (float *)(g + s->lay.cp_basis);
+    return G;
+}
+
+extern "C" {
+
+size_t tvr_cp_grad_scratch_bytes(const tvr_scene *s)
+{
+    if (cp_required(s, __func__) != TVR_OK) return 0;
+    return s->lay.mlp_image;
+}
+
+int tvr_cp_march_forward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, float *depth_out, void *scratch,
+                         size_t scratch_bytes, void *stream_)
+{
+    int rc = cp_required(s, __func__);
+    if (rc != TVR_OK) return rc;
+    rc = scene_ready(s);
+    if (rc != TVR_OK) return rc;
+    if (!rays || !depth_out || n_rays <= 0) return fail(TVR_ERR_INVALID, "rays/depth_out NULL or n_rays <= 0");
+    if (S <= 0 || S > 4096) return fail(TVR_ERR_INVALID, "n_samples=%d out of [1,4096]", S);
+    if ((size_t)n_rays * (size_t)S >= (1ull << 32)) return fail(TVR_ERR_INVALID, "n_rays*n_samples must be < 2^32 per call");
+    if (!(eps_T >= 0.0f) || eps_T > s->desc.weight_thres) return fail(TVR_ERR_INVALID, "eps_T=%g must be in [0, weight_thres]", eps_T);
+    ScratchLayout L = scratch_layout(n_rays, S);
+    if (!scratch || scratch_bytes < L.total || (uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "scratch too small (%zu < %zu) or misaligned", scratch_bytes, L.total);
+    hipStream_t stream = (hipStream_t)stream_;
+    MarchOut mo = carve_scratch((char *)scratch, L, depth_out);
+    const MarchSampling sm = {jitter, nullptr};
+    HIP_TRY(launch_zero_header(mo.counter, stream));                   // [0] queue length, [1] the march's tile counter, [2] its fault flag
+    HIP_TRY(launch_cp_march(s->dev, s->cpd, rays, (int)n_rays, S, sm, eps_T, mo, nullptr, stream));
+    if (n_rays <= TVR_RAY_ORDER_MAX_RAYS)                              // a training queue in ray order, as march_forward_impl leaves it
+        HIP_TRY(launch_queue_ray_order(mo, (unsigned *)((char *)scratch + L.ray_new), mo.q_out, (unsigned *)((char *)scratch + L.q_j), (int)n_rays, stream));
+    return TVR_OK;
+}
+
+int tvr_cp_march_backward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, const void *fwd_scratch, size_t fwd_scratch_bytes,
+                          const float *grad_w, const float *grad_acc, void *grad_scratch, size_t grad_scratch_bytes, const tvr_cp_grads *out, void *stream_)
+{
+    int rc = cp_required(s, __func__);
+    if (rc != TVR_OK) return rc;
+    rc = scene_ready(s);
+    if (rc != TVR_OK) return rc;
+    if (!rays || !fwd_scratch || !grad_w || !grad_acc || !grad_scratch || !out || n_rays <= 0) return fail(TVR_ERR_INVALID, "NULL argument or n_rays <= 0");
+    for (int i = 0; i < 3; ++i)
+        if (!out->density_line[i]) return fail(TVR_ERR_INVALID, "density gradient pointer %d is NULL", i);
+    if (S <= 0 || S > 4096) return fail(TVR_ERR_INVALID, "n_samples=%d out of [1,4096]", S);
+    if ((size_t)n_rays * (size_t)S >= (1ull << 32)) return fail(TVR_ERR_INVALID, "n_rays*n_samples must be < 2^32 per call");
+    if (!(eps_T >= 0.0f) || eps_T > s->desc.weight_thres) return fail(TVR_ERR_INVALID, "eps_T=%g must be in [0, weight_thres]", eps_T);
+    ScratchLayout L = scratch_layout(n_rays, S);
+    if (fwd_scratch_bytes < L.total || (uintptr_t)fwd_scratch % 256) return fail(TVR_ERR_SCRATCH, "forward scratch %zu B < %zu B or misaligned", fwd_scratch_bytes, L.total);
+    if (grad_scratch_bytes < s->lay.mlp_image || (uintptr_t)grad_scratch % 256) return fail(TVR_ERR_SCRATCH, "gradient scratch too small or misaligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const tvr_scene_desc &d = s->desc;
+    CpGradImages G = cp_carve_grads(s, (char *)grad_scratch);
+    for (int i = 0; i < 3; ++i) HIP_TRY(launch_zero_f32(G.dline[i], (long long)(d.grid[kVecH[i]] + 1) * s->cpd.rd, stream));       // (rd is a multiple of 16, blocks 256-B aligned)
+    MarchOut mo = carve_scratch((char *)fwd_scratch, L, nullptr);
+    HIP_TRY(launch_cp_march_backward(s->dev, s->cpd, rays, (int)n_rays, S, jitter, eps_T, mo, grad_w, grad_acc, G.dline, stream));
+    for (int i = 0; i < 3; ++i) HIP_TRY(launch_unpack_grad(G.dline[i], out->density_line[i], d.density_n_comp[0], s->cpd.rd, d.grid[kVecH[i]], 1, stream));
+    return TVR_OK;
+}
+
+int tvr_cp_app_backward(tvr_scene *s, const float *xyz, int64_t m, const float *grad_features, size_t grad_features_bytes, void *grad_scratch, size_t grad_scratch_bytes,
+                        const tvr_cp_grads *out, void *stream_)
+{
+    int rc = cp_required(s, __func__);
+    if (rc != TVR_OK) return rc;
+    rc = scene_ready(s);
+    if (rc != TVR_OK) return rc;
+    if (!grad_scratch || !out || m < 0 || (m > 0 && (!xyz || !grad_features))) return fail(TVR_ERR_INVALID, "NULL argument or m < 0");
+    for (int i = 0; i < 3; ++i)
+        if (!out->app_line[i]) return fail(TVR_ERR_INVALID, "appearance gradient pointer %d is NULL", i);
+    if (!out->basis_mat) return fail(TVR_ERR_INVALID, "basis_mat gradient pointer is NULL");
+    if (m > 0) NEED("grad_features [m,27]", grad_features_bytes, m, TVR_APPDIM);
+    if ((uint64_t)m >= (1ull << 32)) return fail(TVR_ERR_INVALID, "m = %lld: at most 2^32 - 1 entries per call", (long long)m);
+    if (grad_scratch_bytes < s->lay.mlp_image || (uintptr_t)grad_scratch % 256) return fail(TVR_ERR_SCRATCH, "gradient scratch too small or misaligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const tvr_scene_desc &d = s->desc;
+    CpGradImages G = cp_carve_grads(s, (char *)grad_scratch);
+    for (int i = 0; i < 3; ++i) HIP_TRY(launch_zero_f32(G.aline[i], (long long)(d.grid[kVecH[i]] + 1) * s->cpd.ra, stream));       // (ra is a multiple of 4)
+    HIP_TRY(launch_zero_f32(G.basis, (long long)TVR_APPDIM * s->cpd.ra, stream));
+    if (m > 0) HIP_TRY(launch_cp_app_backward(s->dev, s->cpd, xyz, m, grad_features, G.aline, G.basis, stream));
+    for (int i = 0; i < 3; ++i) HIP_TRY(launch_unpack_grad(G.aline[i], out->app_line[i], d.app_n_comp[0], s->cpd.ra, d.grid[kVecH[i]], 1, stream));
+    HIP_TRY(launch_copy_cols(out->basis_mat, d.app_n_comp[0], 0, G.basis, s->cpd.ra, d.app_n_comp[0], TVR_APPDIM, stream));
+    return TVR_OK;
+}
+
+}  // extern "C"
 
 // ---- the training step without a host read (include/tvr.h: tvr_train_forward / tvr_train_backward) ----
 struct WorkLayout {

@@ -174,6 +174,12 @@ hipError_t launch_cp_density_gradient(const SceneDev &sc, const CpDev &cp, const
 hipError_t launch_cp_app_feature(const SceneDev &sc, const CpDev &cp, const float *xyz, int xyz_stride, long long m, const unsigned *m_dev, const unsigned *q_ray,
                                  const float *rays, float *feats, float *dirs, hipStream_t stream);
 hipError_t launch_cp_rgbw(const MarchOut &mo, const float *rgb, long long cap, hipStream_t stream);
+// tvr_cp_train.hip: the CP field's backward kernels.  gline[i]: the packed gradient image of line i ([L_i + 1][rd] / [L_i + 1][ra] fp32, zeroed by the caller); gbasis:
+// [27][ra] fp32, zeroed by the caller; xyz [m,3], dF [m,27].  Sums are float atomics: reproducible to rounding.
+hipError_t launch_cp_march_backward(const SceneDev &sc, const CpDev &cp, const float *rays, int n_rays, int S, const float *jitter, float eps_T, const MarchOut &mo,
+                                    const float *grad_w, const float *grad_acc, float *const gline[3], hipStream_t stream);
+hipError_t launch_cp_app_backward(const SceneDev &sc, const CpDev &cp, const float *xyz, long long m, const float *dF, float *const gline[3], float *gbasis,
+                                  hipStream_t stream);
 hipError_t launch_cp_pack_basis(const float *basis, int r_app, int ra, float4 *out, hipStream_t stream);
 int march_cu_count();
 

@@ -34,7 +34,7 @@ from .render import N_to_reso, OctreeRender_trilinear_fast, cal_n_samples
 from .variants import NerfPlusPlus, REFTensoRF
 
 MODELS = {"TensorVMSplit": TensorVMSplit, "TensorCP": TensorCP, "REFTensoRF": REFTensoRF, "NerfPlusPlus": NerfPlusPlus}
-RENDER_ONLY_MODELS = ("TensorCP",)       # constructed, loaded and rendered (render_test); their training kernels are not built
+RENDER_ONLY_MODELS = ("TensorCP",)       # constructed, loaded and rendered (render_test) by default; TensorCP trains with --cp_training 1
 
 
 def parse_config_file(path: str) -> Dict[str, object]:
@@ -76,6 +76,8 @@ def config_parser(cmd: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--model_name", type=str, default="TensorVMSplit", choices=["TensorVMSplit", "TensorCP", "NerfPlusPlus", "REFTensoRF"])
     # (not a reference option) arithmetic of the appearance network in the evaluation renders: field.py `mlp_arith`, include/tvr.h TVR_ARITH_*; training is fp32-class always
     p.add_argument("--mlp_arith", type=str, default="f32", choices=["f32", "f16act", "f16"])
+    # (not a reference option) 1 = train a TensorCP model through the CP backward kernels (cp.TensorCP.cp_training); 0 = TensorCP only renders, as before
+    p.add_argument("--cp_training", type=int, default=0)
     p.add_argument("--dataset_name", type=str, default="blender", choices=["blender", "llff", "nsvf", "dtu", "tankstemple", "own_data"])
     for name in ("with_depth", "lindisp", "white_bkgd"):
         p.add_argument("--" + name, action="store_true")
@@ -423,9 +425,12 @@ def reconstruction(args, device="cuda", log=print, train_dataset=None, val_datas
     """train.py:113-371.  Returns (tensorf, logfolder, PSNRs_test of the last visualisation or final test).
     `train_dataset` / `val_dataset`: ready-made datasets (objects with all_rays, all_rgbs, scene_bbox, white_bg, near_far as BlenderRays has them) instead of the
     Blender folder under args.datadir — synthetic training sets (scripts/reconstruction_timing.py)."""
-    if getattr(args, "model_name", None) in RENDER_ONLY_MODELS:          # before any data is touched
-        raise NotImplementedError(f"model_name {args.model_name!r}: CP training is not built (no backward kernels for the CP march and features yet); "
-                                  "a CP checkpoint renders through --render_only 1 --ckpt ...")
+    cp_training = bool(int(getattr(args, "cp_training", 0) or 0))
+    if getattr(args, "model_name", None) in RENDER_ONLY_MODELS and not cp_training:          # before any data is touched
+        raise NotImplementedError(f"model_name {args.model_name!r}: CP training is not built into the default path (the CP backward kernels are opt-in: pass "
+                                  "--cp_training 1); a CP checkpoint renders through --render_only 1 --ckpt ...")
+    if getattr(args, "model_name", None) == "TensorCP" and float(getattr(args, "Ortho_weight", 0.0) or 0.0) > 0:
+        raise ValueError("Ortho_weight > 0 with TensorCP: the class has no vector_comp_diffs (tensoRF.py:317-447); set Ortho_weight to 0")
     if args.dataset_name != "blender":
         raise NotImplementedError("only the Blender loader exists in the reference (dataLoader/__init__.py)")
     if args.model_name not in MODELS:
@@ -468,6 +473,8 @@ def reconstruction(args, device="cuda", log=print, train_dataset=None, val_datas
         if isinstance(tensorf, NerfPlusPlus):
             tensorf.set_nerfplusplus(bg_freq=args.bg_freq, bg_view_freq=args.bg_view_freq, bg_D=args.bg_D, radii=args.radii)
         tensorf.mlp_arith = getattr(args, "mlp_arith", "f32")            # (the evaluation renders of the run; the training steps compute fp32-class whatever it says)
+    if cp_training and isinstance(tensorf, TensorCP):
+        tensorf.cp_training = True                                       # opt in to the CP backward kernels (cp.py); the eager chain, no fused step
 
     if args.lr_decay_iters > 0:
         lr_factor = args.lr_decay_target_ratio ** (1 / args.lr_decay_iters)
