@@ -19,7 +19,7 @@
 // The transmittance is a 6-step wave scan (DPP/shuffle) with the carry in a register; the ray stops once T < eps_T
 // (eps_T <= weight threshold, so no appearance sample is ever skipped).  Appearance samples (w > thres) are compacted
 // with a ballot into a per-wave LDS list and flushed once per ray into a contiguous, sample-ordered segment of the
-// global queue (one atomicAdd per ray) -> the compositing order per ray is fixed, results are deterministic.
+// global queue (one atomicAdd per ray; the volume marches: one for up to MARCH_PEND rays, tvr_march_body.h) -> the compositing order per ray is fixed, results are deterministic.
 #include <cstdlib>
 #include "tvr_device.h"
 #include "tvr_kernels.h"
@@ -47,13 +47,16 @@ __global__ __launch_bounds__(64 * MARCH_MAX_WAVES) void march_kernel(const Scene
 // a group needs its header and 6 B per sample and wave; the launch shape and why: tvr_march_body.h (MARCH_VOL_*), DESIGN.md 4.1.
 // PLAIN (only with !DENSE): the instantiation the frames of a plain scene run — no alpha volume, no explicit depths, no lam6, a volume below 4 GiB (launch_march_vol
 // checks); those paths are absent from it at compile time and vol_density32 addresses the volume with 32-bit offsets (tvr_march_body.h).
-template <bool DENSE, bool PLAIN>
+// BATCH: one queue reservation for several rays (MARCH_BATCH, tvr_march_body.h).  A launch with no more rays than waves (a 4096-ray chunk on 256 CUs) has nothing to batch —
+// every wave marches about one ray — and the way through the waiting ray's record would add its latency to every such call (measured: 157 calls per frame, +0.08 ms), so
+// launch_march_vol gives it the unbatched instantiation; the two write the same queue entries for a ray, so which one runs changes no result.
+template <bool DENSE, bool PLAIN, bool BATCH>
 __global__ __launch_bounds__(64 * MARCH_VOL_WAVES, DENSE ? MARCH_VOL_OCC - 1 : MARCH_VOL_OCC) void march_vol_kernel(const SceneDev sc, const float *__restrict__ dvol, const float *__restrict__ rays,
                                                                          const int n_rays, const int S, const int s_cap, const MarchSampling sm, const float eps_T,
                                                                          MarchOut mo, const tvr_dense_out dn)
 {
     static_assert(!(PLAIN && DENSE), "the plain form has no dense outputs");
-    constexpr bool LDSL = false, CP = false, VOL = true;
+    constexpr bool LDSL = false, CP = false, VOL = true, MARCH_BATCH = BATCH;
     const CpDev cp = {};
 #include "tvr_march_body.inc"
 }
@@ -270,24 +273,38 @@ static hipError_t launch_march_vol(const SceneDev &sc, const float *dvol, const 
                                    const tvr_dense_out *dense, hipStream_t stream)
 {
     const int groups = MARCH_VOL_GROUPS;                     // per CU
-    const size_t kLds = 160 * 1024 / (size_t)groups, per_wave = (size_t)S * 6, fixed = MARCH_HDR + 64;
-    int waves = (int)((kLds - fixed) / per_wave);
-    waves = waves >= MARCH_VOL_WAVES ? MARCH_VOL_WAVES : (waves >= 8 ? 8 : (waves >= 4 ? 4 : (waves >= 2 ? 2 : 1)));
-    const size_t lds = fixed + (size_t)waves * per_wave;
+    const size_t kLds = 160 * 1024 / (size_t)groups, per_list = (size_t)S * 6, fixed = MARCH_HDR + 64;
     const int n_tiles = (n_rays + MARCH_TILE - 1) / MARCH_TILE;
-    long long grid = (long long)device_cu_count() * groups * (MARCH_VOL_WAVES / waves);
-    if (grid > n_tiles) grid = n_tiles;
-    if (grid < 1) grid = 1;
+    int waves = 1;
+    size_t lds = 0;
+    long long grid = 1;
+    // per wave: the list (6 B per sample) and, in a launch that batches, `per_pend` bytes behind the lists (16-byte aligned) for the records of the waiting rays
+    auto shape = [&](size_t per_pend) {
+        const int w = (int)((kLds - fixed - (per_pend ? 16 : 0)) / (per_list + per_pend));
+        waves = w >= MARCH_VOL_WAVES ? MARCH_VOL_WAVES : (w >= 8 ? 8 : (w >= 4 ? 4 : (w >= 2 ? 2 : 1)));
+        lds = per_pend ? fixed + (((size_t)waves * per_list + 15) & ~(size_t)15) + (size_t)waves * per_pend : fixed + (size_t)waves * per_list;
+        grid = (long long)device_cu_count() * groups * (MARCH_VOL_WAVES / waves);
+        if (grid > n_tiles) grid = n_tiles;
+        if (grid < 1) grid = 1;
+    };
+    shape(0);                                                              // the unbatched launch: the parent's shape and LDS
+    // more rays than waves: a wave marches several and reserves once for a batch of them (MARCH_BATCH, tvr_march_body.h); the records may then cost a step in waves per group
+    // (512 samples: 16 waves either way; the step from 16 to 8 waves moves from 1702 to 1637 samples), with as many more groups
+    const bool batch = (long long)n_rays > grid * (long long)waves;
+    if (batch) shape((size_t)MARCH_PEND * MARCH_PEND_WORDS * 4);
     tvr_dense_out none = {};
     const tvr_dense_out &dn = dense ? *dense : none;
     const unsigned long long vol_bytes = 4ull * (unsigned long long)(sc.grid[0] + 1) * (unsigned long long)(sc.grid[1] + 1) * (unsigned long long)(sc.grid[2] + 1);
     const bool plain = !dense && sc.avol == nullptr && sm.zv == nullptr && mo.lam6 == nullptr && vol_bytes < (1ull << 32);
-    const void *fn = dense ? (const void *)march_vol_kernel<true, false> : (plain ? (const void *)march_vol_kernel<false, true> : (const void *)march_vol_kernel<false, false>);
-    hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t rc = hipSuccess;
+    auto go = [&](auto kern) {
+        rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (rc == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
+    };
+    if (dense) batch ? go(march_vol_kernel<true, false, true>) : go(march_vol_kernel<true, false, false>);
+    else if (plain) batch ? go(march_vol_kernel<false, true, true>) : go(march_vol_kernel<false, true, false>);
+    else batch ? go(march_vol_kernel<false, false, true>) : go(march_vol_kernel<false, false, false>);
     if (rc != hipSuccess) return rc;
-    if (dense) hipLaunchKernelGGL((march_vol_kernel<true, false>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
-    else if (plain) hipLaunchKernelGGL((march_vol_kernel<false, true>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
-    else hipLaunchKernelGGL((march_vol_kernel<false, false>), dim3((unsigned)grid), dim3(64 * waves), lds, stream, sc, dvol, rays, n_rays, S, S, sm, eps_T, mo, dn);
     return hipGetLastError();
 }
 

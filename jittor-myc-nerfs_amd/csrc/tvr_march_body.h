@@ -30,6 +30,10 @@
 // After the trim (profiles/march_trim.txt) the plain form holds 39 registers and the shape was measured again on the frame in pieces: 1 x 16 waves 12.76 - 12.77 ms,
 // 1 x 8 13.5, 2 x 8 13.3, 2 x 16 14.1.  The launch bound now matters for the SCALAR file: bound (1024, 7) gives the plain form 96 SGPRs and no spill, and the frame
 // 13.95 ms instead of 12.5 — the ten values that spill under (1024, 8) are all outside the chunk loop and stay spilled.
+// With the queue reservations batched (MARCH_BATCH below; profiles/march_batch.txt) the kernel is no longer pinned by the queue counter's line — which is why it had
+// ignored occupancy — and the shape and the hand-out word were measured once more on the frame in pieces: 1 x 16 waves 11.86 - 11.99 ms (kept), 1 x 8 12.06 - 12.10, 2 x 8
+// 12.00 - 12.20, 2 x 16 12.31 - 12.33; MARCH_CTR_WORD 32 11.78 - 12.02 (inside the spread: word 1 stays, although the march ALONE gains 0.3 ms with its hand-out on a
+// line of its own, 2.46 -> 2.15 ms).  One group of 16 waves wins by less than before, and 2 x 16 still loses to the co-scheduled shade kernel.
 #ifndef MARCH_VOL_WAVES
 #define MARCH_VOL_WAVES 16                // waves per group
 #endif
@@ -110,6 +114,24 @@ __device__ __forceinline__ float vol_density(const float *__restrict__ D, int gx
 // The plain form of the volume march (march_vol_kernel<false, true>: no alpha volume, no explicit depths, no lam6, a volume below 4 GiB — launch_march_vol checks) is
 // compiled without those paths; kernels that do not name PLAIN themselves (march_kernel, cp_march_kernel) see this `false`.
 constexpr bool PLAIN = false;
+
+// Queue reservations of the volume marches (march_vol_kernel, all three forms).  A returning atomicAdd on the queue counter per ray with appearance samples pinned
+// the kernel: 384 000 of them per bench frame plus 40 000 tile hand-outs on one 128-byte line, at the ~88 per microsecond one word sustains, are 4.8 ms of a 4.95 ms
+// kernel (profiles/march_batch.txt, block A: 1.63 ms with the reservations off that line).  So a wave keeps the lists of up to MARCH_PEND finished rays in the list
+// it already owns (bufw / bufj: a RING of s_cap entries, the ray in progress appending at the tail) and reserves ONCE for all of them:
+//   - a ray's record {o, d, tmin, jitter, ray, first entry within the batch} waits in LDS (MARCH_PEND_WORDS words; MARCH_PEND of them per wave) — not in scalar
+//     registers, which the chunk loop has none to spare of (the scalar budget above);
+//   - the flush adds the batch's total to the counter, writes ray_off of its rays and the entries: a lane finds its entry's ray by comparing its index with the
+//     <= MARCH_PEND first-entry numbers, and recomputes q_pos from the record with the expressions (and therefore the bits) of the unbatched write;
+//   - it runs when MARCH_PEND rays wait, when the ray in progress needs room the waiting rays hold (a ray alone never exceeds s_cap, so it fits afterwards and nothing
+//     is copied), and behind the ray loop, which every exit — queue exhausted, both fault breaks — leaves through.
+// acc, depth, ray_cnt (and ray_off = 0 of a ray without entries) are written when the ray ends, as before.  The queue stays contiguous, *counter exact, a ray's
+// segment contiguous and in sample order; only the order of the segments changes, which already depended on which wave finished first.
+// Kernels that do not name MARCH_BATCH themselves (march_kernel, cp_march_kernel) see this `false` and compile to what they were; march_vol_kernel names it after its BATCH
+// parameter, which launch_march_vol sets for launches with more rays than waves (tvr_march.hip).
+constexpr bool MARCH_BATCH = false;
+#define MARCH_PEND 8                      // rays per reservation at most
+#define MARCH_PEND_WORDS 12               // a waiting ray's record, 32-bit words: o[3], d[3], tmin, jitter, ray, first entry, 2 of padding
 
 // What a march touches once per ray — the ray and jitter arrays in front of the chunk loop, the outputs behind it — costs the chunk loop scalar registers for nothing:
 // kernel arguments are loaded at the kernel's entry and stay live (march_vol_kernel<false> kept 100 of them in spilled lanes, 40 v_readlane_b32 inside the chunk loop).
@@ -227,4 +249,46 @@ __device__ __forceinline__ void scan_mul_dpp(float &x, float &excl, float &last)
     }
     excl = march_up<1>(x);
     last = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+}
+
+// The flush of MARCH_BATCH (above): one reservation for the n_pend rays whose entries stand at [ring_head, ring_head + pend_total) of the wave's ring, then their ray_off
+// and entries.  The three numbers are the same in every lane (the body keeps them in vector registers); they come back as the empty set behind the flushed entries.
+template <bool PLAIN_F>
+__device__ __forceinline__ void march_flush(const SceneDev &sc, const MarchSampling &sm, const MarchOut &mo, const int S, const int s_cap, const int lane, const float *bufw,
+                                            const unsigned short *bufj, const float *pend, int &ring_head, int &pend_total, int &n_pend)
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const MarchOut mf = march_arg_now<PLAIN_F>(mo, offsetof(MarchVolArgs, mo));
+    const bool jit_f = march_arg_now<PLAIN_F>(sm.jitter, offsetof(MarchVolArgs, sm.jitter)) != nullptr;
+    const int f_total = __builtin_amdgcn_readfirstlane(pend_total), f_rays = __builtin_amdgcn_readfirstlane(n_pend), f_head = __builtin_amdgcn_readfirstlane(ring_head);
+    unsigned fbase = 0;
+    if (lane == 0) fbase = atomicAdd(mf.counter, (unsigned)f_total);          // ONE reservation for the f_rays rays
+    fbase = __builtin_amdgcn_readfirstlane(fbase);
+    if (lane < f_rays) mf.ray_off[__float_as_uint(pend[lane * MARCH_PEND_WORDS + 8])] = fbase + __float_as_uint(pend[lane * MARCH_PEND_WORDS + 9]);
+    for (int i = lane; i < f_total; i += 64) {
+        int k = 0;                                                            // the ray of entry i: the last one whose first entry is <= i
+        for (int m = 1; m < f_rays; ++m) k += (unsigned)i >= __float_as_uint(pend[m * MARCH_PEND_WORDS + 9]) ? 1 : 0;
+        const float *rec = pend + k * MARCH_PEND_WORDS;
+        int rp = f_head + i;
+        if (rp >= s_cap) rp -= s_cap;
+        const unsigned ej = bufj[rp];
+        const unsigned eray = __float_as_uint(rec[8]);
+        float fj = (float)ej;
+        if (jit_f) fj = fj + rec[7];
+        const float *__restrict__ zr = (!PLAIN_F && sm.zv) ? sm.zv + (size_t)eray * S : nullptr;
+        const float z = zr ? zr[ej] : rec[6] + sc.step * fj;
+        float4 qv;
+        qv.x = ((rec[0] + rec[3] * z) - sc.lo[0]) * sc.inv[0] - 1.0f;
+        qv.y = ((rec[1] + rec[4] * z) - sc.lo[1]) * sc.inv[1] - 1.0f;
+        qv.z = ((rec[2] + rec[5] * z) - sc.lo[2]) * sc.inv[2] - 1.0f;
+        qv.w = bufw[rp];
+        mf.q_pos[fbase + i] = qv;
+        mf.q_ray[fbase + i] = eray;
+        if (mf.q_j) mf.q_j[fbase + i] = ej;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    ring_head = f_head + f_total >= s_cap ? f_head + f_total - s_cap : f_head + f_total;
+    pend_total = 0;
+    n_pend = 0;
+    asm volatile("" : "+v"(ring_head), "+v"(pend_total), "+v"(n_pend));
 }

@@ -6,7 +6,7 @@
 // `dvol` (the baked density volume, tvr_scene_set_density_volume; unused unless VOL).
     static_assert(!(CP && LDSL), "the CP lines (up to 96 channels) do not go through LDS");
     static_assert(!(VOL && (CP || LDSL)), "the baked volume replaces the factored evaluation: no lines in LDS, no CP lines");
-    // LDS: [cursor 16 B][lines: 3 x (L+1) x 4 float4, LDSL only][per-wave weight lists f32 s_cap][per-wave sample lists u16 s_cap]
+    // LDS: [cursor 16 B][lines: 3 x (L+1) x 4 float4, LDSL only][per-wave weight lists f32 s_cap][per-wave sample lists u16 s_cap][MARCH_BATCH, 16-byte aligned: per-wave records of the rays that wait for their reservation]
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -17,8 +17,8 @@
     const float4 *ls1 = ls0 + ln0, *ls2 = ls1 + ln1;                     // line i runs along axis vecMode[i] = 2 - i
     float *bufw = (float *)(ls2 + ln2) + (size_t)wave * s_cap;
     unsigned short *bufj = (unsigned short *)((float *)(ls2 + ln2) + (size_t)n_waves * s_cap) + (size_t)wave * s_cap;
-#ifdef TVR_MARCH_TIMELINE                               // diagnostic build (scripts/march_timeline.py): stats[32 + 8 b ..] = {start, filled, first wave end, last wave end, chunks, rays} of group b, 100 MHz ticks
-    unsigned long long tl_chunks = 0ull, tl_rays = 0ull;
+#ifdef TVR_MARCH_TIMELINE                               // diagnostic build (scripts/march_timeline.py): stats[32 + 8 b ..] = {start, filled, first wave end, last wave end, chunks, rays | queue reservations << 32} of group b, 100 MHz ticks
+    unsigned long long tl_chunks = 0ull, tl_rays = 0ull, tl_resv = 0ull;
     if (mo.stats && threadIdx.x == 0) mo.stats[32 + 8 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
     if (threadIdx.x == 0) *cursor = 0u;
@@ -51,6 +51,17 @@
     // shade 15.25 vs 15.65 ms against per-XCD contiguous bands), and a launch with few tiles per group has no tail.
     unsigned long long st_eval = 0, st_bbox = 0, st_term = 0;
     int last_start = 0;                                  // first ray of this wave's previous handout (dynamic queue: picks the tail granularity)
+
+    // MARCH_BATCH (tvr_march_body.h): the wave's list is a ring of s_cap entries; [ring_head, ring_head + pend_total) are the entries of the n_pend finished rays that
+    // wait for their reservation, the ray in progress appends behind them.  The waiting rays' records stand behind the groups' lists in LDS.
+    // The three numbers are the same in every lane and are KEPT IN VECTOR REGISTERS (the empty asm makes them opaque): the chunk loop has no scalar register to spare
+    // (tvr_march_body.h, the scalar budget) and what it does with them — an entry's position, the test for room — is vector arithmetic anyway.
+    int ring_head = 0, pend_total = 0, n_pend = 0;
+    float *pend = nullptr;
+    if constexpr (MARCH_BATCH) {
+        pend = (float *)(lds_raw + ((MARCH_HDR + (size_t)n_waves * s_cap * 6 + 15) & ~(size_t)15)) + (size_t)wave * (MARCH_PEND * MARCH_PEND_WORDS);
+        asm volatile("" : "+v"(ring_head), "+v"(pend_total), "+v"(n_pend));
+    }
 
     for (;;) {
         unsigned ci = 0;
@@ -134,7 +145,14 @@
         int napp = 0;
         bool seen = false, terminated = false;
         int c = 0;
+        bool make_room = false;                            // MARCH_BATCH: the chunk loop was left for a flush and goes on at chunk c
+        for (;;) {
         for (; c * 64 < S; ++c) {
+            if constexpr (MARCH_BATCH) {
+                // Before a chunk, never inside one (the flush's registers would be the chunk loop's): the waiting rays leave when MARCH_PEND of them wait or when
+                // they hold room this chunk's up to 64 entries may need.  A ray alone never exceeds s_cap, so behind the flush the chunk always fits.
+                if (__ballot(n_pend > 0 && (n_pend == MARCH_PEND || pend_total + napp + 64 > s_cap))) { make_room = true; break; }      // (the ballot: a scalar branch)
+            }
             const int j = c * 64 + lane;
             const bool inr = j < S;
             float fj = (float)j, fj1 = (float)(j + 1);
@@ -269,6 +287,14 @@
             dep_l += wgt * z;
             const bool app = wgt > sc.thres;                       // :513
             const unsigned long long ma = __ballot(app);
+            if constexpr (MARCH_BATCH) {
+                if (ma) {
+                    int pos = ring_head + pend_total + napp + __popcll(ma & ((1ull << lane) - 1ull));
+                    if (pos >= s_cap) pos -= s_cap;
+                    if (app) { bufw[pos] = wgt; bufj[pos] = (unsigned short)j; }
+                    napp += __popcll(ma);
+                }
+            } else
             if (ma) {
                 const int pos = napp + __popcll(ma & ((1ull << lane) - 1ull));
                 if (app) { bufw[pos] = wgt; bufj[pos] = (unsigned short)j; }
@@ -284,6 +310,13 @@
                 if (dn.weight) dn.weight[q] = wgt;
             }
             if (T < eps_T) { terminated = true; ++c; break; }
+        }
+        if (!make_room) break;
+#ifdef TVR_MARCH_TIMELINE
+        tl_resv++;
+#endif
+        if constexpr (MARCH_BATCH) march_flush<PLAIN>(sc, sm, mo, S, s_cap, lane, bufw, bufj, pend, ring_head, pend_total, n_pend);
+        make_room = false;
         }
         if (DENSE) {
             // samples never visited (early exit) get zeros so the dense arrays are fully defined
@@ -311,7 +344,38 @@
         const float acc = wave_sum(acc_l);
         const float dep = wave_sum(dep_l);
         const MarchOut mt = march_arg_now<PLAIN>(mo, offsetof(MarchVolArgs, mo));
+        if constexpr (MARCH_BATCH) {
+            // the ray's own outputs now; its entries and ray_off with the wave's next reservation (march_flush)
+            if (lane == 0) {
+                if (napp == 0) mt.ray_off[ray] = 0u;
+                mt.ray_cnt[ray] = (unsigned)napp;
+                mt.acc[ray] = acc;
+                mt.depth[ray] = dep + (1.0f - acc) * d[2];            // :531 (rays[..., -1] is d_z)
+                if (!PLAIN && mt.lam6) mt.lam6[ray] = lam6 * expf((float)(S - n6) * 9.5367386e-7f);
+                if (DENSE) {
+                    if (dn.bg_weight) dn.bg_weight[ray] = T;
+                    if (dn.acc) dn.acc[ray] = acc;
+                    if (dn.t_min) dn.t_min[ray] = tmin;
+                }
+            }
+            if (napp > 0) {
+                if (lane == 0) {
+                    float *rec = pend + n_pend * MARCH_PEND_WORDS;      // (n_pend < MARCH_PEND: a full set left before this ray's first chunk)
+                    rec[0] = o[0]; rec[1] = o[1]; rec[2] = o[2];
+                    rec[3] = d[0]; rec[4] = d[1]; rec[5] = d[2];
+                    rec[6] = tmin; rec[7] = u;
+                    rec[8] = __uint_as_float((unsigned)ray); rec[9] = __uint_as_float((unsigned)pend_total);
+                }
+                pend_total += napp;
+                ++n_pend;
+                asm volatile("" : "+v"(pend_total), "+v"(n_pend));
+            }
+            continue;
+        }
         unsigned base = 0;
+#ifdef TVR_MARCH_TIMELINE
+        if (napp > 0) tl_resv++;
+#endif
         if (lane == 0 && napp > 0) base = atomicAdd(mt.counter, (unsigned)napp);
         base = __shfl(base, 0);
         if (lane == 0) {
@@ -344,13 +408,19 @@
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
+    if constexpr (MARCH_BATCH) {
+#ifdef TVR_MARCH_TIMELINE
+        if (__ballot(n_pend > 0)) tl_resv++;
+#endif
+        if (__ballot(n_pend > 0)) march_flush<PLAIN>(sc, sm, mo, S, s_cap, lane, bufw, bufj, pend, ring_head, pend_total, n_pend);       // every exit of the ray loop comes through here: the queue ran out, or one of the two fault breaks
+    }
 #ifdef TVR_MARCH_TIMELINE
     if (mo.stats && lane == 0) {
         const unsigned long long te = __builtin_amdgcn_s_memrealtime();
         atomicMin((unsigned long long *)&mo.stats[32 + 8 * blockIdx.x + 2], te);
         atomicMax((unsigned long long *)&mo.stats[32 + 8 * blockIdx.x + 3], te);
         atomicAdd((unsigned long long *)&mo.stats[32 + 8 * blockIdx.x + 4], tl_chunks);
-        atomicAdd((unsigned long long *)&mo.stats[32 + 8 * blockIdx.x + 5], tl_rays);
+        atomicAdd((unsigned long long *)&mo.stats[32 + 8 * blockIdx.x + 5], tl_rays | (tl_resv << 32));
     }
 #endif
     unsigned long long *const stats_r = march_arg_now<PLAIN>(mo.stats, offsetof(MarchVolArgs, mo.stats));

@@ -6,7 +6,9 @@ kernel's resource metadata from the code object's notes.  isa_check names branch
 in front of them is added or removed, so the labels are renumbered per kernel in order of appearance; nothing else is normalised.
 Exit status 1 on any `differs` or `only in NEW`.
 
-usage: isa_diff.py OLD.so NEW.so
+usage: isa_diff.py OLD.so NEW.so [OLD_KERNEL=NEW_KERNEL ...]
+Each further argument names a kernel of OLD and the kernel of NEW that took its place under another (mangled) name — a template that gained a parameter —
+and is compared like a pair of equal names: `renamed identical` / `renamed differs`.  They count for the exit status like the others.
 """
 import hashlib
 import os
@@ -66,7 +68,7 @@ def load(path):
     return ks, md
 
 
-def main(old, new):
+def main(old, new, renamed=()):
     (ko, mo), (kn, mn) = load(old), load(new)
     for tag, p, ks in (("OLD", old, ko), ("NEW", new, kn)):
         print(f"{tag} {p}  sha256 {hashlib.sha256(open(p, 'rb').read()).hexdigest()}  kernels {len(ks)}  instructions {sum(len(v) for v in ks.values())}")
@@ -90,10 +92,17 @@ def main(old, new):
         bad += verdict.startswith(("differs", "only in NEW"))
         print(f"{verdict:12s} {k}")
     print("  ".join(f"{v} {k}" for k, v in count.items()))
+    for pair in renamed:
+        a, b = pair.split("=")
+        if a not in ko or b not in kn:
+            sys.exit(f"{pair}: no such kernel in {'OLD' if a not in ko else 'NEW'}")
+        same = ko[a] == kn[b] and mo[a] == mn[b]
+        bad += not same
+        print(f"renamed {'identical' if same else 'differs'} (instructions {len(ko[a])} -> {len(kn[b])}; metadata {'equal' if mo[a] == mn[b] else 'differs'})  {a}  ->  {b}")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    if len(sys.argv) < 3 or not all("=" in a for a in sys.argv[3:]):
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], sys.argv[3:]))

@@ -51,7 +51,9 @@ for n in sizes:
         if os.environ.get("TL_XCDCLK"):                   # a -DS16_XCDCLK build: slots 4 / 5 hold wave 0's shader-clock / 100 MHz ticks over the shade kernel
             ghz = 0.1 * t[:, 4] / np.maximum(t[:, 5], 1)
             print("           shader clock per XCD, GHz      : " + " ".join(f"{ghz[(np.arange(len(ghz)) % 8) == k].mean():8.3f}" for k in range(8)))
-    ch, ry = t[:, 4], t[:, 5]
+    raw5 = st[32:].view(256, 8)[:, 5].cpu().numpy()[live]        # rays | queue reservations << 32 (csrc/tvr_march_body.inc)
+    ch, ry, resv = t[:, 4], (raw5 & 0xFFFFFFFF).astype(np.float64), (raw5 >> 32).astype(np.float64)
+    print(f"  queue reservations: {resv.sum():.0f} for {ry.sum():.0f} rays of the launch ({resv.sum() / max(ry.sum(), 1):.3f} per ray)")
     busy = (t[:, 3] - t[:, 1]) / 100.0
     print(f"  chunks / group: min {ch.min():.0f} median {np.median(ch):.0f} max {ch.max():.0f}; rays / group median {np.median(ry):.0f}; us per chunk and group (busy / chunks): median {np.median(busy / np.maximum(ch, 1)):.3f}")
     print(f"  per-wave chain: {np.median(busy) :.1f} us busy per group for {np.median(ch) / 16:.1f} chunks per wave -> {np.median(busy) / max(np.median(ch) / 16, 1e-9):.2f} us per chunk in a wave's chain")
