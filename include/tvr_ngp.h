@@ -84,7 +84,12 @@ int tvr_ngp_net_pack(const tvr_ngp_net_params *params, void *packed, size_t pack
 /* NGPNetworks.execute_ (ngp_network.py:78-85) fused: positions [n, pos_stride floats] in [0,1], directions warped to [0,1]
  * [n, dir_stride floats] (the sampler's rows: coords, stride 7 and coords+4, stride 7) -> out [n,4] = (rgb raw, density raw).
  * n is read from n_dev[0] (uint32, device; e.g. counter+1 of tvr_ngp_sample) when n_dev != NULL, clamped to n_max;
- * otherwise n = n_max. */
+ * otherwise n = n_max.  Rows of `out` from n on are left as they were.
+ * Valid range: the default build hands the hash features, every hidden activation, the 16 density outputs and the SH values from one
+ * layer to the next as TWO fp16 halves (hi = the value rounded toward zero, lo = the remainder), which sum to the value exactly only
+ * while |value| <= 65504, the largest finite fp16.  Above that the hi half saturates: the outputs stay finite but are WRONG, and
+ * nothing reports it.  Outputs are held to 2e-4 * max(1, |out|) against fp64 up to half that range (3e4).  The same holds for
+ * tvr_ngp_render, which runs the same network code. */
 int tvr_ngp_network(const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const void *net_packed, const void *positions, int32_t pos_stride,
                     const void *dirs, int32_t dir_stride, int64_t n_max, const void *n_dev, void *out, void *stream);
 
@@ -98,6 +103,10 @@ int tvr_ngp_composite(const void *net_out, const void *coords, const void *numst
  * composites them in order, stopping at the sample where compute_rgbs_inference breaks (T < 1e-4) — the samples behind it
  * contribute nothing, so their gathers and networks are skipped.  cfg->slab_rays = n_rays_per_batch reproduces the slab loop's
  * jitter.  rgb [n_rays,3]; stats (optional, device) uint64[2] = (samples evaluated, samples marched).
+ * "Evaluated" counts WHOLE TILES of 32 steps (the last tile of a ray counts its real steps only), up to and including the tile that
+ * holds the break: a ray of n steps adds n if it never breaks, and min(n, 32 * (b / 32 + 1)) if it breaks at sample b (the first
+ * sample that sees T < 1e-4 in front of it) — the samples of that tile behind b went through the networks although they are not
+ * composited.  A ray without steps adds nothing and receives the background itself; stats are zeroed even when n_rays == 0.
  * scratch: tvr_ngp_render_scratch_bytes(n_rays). */
 size_t tvr_ngp_render_scratch_bytes(int64_t n_rays);
 int tvr_ngp_render(const tvr_ngp_march_cfg *cfg, const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const void *net_packed, const void *rays_o,
