@@ -30,8 +30,10 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#define S16_WAVES 8         // two waves per SIMD
+#define S16_WAVES 8         // the factored kernel: two waves per SIMD
 #define S16_THREADS (64 * S16_WAVES)
+#define S16_VOL_WAVES 12    // the volume kernel: three, their matrix phases side by side (no matrix token)
+#define S16_VOL_THREADS (64 * S16_VOL_WAVES)
 #define S16_TILE 32
 #ifndef S16_PRIO_M
 #define S16_PRIO_M 2      // s_setprio in the matrix phase / the gather phase / layer 3's tail (the 32x32 kernel's measured choice)
@@ -42,7 +44,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef S16_PD
 #define S16_PD 2          // A-fragment pairs are read this many row blocks ahead, ring of S16_PD + 2
 #endif
-#define S16_RN (S16_PD + 2)
+#define S16_VOL_PD 1      // the volume kernel's: 8 registers fewer, what three waves per SIMD need (168 VGPRs)
 #ifndef S16_MSLEEP
 #define S16_MSLEEP 2
 #endif
@@ -234,14 +236,21 @@ template <bool RC, bool REF>
 __global__ __launch_bounds__(S16_THREADS, 2) void shade16_kernel(const SceneDev sc, const ShadeArgs a)
 {
     constexpr bool VOL = false;
+    constexpr int NW = S16_WAVES, PD = S16_PD;
+    constexpr bool TOKEN = true;
     const float4 *const fvol = nullptr;
 #include "tvr_shade16_body.inc"
 }
 
 template <bool RC>
-__global__ __launch_bounds__(S16_THREADS, 2) void shade16_vol_kernel(const SceneDev sc, const ShadeArgs a, const float4 *__restrict__ fvol)
+__global__ __launch_bounds__(S16_VOL_THREADS, 3) void shade16_vol_kernel(const SceneDev sc, const ShadeArgs a, const float4 *__restrict__ fvol)
 {
     constexpr bool REF = false, VOL = true;
+    constexpr int NW = S16_VOL_WAVES, PD = S16_VOL_PD;
+    // A matrix phase alone keeps the vector-issue port 58 % busy (6.0 k issue cycles in 10.3 k: MFMA -> VALU chains, fragment reads), and behind the token a SIMD is in
+    // exactly one matrix phase at a time: the gather was hidden already, the slack sat inside the phase.  Three waves without the token fill each other's gaps
+    // (profiles/shade_vol_overlap.txt: 10.2 -> 9.3 ms; three waves WITH the token: 10.4).
+    constexpr bool TOKEN = false;
 #include "tvr_shade16_body.inc"
 }
 
@@ -258,8 +267,8 @@ hipError_t launch_shade16(const SceneDev &sc, const ShadeArgs &a, hipStream_t st
     if (e != hipSuccess) return e;
     unsigned grid = 256;       // one workgroup per CU (the LDS holds the weights), persistent over 32-entry tiles
     if (fvol) {
-        if (rc) hipLaunchKernelGGL((shade16_vol_kernel<true>), dim3(grid), dim3(S16_THREADS), lds, stream, sc, a, fvol);
-        else hipLaunchKernelGGL((shade16_vol_kernel<false>), dim3(grid), dim3(S16_THREADS), lds, stream, sc, a, fvol);
+        if (rc) hipLaunchKernelGGL((shade16_vol_kernel<true>), dim3(grid), dim3(S16_VOL_THREADS), lds, stream, sc, a, fvol);
+        else hipLaunchKernelGGL((shade16_vol_kernel<false>), dim3(grid), dim3(S16_VOL_THREADS), lds, stream, sc, a, fvol);
     } else if (ref) {
         if (rc) hipLaunchKernelGGL((shade16_kernel<true, true>), dim3(grid), dim3(S16_THREADS), lds, stream, sc, a);
         else hipLaunchKernelGGL((shade16_kernel<false, true>), dim3(grid), dim3(S16_THREADS), lds, stream, sc, a);

@@ -1,5 +1,8 @@
 // tvr_shade16_body.inc — the body of shade16_kernel and shade16_vol_kernel (tvr_shade16.hip), shared as text like the march's (tvr_march_body.inc): the including kernel
-// provides the parameters `sc`, `a`, the compile-time switches RC, REF, VOL and, for VOL, the volume pointer `fvol`.
+// provides the parameters `sc`, `a`, the compile-time switches RC, REF, VOL, the waves per workgroup NW (a multiple of 4: NW / 4 waves per SIMD), TOKEN (the matrix
+// phases of a SIMD's waves take turns behind its matrix token, or run side by side), the read-ahead PD of the A-fragment ring and, for VOL, the volume pointer `fvol`.
+    static_assert(NW % 4 == 0 && NW >= 8 && NW <= 16 && PD >= 1, "NW / 4 waves per SIMD, ring of PD + 2");
+    constexpr int RN = PD + 2;
     static_assert(!(REF && VOL), "REFTensoRF's heads read h: no volume form");
     constexpr int IMAGE_BYTES = VOL ? TVR16_BASH : TVR16_IMAGE_BYTES;       // VOL: no basis fragments in LDS
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -9,19 +12,21 @@
     const bool up = g >= 2;                                       // upper half of the wave: loads entry B's queue record, packs entry B's k-step 4
     {
         const uint4 *src = (const uint4 *)sc.img16;
-        for (int i = tid; i < IMAGE_BYTES / 16; i += S16_THREADS) ((uint4 *)smem)[i] = src[i];
+        for (int i = tid; i < IMAGE_BYTES / 16; i += (64 * NW)) ((uint4 *)smem)[i] = src[i];
         if (tid < 4) ((int *)(smem + IMAGE_BYTES))[tid] = 0;
         __syncthreads();
     }
 #ifdef TVR_DEBUG_SIMD
-    // debug build (tests/test_gpu_faults.py): the token pairs waves w and w + 4, assuming they sit on one SIMD (tvr_shade.hip's check, same slots)
+    // debug build (tests/test_gpu_faults.py): the token groups waves w, w + 4, ... of a workgroup, assuming they sit on one SIMD (tvr_shade.hip's check, same slots:
+    // stats[15] counts the waves that do not share wave w's SIMD, stats[16..23] are the SIMD ids of workgroup 0's first eight waves); kernels without the token report
+    // their placement all the same: NW / 4 waves per SIMD is what their register budget assumes
     {
-        __shared__ int simd_of[S16_WAVES];
+        __shared__ int simd_of[NW];
         const int hw = __builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);
         if (lane == 0) simd_of[wave] = hw;
         __syncthreads();
-        if (a.stats && tid < S16_WAVES / 2 && simd_of[tid] != simd_of[tid + S16_WAVES / 2]) atomicAdd((unsigned long long *)&a.stats[15], 1ull);
-        if (a.stats && blockIdx.x == 0 && tid < S16_WAVES) a.stats[16 + tid] = (unsigned long long)simd_of[tid];
+        if (a.stats && tid >= 4 && tid < NW && simd_of[tid] != simd_of[tid & 3]) atomicAdd((unsigned long long *)&a.stats[15], 1ull);
+        if (a.stats && blockIdx.x == 0 && tid < 8) a.stats[16 + tid] = (unsigned long long)simd_of[tid];
         __syncthreads();
     }
 #endif
@@ -30,11 +35,12 @@
     const long long n_total = (long long)(*a.counter);
     const long long n_tiles = (n_total + S16_TILE - 1) / S16_TILE;
     unsigned long long clk0 = 0ull, ref0 = 0ull;
-    if (a.stats && tid == 0) { clk0 = __builtin_amdgcn_s_memtime(); ref0 = __builtin_amdgcn_s_memrealtime(); }
+    // (VOL: read by every wave, so that the two stamps live in scalar registers across the tile loop: at 168 VGPRs a per-lane copy is a spill)
+    if (a.stats && (VOL || tid == 0)) { clk0 = __builtin_amdgcn_s_memtime(); ref0 = __builtin_amdgcn_s_memrealtime(); }
 #if S16_TIMING
     unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    const long long tile_stride = (long long)gridDim.x * S16_WAVES;
+    const long long tile_stride = (long long)gridDim.x * NW;
     const unsigned lblk = xcd_remap(blockIdx.x, gridDim.x);
     // A-fragment addresses of the basis product (compact image, tvr_device.h)
     const int c11 = c < TVR16_BAS_ROWS1 ? c : TVR16_BAS_ROWS1 - 1;
@@ -55,10 +61,10 @@
     // Only for launches with at least S16_TICKET_MIN tiles per wave: a ticket is a 4-tile quantum, and a call with a handful of tiles per wave (a 4096-ray chunk: 5) is
     // better off with the static stride's one-tile quantum (157 such calls: 32.1 ms with tickets for everyone against 27.2).
     unsigned *const tk = const_cast<unsigned *>(a.counter) + 16;
-    const bool dyn = n_tiles >= (long long)gridDim.x * S16_WAVES * S16_TICKET_MIN;               // (uniform over the grid)
+    const bool dyn = n_tiles >= (long long)gridDim.x * NW * S16_TICKET_MIN;               // (uniform over the grid)
     const int tkn = dyn ? S16_TICKET : 1;
-    const long long tick0 = (long long)gridDim.x * S16_WAVES * S16_TICKET;                     // tiles covered by the static first tickets
-    long long tile_first = ((long long)lblk * S16_WAVES + wave) * tkn;
+    const long long tick0 = (long long)gridDim.x * NW * S16_TICKET;                     // tiles covered by the static first tickets
+    long long tile_first = ((long long)lblk * NW + wave) * tkn;
     unsigned tk_pending = 0;                                                                     // lane 0: the returned value of the ticket atomic in flight
     if (dyn && lane == 0) tk_pending = atomicAdd(tk, (unsigned)S16_TICKET);
     int tk_sub = 0;
@@ -153,7 +159,7 @@
             halves_f(d0, dA[0], dB[0]); halves_f(d1, dA[1], dB[1]); halves_f(d2, dA[2], dB[2]);
             vol_features(fvol, sc, qe, g, FA, FB);
             S16_STAMP(tg1);
-            have_tok = take_matrix_token(mtok, lane);
+            if constexpr (TOKEN) have_tok = take_matrix_token(mtok, lane); else __builtin_amdgcn_s_setprio(S16_PRIO_M);
             S16_STAMP(tgW);
         } else {
             PP pp[3];
@@ -246,7 +252,7 @@
                     rbias = *(const float4 *)((const unsigned char *)sc.refg16 + 10 * TVR16_FRAG + 16 * g);      // head biases of rows 4g .. 4g+3 (zeros in groups 2, 3)
                 }
                 S16_STAMP(tg1);
-                have_tok = take_matrix_token(mtok, lane);
+                if constexpr (TOKEN) have_tok = take_matrix_token(mtok, lane); else __builtin_amdgcn_s_setprio(S16_PRIO_M);
                 S16_STAMP(tgW);
                 f32x4 aF[2][2] = {{f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}}, {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}}};
 #pragma unroll
@@ -331,11 +337,11 @@
             S16_LDS_BASE(W1Lb, smem + TVR16_W1L + lane * 16);
             S16_LDS_BASE(W2Hb, smem + TVR16_W2H + lane * 16);
             S16_LDS_BASE(W2Lb, smem + TVR16_W2L + lane * 16);
-            AF16 ring[S16_RN];
+            AF16 ring[RN];
             Frag bA, bB, nA, nB;
             Frag frA[4], frB[4];
 #pragma unroll
-            for (int q0 = 0; q0 < S16_PD; ++q0) { ring[q0].h = *(const uint4 *)(W1Hb + q0 * TVR16_FRAG); ring[q0].l = *(const uint4 *)(W1Lb + q0 * TVR16_FRAG); }
+            for (int q0 = 0; q0 < PD; ++q0) { ring[q0].h = *(const uint4 *)(W1Hb + q0 * TVR16_FRAG); ring[q0].l = *(const uint4 *)(W1Lb + q0 * TVR16_FRAG); }
             l1_frag(0, FA, SA, CA, bA);
             l1_frag(0, FB, SB_, CB, bB);
             S16_SB;
@@ -344,15 +350,15 @@
 #pragma unroll
                 for (int rb = 0; rb < 8; ++rb) {
                     const int q = 8 * s + rb;
-                    if (q + S16_PD < 40) {
-                        ring[(q + S16_PD) % S16_RN].h = *(const uint4 *)(W1Hb + (q + S16_PD) * TVR16_FRAG);
-                        ring[(q + S16_PD) % S16_RN].l = *(const uint4 *)(W1Lb + (q + S16_PD) * TVR16_FRAG);
+                    if (q + PD < 40) {
+                        ring[(q + PD) % RN].h = *(const uint4 *)(W1Hb + (q + PD) * TVR16_FRAG);
+                        ring[(q + PD) % RN].l = *(const uint4 *)(W1Lb + (q + PD) * TVR16_FRAG);
                     } else {                           // layer 2's first fragments ride in the ring behind layer 1's last
-                        const int q2 = q + S16_PD - 40;                  // (row block 0, k-step q2)
-                        ring[(q + S16_PD) % S16_RN].h = *(const uint4 *)(W2Hb + (q2 * 8) * TVR16_FRAG);
-                        ring[(q + S16_PD) % S16_RN].l = *(const uint4 *)(W2Lb + (q2 * 8) * TVR16_FRAG);
+                        const int q2 = q + PD - 40;                  // (row block 0, k-step q2)
+                        ring[(q + PD) % RN].h = *(const uint4 *)(W2Hb + (q2 * 8) * TVR16_FRAG);
+                        ring[(q + PD) % RN].l = *(const uint4 *)(W2Lb + (q2 * 8) * TVR16_FRAG);
                     }
-                    mfma6(ring[q % S16_RN], bA, bB, acc1[rb][0], acc1[rb][1]);
+                    mfma6(ring[q % RN], bA, bB, acc1[rb][0], acc1[rb][1]);
                 }
                 if (s + 1 < 5) { l1_frag(s + 1, FA, SA, CA, nA); l1_frag(s + 1, FB, SB_, CB, nB); }
                 else { relu_frag(0, 0, frA[0]); relu_frag(0, 1, frB[0]); }              // (acc1[0], acc1[1] are complete after row block 1 of this k-step)
@@ -406,12 +412,12 @@
                     }
 #pragma unroll
                     for (int ks = 0; ks < 4; ++ks) {
-                        const int q = 4 * rb + ks, qn = q + S16_PD;
+                        const int q = 4 * rb + ks, qn = q + PD;
                         if (qn < 32) {
-                            ring[(40 + qn) % S16_RN].h = *(const uint4 *)(W2Hb + (8 * (qn & 3) + (qn >> 2)) * TVR16_FRAG);
-                            ring[(40 + qn) % S16_RN].l = *(const uint4 *)(W2Lb + (8 * (qn & 3) + (qn >> 2)) * TVR16_FRAG);
+                            ring[(40 + qn) % RN].h = *(const uint4 *)(W2Hb + (8 * (qn & 3) + (qn >> 2)) * TVR16_FRAG);
+                            ring[(40 + qn) % RN].l = *(const uint4 *)(W2Lb + (8 * (qn & 3) + (qn >> 2)) * TVR16_FRAG);
                         }
-                        mfma6(ring[(40 + q) % S16_RN], frA[ks], frB[ks], a2A, a2B);
+                        mfma6(ring[(40 + q) % RN], frA[ks], frB[ks], a2A, a2B);
                         if (rb == 0 && ks + 1 < 4) { relu_frag(ks + 1, 0, frA[ks + 1]); relu_frag(ks + 1, 1, frB[ks + 1]); }
                     }
                     if (rb > 0) l3_block(a2pA, a2pB);
@@ -431,9 +437,9 @@
                         S16_SG_DSR(4);                                          // b2, W3's three quads
 #pragma unroll
                         for (int ks = 0; ks < 4; ++ks) {                        // 32 VALU of layer 3 over 24 MFMAs
-                            if (4 * rb + ks + S16_PD < 32) { S16_SG_DSR(1); }
+                            if (4 * rb + ks + PD < 32) { S16_SG_DSR(1); }
                             S16_SG_MFMA(1); S16_SG_VALU(1); S16_SG_MFMA(1); S16_SG_VALU(2);
-                            if (4 * rb + ks + S16_PD < 32) { S16_SG_DSR(1); }
+                            if (4 * rb + ks + PD < 32) { S16_SG_DSR(1); }
                             S16_SG_MFMA(1); S16_SG_VALU(1); S16_SG_MFMA(1); S16_SG_VALU(2);
                             S16_SG_MFMA(1); S16_SG_VALU(1); S16_SG_MFMA(1); S16_SG_VALU(2);
                         }

@@ -18,6 +18,9 @@ are held to rules that can be CHECKED on the instructions that ship, instead of 
       inline asm (`v_fma_mix_f32`, csrc/tvr_mfma.h) — reported as `valu_to_mfma_adjacent` (must be 0).  `valu_to_mfma_lt2` also counts
       the padded cases (one instruction in between; informational).
 
+Beside the rules every kernel's entry carries what the code object's notes say of its resources: `vgprs`, `agprs`, `sgprs`, `scratch_bytes` (per lane),
+`vgpr_spills`, `sgpr_spills` (None for a .s file, which has no notes).
+
 usage: isa_check.py <libtvr.so | file.s> [--kernel SUBSTR] [--json]
 """
 import json
@@ -60,6 +63,39 @@ def disassemble(path):
             txt = subprocess.run([f"{LLVM}/llvm-objdump", "-d", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout
             kernels.update(resolve_branches(split_kernels(txt.split("\n"), asm=False)))
         return kernels
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+RESOURCE_KEYS = {".vgpr_count": "vgprs", ".agpr_count": "agprs", ".sgpr_count": "sgprs", ".private_segment_fixed_size": "scratch_bytes",
+                 ".vgpr_spill_count": "vgpr_spills", ".sgpr_spill_count": "sgpr_spills"}
+
+
+def metadata(path):
+    """-> {kernel name: {note key: value string}} from `llvm-readelf --notes` of every gfx950 code object bundled in the library."""
+    tmp = tempfile.mkdtemp(prefix="isa_meta_")
+    try:
+        so = os.path.join(tmp, os.path.basename(path))
+        shutil.copy(path, so)
+        subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", so], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+        out = {}
+        for f in sorted(os.listdir(tmp)):
+            if "gfx950" not in f:
+                continue
+            txt = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout
+            cur = None
+            for ln in txt.split("\n"):
+                m = re.match(r"  (- |  )(\.\w+):\s*(\S+)\s*$", ln)     # a kernel's own keys: `  - .key:` opens its entry, `    .key:` continues it
+                if not m:
+                    continue
+                if m.group(1) == "- ":
+                    cur = {}
+                if cur is None:
+                    continue
+                cur[m.group(2)] = m.group(3)
+                if m.group(2) == ".name":
+                    out[m.group(3).strip("'\"")] = cur
+        return out
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
@@ -271,6 +307,7 @@ def phase_report(ins_list):
 
 def audit(path, kernel_filter=None):
     ks = disassemble(path)
+    md = {} if path.endswith(".s") else metadata(path)
     report = {}
     for name, ins in ks.items():
         if kernel_filter and kernel_filter not in name:
@@ -286,6 +323,9 @@ def audit(path, kernel_filter=None):
             "examples": {"raw": [x[1] for x in (a["raw_violations"] + b["raw_violations"])[:3]], "war": [f"{x[1]}  ->  {x[2]}" for x in a["war_adjacent"][:3]],
                          "valu_to_mfma": [f"{x[1]}  ->  {x[2]}" for x in a["valu_to_mfma_lt2"][:3]]},
         }
+        for key, out in RESOURCE_KEYS.items():
+            v = md.get(name, {}).get(key)
+            report[name][out] = int(v) if v is not None else None
     return report
 
 
@@ -304,6 +344,8 @@ if __name__ == "__main__":
                 continue
             print(f"{k[:70]:70s} ins {v['instructions']:6d} mfma {v['mfma']:4d} vmem_ld {v['vmem_loads']:4d}  RAW {v['raw_violations_fallthrough']}/{v['raw_violations_execz_taken']}"
                   f"  loads-in-matrix-phase {v['vmem_loads_between_first_and_last_mfma']:3d}  WAR-adjacent {v['war_adjacent']:3d}  valu->mfma<2 {v['valu_to_mfma_lt2']:3d} (adjacent {v['valu_to_mfma_adjacent']})  loops {[(l['mfma'], l['vmem_loads_between_first_and_last_mfma']) for l in v['loops']]}")
+            if v["vgprs"] is not None:
+                print(f"      resources: {v['vgprs']} VGPRs, {v['agprs']} AGPRs, {v['sgprs']} SGPRs, scratch {v['scratch_bytes']} B, spills {v['vgpr_spills']} / {v['sgpr_spills']}")
             for kind, ex in v["examples"].items():
                 for e in ex[:2]:
                     print(f"      {kind}: {e}")

@@ -13,10 +13,7 @@ and is compared like a pair of equal names: `renamed identical` / `renamed diffe
 import hashlib
 import os
 import re
-import shutil
-import subprocess
 import sys
-import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_check  # noqa: E402
@@ -31,32 +28,8 @@ def renumber(ins):
 
 
 def metadata(path):
-    """-> {kernel name: {key: value}} from `llvm-readelf --notes` of every gfx950 code object bundled in the library."""
-    tmp = tempfile.mkdtemp(prefix="isa_diff_")
-    try:
-        so = os.path.join(tmp, os.path.basename(path))
-        shutil.copy(path, so)
-        subprocess.run([f"{isa_check.LLVM}/llvm-objdump", "--offloading", so], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
-        out = {}
-        for f in sorted(os.listdir(tmp)):
-            if "gfx950" not in f:
-                continue
-            txt = subprocess.run([f"{isa_check.LLVM}/llvm-readelf", "--notes", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout
-            cur = None
-            for ln in txt.split("\n"):
-                m = re.match(r"  (- |  )(\.\w+):\s*(\S+)\s*$", ln)     # a kernel's own keys: `  - .key:` opens its entry, `    .key:` continues it
-                if not m:
-                    continue
-                if m.group(1) == "- ":
-                    cur = {}
-                if cur is None:
-                    continue
-                cur[m.group(2)] = m.group(3)
-                if m.group(2) == ".name":
-                    out[m.group(3).strip("'\"")] = cur
-        return {k: {key: v.get(key) for key in META} for k, v in out.items()}
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+    """-> {kernel name: {key: value}} for the keys of META (isa_check.metadata reads the code objects' notes)."""
+    return {k: {key: v.get(key) for key in META} for k, v in isa_check.metadata(path).items()}
 
 
 def load(path):
