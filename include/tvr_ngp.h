@@ -1,5 +1,6 @@
 /* tvr_ngp.h — C-ABI of the alt path (BASELINE configs[4]) in libtvr.so: JNeRF Instant-NGP inference
- * (occupancy-bitfield ray march -> multiresolution hash grid + SH-16 -> density / colour networks -> compositing) on MI355X.
+ * (occupancy-bitfield ray march -> multiresolution hash grid + SH-16 -> density / colour networks -> compositing) on MI355X,
+ * and the occupancy grid built and refreshed from the network (the tvr_ngp_grid_* calls at the end).
  *
  * The reference reaches these steps through Jittor's inline-op API (`jt.code(..., cuda_src=...)`, SURVEY.md §8b "Config-5
  * boundary"); the entry points below are what a binding for that path would call instead.  Conventions are tvr.h's: plain
@@ -118,6 +119,54 @@ int tvr_ngp_render(const tvr_ngp_march_cfg *cfg, const tvr_ngp_grid_cfg *grid_cf
 int tvr_ngp_render_profiled(const tvr_ngp_march_cfg *cfg, const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const void *net_packed, const void *rays_o,
                             const void *rays_d, int64_t n_rays, const void *bitfield, const float background[3], void *rgb, void *stats,
                             void *scratch, size_t scratch_bytes, void *stream, float ms_out[2]);
+
+/* ---- the occupancy grid from the network: DensityGridSampler.update_density_grid / update_density_grid_nerf (density_grid_sampler.py:200-259) ----
+ * G = TVR_NGP_GRIDSIZE, cells = G^3, MIN_CONE_STEPSIZE = 1.73205080757f / 1024; density_grid and density_grid_tmp are [5 * cells] fp32 in Morton order per
+ * cascade, as tvr_ngp_update_bitfield reads them.  ALL arithmetic below is fp32, every operation rounded on its own in the order written (no contraction;
+ * divisions correctly rounded); 2^level is exact.  The pcg32 is pcg32.h's (ngp.Pcg32): next_float = bits((next_uint >> 9) | 0x3f800000) - 1.
+ * xyz(c) = (morton3D_invert(c >> 0), morton3D_invert(c >> 1), morton3D_invert(c >> 2)).  Every call checks its arguments on the host before any launch. */
+
+/* mark_untrained_density_grid (op_header/mark_untrained_density_grid.h): cell i, level = i / cells, pos = ((xyz(i % cells) + 0.5f) / G - 0.5f) * 2^level + 0.5f,
+ * r = 0.5f * 1.73205080757f * 2^level / G.  focal_lengths [n,2]; xforms [n,3,4] row-major in the NGP convention (matrix_nerf2ngp): columns 0..2 are the camera
+ * axes c0, c1, c2, column 3 the origin.  Camera j SEES the cell iff, with p = pos - column 3 and (x, y, z) = ((p0*c[0] + p1*c[1]) + p2*c[2]) for c = c0, c1, c2:
+ * z > 0, |x| - r < z / fx * (0.5f * res_w) and |y| - r < z / fy * (0.5f * res_h).  If (grid[i] < 0) != (no camera sees it): grid[i] = seen ? 0 : -1; other
+ * cells keep their value.  n_images == 0 marks every cell unseen. */
+int tvr_ngp_grid_mark_untrained(void *density_grid, int32_t n_images, const void *focal_lengths, const void *xforms, int32_t res_w, int32_t res_h, void *stream);
+
+/* generate_grid_samples_nerf_nonuniform (op_header/generate_grid_samples_nerf_nonuniform.h) on its own.  Sample i of n (0 <= n < 2^30) copies the generator
+ * (rng_state, rng_inc), advances the copy by 4 * i and draws: level = (uint32)(next_float * n_cascades) % n_cascades; for j = 0..9:
+ * idx = ((i + ema_step * n) * 56924617u + j * 19349663u + 96925573u) % cells + level * cells (uint32 wrap-around), stopping at the first j with
+ * density_grid[idx] > thresh — when none does, THE TENTH INDEX IS KEPT; then with three more floats u (x, y, z in this order):
+ * pos = ((xyz(idx % cells) + u) / G - 0.5f) * 2^level + 0.5f and positions_out[i] = (pos - aabb_lo) / (aabb_hi - aabb_lo), indices_out[i] = idx.
+ * positions_out [n,3] fp32, indices_out [n] uint32.  n_cascades in 1..5. */
+int tvr_ngp_grid_samples(int64_t n, uint32_t ema_step, int32_t n_cascades, float thresh, uint64_t rng_state, uint64_t rng_inc, const float aabb_lo[3],
+                         const float aabb_hi[3], const void *density_grid, void *positions_out, void *indices_out, void *stream);
+
+/* NGPNetworks.density (ngp_network.py:87-90) without the colour half: positions [n, pos_stride floats] in [0,1] -> out [n] = the raw density.  Hash gather and
+ * density_mlp only (a third of tvr_ngp_network's MFMAs, no SH); the SAME gathers and MFMAs in the same order, so out[i] is BIT-EQUAL to column 3 of
+ * tvr_ngp_network on the same positions, in whichever arithmetic the library was built with.  n / n_dev as for tvr_ngp_network; its valid range applies. */
+int tvr_ngp_density(const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const void *net_packed, const void *positions, int32_t pos_stride, int64_t n_max,
+                    const void *n_dev, void *out, void *stream);
+
+/* splat_grid_samples_nerf_max_nearest_neighbor: for i < n, atomicMax on the uint32 view of grid_tmp[indices[i]] with the bits of
+ * __expf(raw[i]) * MIN_CONE_STEPSIZE (v_exp_f32 of raw * log2(e); cascade level 0's step for every cascade, as in the reference; non-negative floats are
+ * ordered like their bits).  Indices >= 5 * cells are ignored.  grid_tmp is NOT zeroed here. */
+int tvr_ngp_grid_splat(const void *indices, const void *raw, int64_t n, void *grid_tmp, void *stream);
+
+/* ema_grid_samples_nerf over all 5 * cells: prev = density_grid[i]; density_grid[i] = prev < 0 ? prev : fmaxf(prev * decay, grid_tmp[i]). */
+int tvr_ngp_grid_ema(const void *grid_tmp, void *density_grid, float decay, void *stream);
+
+/* One update_density_grid_nerf, in one call without a host read: density_grid_tmp (caller's scratch, tmp_bytes >= 5 * cells * 4, else TVR_ERR_SCRATCH) is
+ * zeroed; ONE kernel draws both sample populations in registers — population 0: n_uniform samples with thresh -0.01 from (rng_state, rng_inc); population 1:
+ * n_nonuniform samples with thresh 0.01 from that generator advanced by 2^32 (done here, on the host); each population with its own i and n in the index
+ * hash — runs each sample through the hash gather and density_mlp and splats it; then the ema sweep, then tvr_ngp_update_bitfield.  Neither population reads
+ * what the splat writes, so density_grid, density_grid_tmp, bitfield and mean_out are BIT-EQUAL to tvr_ngp_grid_samples (twice) -> tvr_ngp_density ->
+ * tvr_ngp_grid_splat -> tvr_ngp_grid_ema -> tvr_ngp_update_bitfield.  Nothing is written per sample except the one atomic.  The kernel evaluates the
+ * samples in an order of its own (by the Morton cell of their first candidate, for the gathers' locality): the splat is a maximum, no bit depends on it.
+ * The caller advances its generator afterwards (the reference: by 2^32 after each of the two generate calls). */
+int tvr_ngp_grid_update(const float aabb_lo[3], const float aabb_hi[3], const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const void *net_packed,
+                        void *density_grid, void *density_grid_tmp, size_t tmp_bytes, void *bitfield, void *mean_out, int64_t n_uniform, int64_t n_nonuniform,
+                        uint32_t ema_step, int32_t n_cascades, float decay, uint64_t rng_state, uint64_t rng_inc, void *stream);
 
 #ifdef __cplusplus
 }

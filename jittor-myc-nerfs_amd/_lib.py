@@ -303,6 +303,14 @@ SYMBOLS = {
     "tvr_ngp_render_profiled": (C.c_int, [C.POINTER(NgpMarchCfg), C.POINTER(NgpGridCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.POINTER(C.c_float * 3), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_float * 2)]),
     "tvr_ngp_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float * 3), C.c_void_p, C.c_void_p]),
+    "tvr_ngp_grid_mark_untrained": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "tvr_ngp_grid_samples": (C.c_int, [C.c_int64, C.c_uint32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_ngp_density": (C.c_int, [C.POINTER(NgpGridCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_ngp_grid_splat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "tvr_ngp_grid_ema": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "tvr_ngp_grid_update": (C.c_int, [C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(NgpGridCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
 }
 
 ARITH_MIN_PROBE_SAMPLES = 2048          # include/tvr.h TVR_ARITH_MIN_PROBE_SAMPLES

@@ -5,7 +5,8 @@ Mirrors, under jnerf-myc/python/jnerf/:
   HashEncoder          models/position_encoders/hash_encoder/hash_encoder.py:9-30 (+ grid_encode.py:17-39 level table)
   SHEncoder            models/position_encoders/sh_encoder/sh_encoder.py:9-53
   NGPNetworks          models/networks/ngp_network.py:41-96 (plain-Linear branch, the fp32 configs Car.py / Easyship.py)
-  DensityGridSampler   models/samplers/density_grid_sampler/density_grid_sampler.py:17-162 (inference: sample / rays2rgb / bitfield)
+  DensityGridSampler   models/samplers/density_grid_sampler/density_grid_sampler.py:17-259 (inference: sample / rays2rgb / bitfield; the occupancy grid
+                       from the network: mark_untrained_density_grid / update_density_grid_nerf / update_density_grid, csrc/tvr_ngp_grid.hip)
   render_img           runner/runner.py:195-228 (the 4096-ray slab loop) — and render_frame, the same image in one pass
   NerfRays             dataset/dataset.py:267-292,313-320 (ray generation for one camera in the NGP convention)
 State-dict keys are the reference's (`pos_encoder.m_grid`, `density_mlp.0.weight`, ..., `density_grid`, `density_grid_bitfield`).
@@ -215,14 +216,104 @@ class NGPNetworks(torch.nn.Module):
         p = self._rows(pos_input, self.pos_encoder.m_grid.device)
         return self._run(p, p)[:, 3:4]
 
+    def density_raw(self, pos_input: torch.Tensor) -> torch.Tensor:
+        """[n,3] -> [n]: the raw density through the hash gather and `density_mlp` only (`tvr_ngp_density`: no SH, no colour layers) —
+        bit-equal to `forward(pos, pos)[:, 3]`.  Row-strided views are read in place."""
+        grid = self.pos_encoder.m_grid
+        _need_gpu(grid, "NGPNetworks")
+        p = self._rows(pos_input, grid.device)
+        _need_gpu(p, "NGPNetworks.density_raw")
+        n = p.shape[0]
+        out = torch.empty(n, device=grid.device)
+        if n:
+            L.check(L.lib().tvr_ngp_density(C.byref(self.pos_encoder.cfg), grid.data_ptr(), self.packed().data_ptr(), p.data_ptr(), p.stride(0), n, None,
+                                            out.data_ptr(), _stream(grid.device)), "tvr_ngp_density")
+        return out
+
     def set_fp16(self):
         pass                                                            # fp16 = False in the shipped scene configs
 
 
+# ------------------------------------------------------------------------------------------------------------------ occupancy grid from the network
+N_GRID_CELLS = NERF_CASCADES * NERF_GRIDSIZE ** 3
+NERF_MIN_OPTICAL_THICKNESS = 0.01
+
+
+def _f3(v) -> "C.Array":
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def _box(aabb_range):
+    return _f3([aabb_range[0]] * 3), _f3([aabb_range[1]] * 3)
+
+
+def _grid_tensor(t: torch.Tensor, what: str, dtype=torch.float32, numel: Optional[int] = N_GRID_CELLS) -> torch.Tensor:
+    _need_gpu(t, what)
+    if t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise L.TvrError(f"{what}: expected a contiguous {dtype} tensor" + (f" of {numel} elements" if numel is not None else ""))
+    return t
+
+
+def grid_mark_untrained(density_grid: torch.Tensor, focal_lengths, transforms, resolution: Sequence[int]) -> None:
+    """`tvr_ngp_grid_mark_untrained` in place: cells no camera sees become -1, negative cells a camera sees become 0.  `focal_lengths` [n,2],
+    `transforms` [n,3,4] in the NGP convention (`matrix_nerf2ngp`), `resolution` = (W, H)."""
+    g = _grid_tensor(density_grid, "grid_mark_untrained")
+    f = torch.as_tensor(np.asarray(focal_lengths, np.float32).reshape(-1, 2)).to(g.device).contiguous()
+    x = torch.as_tensor(np.asarray(transforms, np.float32).reshape(-1, 3, 4)).to(g.device).contiguous()
+    if f.shape[0] != x.shape[0]:
+        raise L.TvrError(f"grid_mark_untrained: {f.shape[0]} focal lengths for {x.shape[0]} cameras")
+    L.check(L.lib().tvr_ngp_grid_mark_untrained(g.data_ptr(), x.shape[0], f.data_ptr(), x.data_ptr(), int(resolution[0]), int(resolution[1]), _stream(g.device)),
+            "tvr_ngp_grid_mark_untrained")
+
+
+def grid_samples(density_grid: torch.Tensor, n: int, ema_step: int, n_cascades: int, thresh: float, rng: Pcg32, aabb_range) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`tvr_ngp_grid_samples`: (positions [n,3] warped to the aabb, cell indices [n] as int32 holding the uint32 bits).  `rng` is read, not advanced."""
+    g = _grid_tensor(density_grid, "grid_samples")
+    pos = torch.empty(max(n, 0), 3, device=g.device)
+    idx = torch.empty(max(n, 0), dtype=torch.int32, device=g.device)
+    lo, hi = _box(aabb_range)
+    L.check(L.lib().tvr_ngp_grid_samples(n, ema_step & 0xFFFFFFFF, n_cascades, thresh, rng.state, rng.inc, C.byref(lo), C.byref(hi), g.data_ptr(), pos.data_ptr(),
+                                         idx.data_ptr(), _stream(g.device)), "tvr_ngp_grid_samples")
+    return pos, idx
+
+
+def grid_splat(indices: torch.Tensor, raw: torch.Tensor, grid_tmp: torch.Tensor) -> None:
+    """`tvr_ngp_grid_splat`: grid_tmp[indices[i]] = max(., exp(raw[i]) * MIN_CONE_STEPSIZE) (atomic, on the bits)."""
+    t = _grid_tensor(grid_tmp, "grid_splat")
+    i = _grid_tensor(indices, "grid_splat", torch.int32, None)
+    r = _grid_tensor(raw, "grid_splat", torch.float32, None)
+    if i.numel() != r.numel():
+        raise L.TvrError(f"grid_splat: {i.numel()} indices for {r.numel()} densities")
+    L.check(L.lib().tvr_ngp_grid_splat(i.data_ptr(), r.data_ptr(), i.numel(), t.data_ptr(), _stream(t.device)), "tvr_ngp_grid_splat")
+
+
+def grid_ema(grid_tmp: torch.Tensor, density_grid: torch.Tensor, decay: float) -> None:
+    """`tvr_ngp_grid_ema` in place on `density_grid`."""
+    t, g = _grid_tensor(grid_tmp, "grid_ema"), _grid_tensor(density_grid, "grid_ema")
+    L.check(L.lib().tvr_ngp_grid_ema(t.data_ptr(), g.data_ptr(), decay, _stream(g.device)), "tvr_ngp_grid_ema")
+
+
+def grid_update(model: NGPNetworks, density_grid: torch.Tensor, grid_tmp: torch.Tensor, bitfield: torch.Tensor, mean: torch.Tensor, aabb_range, n_uniform: int,
+                n_nonuniform: int, ema_step: int, n_cascades: int, decay: float, rng: Pcg32) -> None:
+    """`tvr_ngp_grid_update`: one whole `update_density_grid_nerf` (zero tmp, ONE kernel that draws, evaluates and splats both populations, ema, bitfield and
+    mean) without a host read.  `grid_tmp` is scratch of at least 5 * 128^3 floats; `rng` is read, not advanced."""
+    g = _grid_tensor(density_grid, "grid_update")
+    t = _grid_tensor(grid_tmp, "grid_update", torch.float32, None)
+    b = _grid_tensor(bitfield, "grid_update", torch.uint8, N_GRID_CELLS // 8)
+    m = _grid_tensor(mean, "grid_update", torch.float32, None)
+    hashgrid = model.pos_encoder.m_grid
+    _need_gpu(hashgrid, "grid_update")
+    lo, hi = _box(aabb_range)
+    L.check(L.lib().tvr_ngp_grid_update(C.byref(lo), C.byref(hi), C.byref(model.pos_encoder.cfg), hashgrid.data_ptr(), model.packed().data_ptr(), g.data_ptr(),
+                                        t.data_ptr(), L.nbytes(t), b.data_ptr(), m.data_ptr(), n_uniform, n_nonuniform, ema_step & 0xFFFFFFFF, n_cascades, decay,
+                                        rng.state, rng.inc, _stream(g.device)), "tvr_ngp_grid_update")
+
+
 # ------------------------------------------------------------------------------------------------------------------ sampler
 class DensityGridSampler(torch.nn.Module):
-    """Inference half of `DensityGridSampler` (density_grid_sampler.py): `sample` -> `model` -> `rays2rgb(inference=True)`.
-    Buffers keep the reference's names so a converted `ckpt['sampler']` loads with `load_state_dict`."""
+    """`DensityGridSampler` (density_grid_sampler.py) without the training-time ray sampling: `sample` -> `model` -> `rays2rgb(inference=True)`, and the
+    occupancy grid built and refreshed from the network (`update_density_grid`, `build_density_grid`).  Buffers keep the reference's names so a converted
+    `ckpt['sampler']` loads with `load_state_dict`; the update's step counter and scratch are plain attributes, not buffers."""
 
     def __init__(self, model: NGPNetworks, aabb_scale: int = 1, n_rays_per_batch: int = 4096, near_distance: float = 0.2,
                  cone_angle_constant: float = 0.00390625, const_dt: bool = True, background_color: Sequence[float] = (1.0, 1.0, 1.0),
@@ -243,6 +334,12 @@ class DensityGridSampler(torch.nn.Module):
         self.register_buffer("density_grid_mean", torch.zeros(1))
         self._coords = self._rays_numsteps = self._counter = None
         self._scratch: Optional[torch.Tensor] = None
+        self.max_cascade = 0                                            # :59-61
+        while (1 << self.max_cascade) < aabb_scale:
+            self.max_cascade += 1
+        self.density_grid_decay = 0.95                                  # :66
+        self.density_grid_ema_step = 0                                  # a plain int (the reference keeps a one-element Var); not part of the state dict
+        self.density_grid_tmp: Optional[torch.Tensor] = None            # allocated by the first update
 
     # -- maintenance
     def update_bitfield(self) -> None:
@@ -251,6 +348,72 @@ class DensityGridSampler(torch.nn.Module):
         dev = self.density_grid.device
         L.check(L.lib().tvr_ngp_update_bitfield(self.density_grid.data_ptr(), self.density_grid_bitfield.data_ptr(), self.density_grid_mean.data_ptr(),
                                                 None, 0, _stream(dev)), "tvr_ngp_update_bitfield")
+
+    def mark_untrained_density_grid(self, focal_lengths, transforms, resolution: Sequence[int]) -> None:
+        """`mark_untrained_density_grid` (density_grid_sampler.py:208-211): the grid is zeroed (the reference's wrapper starts from zeros), then every cell
+        that no camera sees is set to -1 — such a cell is never sampled, updated or marched.  Arguments as `NerfRays.training_views()` returns them."""
+        self.density_grid.zero_()
+        grid_mark_untrained(self.density_grid, focal_lengths, transforms, resolution)
+
+    def _tmp(self) -> torch.Tensor:
+        dev = self.density_grid.device
+        if self.density_grid_tmp is None or self.density_grid_tmp.device != dev:
+            self.density_grid_tmp = L.dev_empty(N_GRID_CELLS, torch.float32, dev, what="density_grid_tmp")
+        return self.density_grid_tmp
+
+    def update_density_grid_nerf(self, decay: float, n_uniform: int, n_nonuniform: int, fused: bool = True) -> None:
+        """`update_density_grid_nerf` (density_grid_sampler.py:200-247): `n_uniform` samples over every cell that is not marked untrained (thresh -0.01)
+        and `n_nonuniform` over the occupied ones (thresh 0.01) go through the density network; each cell keeps the largest optical thickness
+        exp(raw) * MIN_CONE_STEPSIZE it received, the grid becomes max(grid * decay, that), then bitfield and mean are refreshed.
+        `fused=True` is one `tvr_ngp_grid_update`; `fused=False` runs the stand-alone calls (positions, indices and densities in memory) — the same bits.
+        QUIRK kept from the reference: `decay` is accepted and ignored, the ema uses the fixed `density_grid_decay` = 0.95
+        (`ema_grid_samples_nerf(..., decay=0.95)`, :108-109).  The generator is advanced by 2^32 after each of the two generate calls, also when a
+        count is 0."""
+        _need_gpu(self.density_grid, "DensityGridSampler")
+        n_cascades, step, tmp = self.max_cascade + 1, self.density_grid_ema_step, self._tmp()
+        if fused:
+            grid_update(self.model, self.density_grid, tmp, self.density_grid_bitfield, self.density_grid_mean, self.aabb_range, n_uniform, n_nonuniform, step,
+                        n_cascades, self.density_grid_decay, self.rng)
+            self.rng.advance()
+            self.rng.advance()
+        else:
+            tmp.zero_()
+            pos_u, idx_u = grid_samples(self.density_grid, n_uniform, step, n_cascades, -0.01, self.rng, self.aabb_range)
+            self.rng.advance()
+            pos_n, idx_n = grid_samples(self.density_grid, n_nonuniform, step, n_cascades, NERF_MIN_OPTICAL_THICKNESS, self.rng, self.aabb_range)
+            self.rng.advance()
+            raw = self.model.density_raw(torch.cat([pos_u, pos_n]))
+            grid_splat(torch.cat([idx_u, idx_n]), raw, tmp)
+            grid_ema(tmp, self.density_grid, self.density_grid_decay)
+            self.update_bitfield()
+        self.density_grid_ema_step += 1
+
+    def update_density_grid(self, training_step: int, n_training_steps: int = 40000, fused: bool = True) -> None:
+        """`update_density_grid` (density_grid_sampler.py:252-259): every cell of the cascades in use once below step 256, afterwards a quarter of that
+        uniformly and a quarter among the occupied cells."""
+        n = NERF_GRIDSIZE ** 3 * (self.max_cascade + 1)
+        alpha = self.density_grid_decay ** (n_training_steps / 16)     # computed and passed as in the reference; see update_density_grid_nerf
+        if training_step < 256:
+            self.update_density_grid_nerf(alpha, n, 0, fused=fused)
+        else:
+            self.update_density_grid_nerf(alpha, n // 4, n // 4, fused=fused)
+
+    def build_density_grid(self, n_updates: int = 16, focal_lengths=None, transforms=None, resolution=None) -> float:
+        """Occupancy for a network that came without a sampler state (or whose weights changed): the grid is zeroed — or marked, when cameras are given —
+        the step counter reset, and `n_updates` updates of the early policy run.  Returns the fraction of set bits in cascade 0."""
+        _need_gpu(self.density_grid, "DensityGridSampler")
+        if focal_lengths is not None:
+            self.mark_untrained_density_grid(focal_lengths, transforms, resolution)
+        else:
+            self.density_grid.zero_()
+        self.density_grid_ema_step = 0
+        for _ in range(n_updates):
+            self.update_density_grid(0)
+        if n_updates == 0:
+            self.update_bitfield()
+        bits0 = self.density_grid_bitfield[:NERF_GRIDSIZE ** 3 // 8].to(torch.int32)
+        set_bits = sum(int(((bits0 >> k) & 1).sum()) for k in range(8))
+        return set_bits / NERF_GRIDSIZE ** 3
 
     # -- sampling
     def _cfg(self, slab_rays: int) -> L.NgpMarchCfg:
@@ -287,7 +450,7 @@ class DensityGridSampler(torch.nn.Module):
         """`sample` (density_grid_sampler.py:133-146), inference branch: returns (coords_pos [n,3], coords_dir [n,3]) — views of the
         sampler's [n,7] rows.  Like the reference this reads the sample count back (`.item()`, ray_sampler.py:69)."""
         if is_training:
-            raise NotImplementedError("training-time sampling (density-grid update, compaction) is outside this round's scope")
+            raise NotImplementedError("training-time sampling (jitter, compaction) is not built; the density-grid update is: update_density_grid")
         R = rays_o.shape[0]
         coords, index, numsteps, counter = self._sample_raw(rays_o, rays_d, R * self.MAX_STEP, want_index=True)
         samples = int(counter[1].item())
@@ -509,3 +672,9 @@ class NerfRays:
 
     def rays(self, img_id: int) -> Tuple[torch.Tensor, torch.Tensor]:
         return generate_rays(self.transforms[img_id], self.W, self.H, self.focal, self.principal, device=self.device)
+
+    def training_views(self) -> Tuple[np.ndarray, np.ndarray, Tuple[int, int]]:
+        """(focal_lengths [n,2], transforms [n,3,4] in the NGP convention, (W, H)): the arguments of `DensityGridSampler.mark_untrained_density_grid` /
+        `build_density_grid` (the reference's `dataset.focal_lengths`, `dataset.transforms_gpu`, `dataset.resolution`)."""
+        focal = np.tile(np.asarray(self.focal, np.float32), (self.n_images, 1))
+        return focal, np.stack(self.transforms).astype(np.float32).reshape(self.n_images, 3, 4), (self.W, self.H)
