@@ -168,6 +168,42 @@ int tvr_ngp_grid_update(const float aabb_lo[3], const float aabb_hi[3], const tv
                         void *density_grid, void *density_grid_tmp, size_t tmp_bytes, void *bitfield, void *mean_out, int64_t n_uniform, int64_t n_nonuniform,
                         uint32_t ema_step, int32_t n_cascades, float decay, uint64_t rng_state, uint64_t rng_inc, void *stream);
 
+/* ---- training the field: Runner.train (runner/runner.py:62-86) at row level ----
+ * The sampler is the same call in training and inference (density_grid_sampler.py:138-140): tvr_ngp_sample supplies the rows.  The reference's compaction
+ * (op_header/compacted_coord.h; its `T < EPSILON` break is commented out, :40-43) keeps every step of every ray until the row capacity is reached; with bases
+ * handed out as the prefix sum in ray order that is the slice coords[0 : min(total, n_rows)] and, per ray, nc = min(n_rows - min(n_rows, base), n) rows.  The
+ * reference's arrival-order atomics give another layout with the same per-ray content.  The five Linears train through tvr_linear_dx and tvr_gemm_tn (tvr.h). */
+
+/* CalcRgb.execute, forward (calc_rgb.py:35-78; compute_rgbs_fp32 ships only as an object file, so the loop is modelled on compute_rgbs_inference as
+ * oracle/ngp_oracle.c restates it, and on the comment at calc_rgb.h:2-4).  net_out [n_rows,4], coords [n_rows,7], numsteps [n_rays,2] = (n, base),
+ * bg [n_rays,3] DEVICE, rgb_out [n_rays,3].  Ray i, T = 1, for j = 0 .. nc-1: stop if T < 1e-4; row base + j: c = logistic(out[0:3]), sigma = exp(out[3]),
+ * dt = column 3 unwarped, alpha = 1 - exp(-sigma dt); rgb += alpha * T * c; T *= 1 - alpha.  Afterwards, if the loop walked all n UNCOMPACTED steps
+ * (j == n: no break, not cut by the capacity), rgb += T * bg[i].  A ray with n == 0 receives bg[i]; a ray with n > 0 and nc == 0 receives 0.
+ * The per-sample arithmetic is tvr_ngp_composite's own: with one background for all rays and n_rows >= the total, rgb_out is BIT-EQUAL to it.
+ * PARITY-UNPINNED: the reference also passes density_grid_mean into that binary, whose source is absent; no regularisation term is added here and the mean is
+ * not consumed. */
+int tvr_ngp_composite_train(const void *net_out, const void *coords, const void *numsteps, int64_t n_rays, int64_t n_rows, const void *bg, void *rgb_out,
+                            void *stream);
+
+/* The derivative of tvr_ngp_composite_train with the set of composited samples held fixed (the stop index is not differentiated).  rgb_out is the forward's
+ * output, grad_rgb [n_rays,3], grad_net_out [n_rows,4].  With g = grad_rgb[i], T_j the transmittance in front of sample j and
+ * suffix_j = rgb_out[i] - sum_{k<=j} alpha_k T_k c_k (everything behind j, the background term included where it was added):
+ *   d / d out[0:3] = g * alpha_j T_j * c (1 - c)          d / d out[3] = sigma_j dt_j * dot(g, T_j (1 - alpha_j) c_j - suffix_j).
+ * suffix_j is summed from the last composited sample backwards (the subtraction above cancels where little is left behind j while sigma_j dt_j is large), so
+ * rgb_out is kept in the signature only: it is not read and may be NULL.  EVERY row of grad_net_out[0:n_rows] is written: rows behind a break, behind the capacity cut, and rows no ray owns are exactly 0 (the buffer is zeroed on
+ * the stream first).  One owner per row, no atomics: the same bytes on every run.  PARITY-UNPINNED like the forward (no density_grid_mean term). */
+int tvr_ngp_composite_backward(const void *net_out, const void *coords, const void *numsteps, int64_t n_rays, int64_t n_rows, const void *bg, const void *rgb_out,
+                               const void *grad_rgb, void *grad_net_out, void *stream);
+
+/* kernel_grid_backward (HashEncode.h:300-396): for sample i, level l, corner k, feature f: grad_grid[2 * (offsets[l] + e) + f] += w * grad_enc[i, 2l + f], with
+ * e and w EXACTLY the forward's (the same fma, floor, dense wrap and clamp as tvr_ngp_hash_encode; w formed in the forward's factor order, then one product).
+ * grad_enc [n,32]; grad_grid [2 * offsets[16]] is ACCUMULATED into — the caller zeroes it.  positions [n, pos_stride floats] are read in place (the sampler's
+ * rows: stride 7); there is no gradient with respect to them (the reference detaches them).  The adds are float atomics (one global_atomic_add_f32 each, and
+ * LDS float atomics in front of them for the levels small enough to be pre-summed per workgroup): the result depends on arrival order in its last bits, so two
+ * runs need not be byte-identical.  Per entry: |got - exact| <= (count + 8) * 2^-23 * sum |w g| over that entry's `count` contributions. */
+int tvr_ngp_hash_encode_backward(const tvr_ngp_grid_cfg *grid_cfg, const void *positions, int32_t pos_stride, int64_t n, const void *grad_enc, void *grad_grid,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

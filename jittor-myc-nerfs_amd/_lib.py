@@ -311,6 +311,9 @@ SYMBOLS = {
     "tvr_ngp_grid_ema": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "tvr_ngp_grid_update": (C.c_int, [C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(NgpGridCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "tvr_ngp_composite_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_ngp_composite_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_ngp_hash_encode_backward": (C.c_int, [C.POINTER(NgpGridCfg), C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 ARITH_MIN_PROBE_SAMPLES = 2048          # include/tvr.h TVR_ARITH_MIN_PROBE_SAMPLES

@@ -14,6 +14,7 @@
 //
 // Compiled with -ffp-contract=off; FMAs are explicit where the reference's compiler contracts (see oracle/ngp_oracle.c header).
 #include "tvr_ngp_field.h"
+#include "tvr_ngp_composite.h"
 
 
 // ------------------------------------------------------------------------------------------------ march helpers
@@ -25,7 +26,6 @@ struct MarchCfg {
     uint32_t slab_rays;
 };
 
-__device__ __forceinline__ float min_cone_step() { return 1.73205080757f / 1024.0f; }
 __device__ __forceinline__ float max_cone_step() { return min_cone_step() * 16.0f * 1024.0f / 128.0f; }
 __device__ __forceinline__ float calc_dt(const MarchCfg &c, float t)
 {
@@ -521,18 +521,16 @@ __global__ void __launch_bounds__(256) ngp_composite_kernel(const float4 *__rest
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rays) return;
     const uint32_t n = (uint32_t)numsteps[2 * i], base = (uint32_t)numsteps[2 * i + 1];
-    const float max_step = min_cone_step() * 16.0f;
     float T = 1.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
     uint32_t j = 0;
     for (; j < n; ++j) {
         if (T < 1e-4f) break;
         const float4 o = net_out[(size_t)base + j];
-        const float dt = coords[7 * ((size_t)base + j) + 3] * (max_step - min_cone_step()) + min_cone_step();
-        const float alpha = 1.f - __expf(-__expf(o.w) * dt);
+        const float alpha = ngp_alpha(o.w, ngp_row_dt(coords[7 * ((size_t)base + j) + 3]));
         const float w = alpha * T;
-        c0 += w * (1.0f / (1.0f + __expf(-o.x)));
-        c1 += w * (1.0f / (1.0f + __expf(-o.y)));
-        c2 += w * (1.0f / (1.0f + __expf(-o.z)));
+        c0 += w * ngp_logistic(o.x);
+        c1 += w * ngp_logistic(o.y);
+        c2 += w * ngp_logistic(o.z);
         T *= (1.f - alpha);
     }
     if (j == n) {

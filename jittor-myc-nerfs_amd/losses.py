@@ -7,6 +7,14 @@ import ctypes as C
 import torch
 
 
+def huber_loss(x, target, delta=0.1):
+    """`HuberLoss.execute` (jnerf-myc/python/jnerf/models/losses/huber_loss.py): ELEMENTWISE, with rel = |x - target|:
+    rel - delta / 2 where rel > delta, else rel^2 / (2 delta).  The Instant-NGP trainer backpropagates its sum."""
+    rel = torch.abs(x - target)
+    sqr = 0.5 / delta * rel * rel
+    return torch.where(rel > delta, rel - 0.5 * delta, sqr)
+
+
 def _ptr_array(ts):
     return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 

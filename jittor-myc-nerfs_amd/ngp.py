@@ -5,8 +5,9 @@ Mirrors, under jnerf-myc/python/jnerf/:
   HashEncoder          models/position_encoders/hash_encoder/hash_encoder.py:9-30 (+ grid_encode.py:17-39 level table)
   SHEncoder            models/position_encoders/sh_encoder/sh_encoder.py:9-53
   NGPNetworks          models/networks/ngp_network.py:41-96 (plain-Linear branch, the fp32 configs Car.py / Easyship.py)
-  DensityGridSampler   models/samplers/density_grid_sampler/density_grid_sampler.py:17-259 (inference: sample / rays2rgb / bitfield; the occupancy grid
-                       from the network: mark_untrained_density_grid / update_density_grid_nerf / update_density_grid, csrc/tvr_ngp_grid.hip)
+  DensityGridSampler   models/samplers/density_grid_sampler/density_grid_sampler.py:17-267 (inference: sample / rays2rgb / bitfield; the occupancy grid
+                       from the network: mark_untrained_density_grid / update_density_grid_nerf / update_density_grid, csrc/tvr_ngp_grid.hip; training, opt-in:
+                       sample(is_training=True) / rays2rgb(inference=False) / update_batch_rays, csrc/tvr_ngp_train.hip — the trainer is ngp_train.py)
   render_img           runner/runner.py:195-228 (the 4096-ray slab loop) — and render_frame, the same image in one pass
   NerfRays             dataset/dataset.py:267-292,313-320 (ray generation for one camera in the NGP convention)
 State-dict keys are the reference's (`pos_encoder.m_grid`, `density_mlp.0.weight`, ..., `density_grid`, `density_grid_bitfield`).
@@ -167,6 +168,7 @@ class NGPNetworks(torch.nn.Module):
         self.rgb_mlp = torch.nn.Sequential(Lin(32, 64, bias=False), torch.nn.ReLU(), Lin(64, 64, bias=False), torch.nn.ReLU(), Lin(64, 3, bias=False))
         self._packed: Optional[torch.Tensor] = None
         self._sig = None
+        self.hip_training = False                                       # opt-in: forward() under grad mode builds the training graph (forward_train)
 
     def _weights(self):
         return [self.density_mlp[0].weight, self.density_mlp[2].weight, self.rgb_mlp[0].weight, self.rgb_mlp[2].weight, self.rgb_mlp[4].weight]
@@ -207,7 +209,17 @@ class NGPNetworks(torch.nn.Module):
         """[n,3] positions in [0,1] and directions warped to [0,1] -> [n,4] = (rgb raw, density raw) (`execute_`, ngp_network.py:78-85).
         Row-strided views (the sampler's `coords[:, :3]`, `coords[:, 4:]`) are read in place."""
         dev = self.pos_encoder.m_grid.device
+        if self.hip_training and torch.is_grad_enabled():
+            return self.forward_train(pos_input, dir_input)
         return self._run(self._rows(pos_input, dev), self._rows(dir_input, dev))
+
+    def forward_train(self, pos_input: torch.Tensor, dir_input: torch.Tensor) -> torch.Tensor:
+        """`execute_` under autograd, at row level: `tvr_ngp_hash_encode` (backward: `tvr_ngp_hash_encode_backward` into a zeroed buffer, the gradient of
+        `m_grid`), the five bias-free Linears through `autograd_ops._LinearFn` (fp32-input MFMAs forward and dX, `tvr_gemm_tn` for the weight gradients), SH
+        without a gradient.  Positions and directions are detached, as in the reference.  Returns [n,4] = (rgb raw, density raw)."""
+        from .ngp_train import network_train
+        dev = self.pos_encoder.m_grid.device
+        return network_train(self, self._rows(pos_input, dev), self._rows(dir_input, dev))
 
     execute = forward
 
@@ -311,13 +323,14 @@ def grid_update(model: NGPNetworks, density_grid: torch.Tensor, grid_tmp: torch.
 
 # ------------------------------------------------------------------------------------------------------------------ sampler
 class DensityGridSampler(torch.nn.Module):
-    """`DensityGridSampler` (density_grid_sampler.py) without the training-time ray sampling: `sample` -> `model` -> `rays2rgb(inference=True)`, and the
-    occupancy grid built and refreshed from the network (`update_density_grid`, `build_density_grid`).  Buffers keep the reference's names so a converted
+    """`DensityGridSampler` (density_grid_sampler.py): `sample` -> `model` -> `rays2rgb(inference=True)`, the occupancy grid built and refreshed from the
+    network (`update_density_grid`, `build_density_grid`), and — opt-in, for `ngp_train.NGPTrainer` — the training branch of `sample` with its row capacity
+    `target_batch_size` and `rays2rgb(out, background)` under autograd.  Buffers keep the reference's names so a converted
     `ckpt['sampler']` loads with `load_state_dict`; the update's step counter and scratch are plain attributes, not buffers."""
 
     def __init__(self, model: NGPNetworks, aabb_scale: int = 1, n_rays_per_batch: int = 4096, near_distance: float = 0.2,
                  cone_angle_constant: float = 0.00390625, const_dt: bool = True, background_color: Sequence[float] = (1.0, 1.0, 1.0),
-                 rng: Optional[Pcg32] = None):
+                 rng: Optional[Pcg32] = None, target_batch_size: int = 1 << 18):
         super().__init__()
         if aabb_scale > (1 << (NERF_CASCADES - 1)):
             raise ValueError(f"NeRF dataset's aabb_scale must <= {1 << (NERF_CASCADES - 1)}, but now is {aabb_scale}")     # :55-58
@@ -340,6 +353,13 @@ class DensityGridSampler(torch.nn.Module):
         self.density_grid_decay = 0.95                                  # :66
         self.density_grid_ema_step = 0                                  # a plain int (the reference keeps a one-element Var); not part of the state dict
         self.density_grid_tmp: Optional[torch.Tensor] = None            # allocated by the first update
+        # training-time sampling (:76-78, :131): the row capacity, the step the trainer sets, and the rows seen since the last update_batch_rays
+        self.target_batch_size = int(target_batch_size)
+        self.max_train_samples = n_rays_per_batch * MAX_STEP            # the training branch's row buffer, fixed like the reference's (ray_sampler.py:15)
+        self.update_den_freq = 16
+        self.training_step = 0
+        self.measured_batch_size = 0
+        self._rays_numsteps_compacted = None
 
     # -- maintenance
     def update_bitfield(self) -> None:
@@ -447,22 +467,64 @@ class DensityGridSampler(torch.nn.Module):
         return coords, index, numsteps, counter
 
     def sample(self, img_ids, rays_o: torch.Tensor, rays_d: torch.Tensor, rgb_target=None, is_training: bool = False):
-        """`sample` (density_grid_sampler.py:133-146), inference branch: returns (coords_pos [n,3], coords_dir [n,3]) — views of the
-        sampler's [n,7] rows.  Like the reference this reads the sample count back (`.item()`, ray_sampler.py:69)."""
-        if is_training:
-            raise NotImplementedError("training-time sampling (jitter, compaction) is not built; the density-grid update is: update_density_grid")
+        """`sample` (density_grid_sampler.py:133-164): returns (coords_pos [n,3], coords_dir [n,3]) — views of the sampler's [n,7] rows.  Like the
+        reference this reads the sample count back (`.item()`, ray_sampler.py:69).
+        `is_training=True` is the training branch: the SAME sampling call (there is no training-time jitter of its own, :138-140), then the compaction to
+        the row capacity `target_batch_size`.  The reference's `compacted_coord` keeps every step of every ray until the capacity is reached (its
+        `T < EPSILON` break is commented out, op_header/compacted_coord.h:40-43), so the network forward it runs first (:154) feeds a loop whose result is
+        unused: that forward is NOT run here.  Bases are the prefix sum in ray order, so a ray's compacted base is its sampled base and the compaction is
+        the slice `coords[:min(total, cap)]` plus `steps_c = min(cap - min(cap, base), steps)` (`_rays_numsteps_compacted`); the reference's arrival-order
+        atomics give another layout with the same per-ray content.  Only the used rows are returned (the reference returns all `cap` rows, zero-padded).
+        Around it, as in the reference: `update_density_grid(step)` when `training_step % update_den_freq == 0`, `update_batch_rays()` when it is
+        `update_den_freq - 1`; `measured_batch_size` grows by the uncapped total.
+        Opt-in like the rest of training: the branch (and `rays2rgb(inference=False)`) needs `model.hip_training` set (`NGPTrainer` does it); without it the call raises, as before."""
+        if is_training and not self.model.hip_training:
+            raise NotImplementedError("training-time sampling is opt-in: set model.hip_training = True (ngp_train.NGPTrainer does) before sample(is_training=True)")
+        if is_training and self.training_step % self.update_den_freq == 0:
+            self.update_density_grid(self.training_step)
         R = rays_o.shape[0]
-        coords, index, numsteps, counter = self._sample_raw(rays_o, rays_d, R * self.MAX_STEP, want_index=True)
+        # training: `update_batch_rays` may raise the ray count up to the row capacity, so the buffer keeps the size the reference fixes at construction
+        # (n_rays_per_batch * MAX_STEP rows); a ray whose steps would cross it gets (0, base), as in the reference
+        max_samples = min(R * self.MAX_STEP, self.max_train_samples) if is_training else R * self.MAX_STEP
+        coords, index, numsteps, counter = self._sample_raw(rays_o, rays_d, max_samples, want_index=True)
         samples = int(counter[1].item())
-        coords = coords[:samples]
+        if is_training:
+            cap = self.target_batch_size
+            self.measured_batch_size += samples
+            coords = coords[:min(samples, cap)]
+            n, base = numsteps[:, 0], numsteps[:, 1]
+            steps_c = torch.minimum(cap - torch.clamp(base, max=cap), n)
+            self._rays_numsteps_compacted = torch.stack([steps_c, base], 1).contiguous()
+            if self.training_step % self.update_den_freq == self.update_den_freq - 1:
+                self.update_batch_rays()
+        else:
+            coords = coords[:samples]
         self._coords, self._rays_numsteps, self._counter, self._rays_index = coords, numsteps, counter, index
         return coords[:, :3], coords[:, 4:]
 
+    @staticmethod
+    def batch_rays(n_rays_per_batch: int, target_batch_size: int, measured_batch_size: int, update_den_freq: int = 16) -> int:
+        """`update_batch_rays` (density_grid_sampler.py:262-267), the same arithmetic: rays per batch so that a batch fills the row capacity."""
+        measured = max(measured_batch_size / update_den_freq, 1)
+        rays_per_batch = int(n_rays_per_batch * target_batch_size / measured)
+        return int(min((int(rays_per_batch) + 127) // 128 * 128, target_batch_size))
+
+    def update_batch_rays(self) -> None:
+        self.n_rays_per_batch = self.batch_rays(self.n_rays_per_batch, self.target_batch_size, self.measured_batch_size, 16)   # the reference divides by 16
+        self.measured_batch_size = 0
+
     def rays2rgb(self, network_outputs: torch.Tensor, training_background_color=None, inference: bool = False) -> torch.Tensor:
-        """`rays2rgb` (density_grid_sampler.py:163-190) -> `CalcRgb.inference` (calc_rgb.py:118-150)."""
-        if not inference:
-            raise NotImplementedError("only inference=True (CalcRgb.inference) is built")
+        """`rays2rgb` (density_grid_sampler.py:163-190).  `inference=True`: `CalcRgb.inference` (calc_rgb.py:118-150).  `inference=False`: `CalcRgb.execute`
+        (:35-78) under autograd over `tvr_ngp_composite_train` / `tvr_ngp_composite_backward`, on the rows of the last `sample(is_training=True)`;
+        `training_background_color` is [n_rays,3]."""
         assert network_outputs.shape[0] == self._coords.shape[0]
+        if not inference:
+            if not self.model.hip_training:
+                raise NotImplementedError("the training compositor is opt-in: set model.hip_training = True (ngp_train.NGPTrainer does)")
+            from .ngp_train import composite_train
+            if training_background_color is None:
+                training_background_color = torch.tensor(self.background_color, device=self._coords.device).expand(self._rays_numsteps.shape[0], 3)
+            return composite_train(network_outputs, self._coords, self._rays_numsteps, training_background_color)
         return self._composite(network_outputs, self._coords, self._rays_numsteps,
                                self.background_color if training_background_color is None else training_background_color)
 
