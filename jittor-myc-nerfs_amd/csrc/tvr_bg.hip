@@ -17,12 +17,6 @@
 #include "tvr_kernels.h"
 #include "tvr_mfma.h"
 
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return tvr_set_error(TVR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 #define BG_MAX_BLOCKS 77                      // fragment blocks (2 KiB each) per stage image
 #define BG_BIAS_FLOATS 640                    // 4 x 128 base biases, 64 rgb-hidden, sigma, 3 rgb (padded)
 #define BG_WAVES 8

@@ -8,6 +8,13 @@ struct SceneDev;
 // records the text tvr_last_error() returns (thread-local) and hands `code` back; defined in tvr_api.hip
 int tvr_set_error(int code, const char *fmt, ...);
 
+// a HIP call inside a function that returns a status: its failure becomes TVR_ERR_HIP with the call's text and HIP's message
+#define HIP_TRY(expr)                                                                                    \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) return tvr_set_error(TVR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
 // Outputs of the march kernel / inputs of shade + composite.  The "queue" holds one entry per appearance sample
 // (weight > thres); each ray's entries are contiguous and in sample order.
 struct MarchOut {

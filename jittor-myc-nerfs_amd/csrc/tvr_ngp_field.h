@@ -12,12 +12,6 @@
 #define NGP_G TVR_NGP_GRIDSIZE
 #define NGP_CELLS (NGP_G * NGP_G * NGP_G)
 
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return tvr_set_error(TVR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------------ PCG32 (pcg32.h)
 struct Pcg {
     uint64_t state, inc;
