@@ -204,6 +204,46 @@ int tvr_ngp_composite_backward(const void *net_out, const void *coords, const vo
 int tvr_ngp_hash_encode_backward(const tvr_ngp_grid_cfg *grid_cfg, const void *positions, int32_t pos_stride, int64_t n, const void *grad_enc, void *grad_grid,
                                  void *stream);
 
+/* ---- geometry: the density's spatial gradient, and the density on a lattice (csrc/tvr_ngp_geom.hip) ----
+ *
+ * tvr_ngp_density_gradient: positions [n, pos_stride floats] in [0,1] -> raw_out [n] (may be NULL) and grad_out [n,3] = d raw / d position, the position being the
+ * unit-cube position the kernels take.  n / n_dev / row stride as for tvr_ngp_density; rows from n on are left as they were; every check on the host before any launch.
+ * raw_out is BIT-EQUAL to tvr_ngp_density (the same gathers, fma chains and MFMAs in the same order; the tangent work sits between them).
+ * DEFINITION.  Level l, with encode_level's own x = fmaf(p, scale_l, 0.5), cell floor(x) and fp32 fractions f = x - floor(x), corner values v (feature c = 0, 1):
+ *   d enc[2l+c] / d p_k = scale_l * sum over the 8 corners of (d w / d f_k) * v_c,   d w / d f_k = the corner's weight with its factor k replaced by +1 (far corner
+ *   along k) or -1 (near corner) — the dy_dx block of kernel_grid (HashEncode.h:206-249), which the reference carries and never calls.
+ *   h = W0 enc (density_mlp.0), raw = W1[0,:] relu(h) (density_mlp.2);  grad raw = sum_k (W0^T (W1[0,:] * [h > 0]))_k * d enc_k / d p.
+ * The gradient is piecewise: inside one cell of every level and one ReLU pattern it is a constant times a bilinear function of the fractions, and THAT is the
+ * definition — no smoothing across cells, no finite difference.  [h > 0] is decided by an fp32-class evaluation of h (error about 2^-22 of sum_k |W0_jk| |enc_k|): at
+ * a point where some |h_j| is within that of 0 an exact evaluation may pick the other branch.
+ * EVALUATION (forward mode).  The corner sum is taken edge by edge, (product of the two other factors) * (far value - near value) over the four edges along k; the
+ * three tangent encodings go through density_mlp.0 as three more operand columns against the same packed weight image (four times tvr_ngp_density's layer-0 products,
+ * no memory traffic beyond its own), are masked by [h > 0], and row 0 of density_mlp.2 is applied in fp32 (read from the packed fp32 image).  In the default build the
+ * mask's h is evaluated separately from the value's: the value path resolves hash features below 2^-14 to multiples of 2^-24 only (its fp16 halves), which leaves a
+ * hidden unit of a small encoding at exactly 0; for the mask the encoding column is divided by a power of two of its own first, through the same weights.
+ * RANGE.  scale_l reaches 2048 * aabb_scale - 1 (32 767 at aabb_scale 16) and multiplies differences of the table's values, so a tangent can pass the 65504 up to which
+ * the default build's fp16 hi/lo split is exact.  Each tangent column (one sample, one axis) is therefore divided by a power of two of its own — chosen from its largest
+ * magnitude so that this lies in [2^14, 2^15) — before the split (both halves rounded to nearest, which that range allows), and the hidden tangents are multiplied back
+ * afterwards.  Powers of two are exact and the layer is linear in the column, so nothing is assumed about scale_l, the table's values or the weights beyond
+ * tvr_ngp_network's own valid range for the VALUE path. */
+int tvr_ngp_density_gradient(const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const void *net_packed, const void *positions, int32_t pos_stride, int64_t n_max,
+                             const void *n_dev, void *raw_out, void *grad_out, void *stream);
+
+/* tvr_ngp_density_grid: the RAW density on a lattice.  volume_out [dims[0], dims[1], dims[2]] fp32, the last axis fastest (as tvr_mesh_count / tvr_mesh_emit read a
+ * volume).  Lattice point (i, j, k) is the unit-cube position p = (fmaf(i, spacing[0], origin[0]), fmaf(j, spacing[1], origin[1]), fmaf(k, spacing[2], origin[2])),
+ * formed in the kernel: no point tensor exists.  The level set sigma = s of the density is raw = log s.
+ *   - a point with a coordinate outside [0, 1] receives empty_value;
+ *   - with bitfield != NULL (TVR_NGP_BITFIELD_BYTES, as tvr_ngp_update_bitfield writes it): x = p * (aabb_hi - aabb_lo) + aabb_lo (fp32: one subtraction on the host,
+ *     then a product and a sum, each rounded), mip = min(4, max(0, frexp exponent of max_k |x_k - 0.5|, + 1)), cell c_k = clamp((int)(((x_k - 0.5) * 2^-mip + 0.5)
+ *     * 128), 0, 127) — the march's lookup (cascaded_grid_idx_at) — and a point whose bit morton(c) of cascade mip is clear receives empty_value WITHOUT being
+ *     evaluated; aabb_lo / aabb_hi are read only in this case;
+ *   - every other point holds exactly what tvr_ngp_density returns for p (the same tile code: bit-equal).
+ * Work is handed out in bricks of 2 x 4 x 4 lattice points (one 32-sample tile), neighbouring bricks to neighbouring waves; a brick without a point to evaluate
+ * does no gather and no MFMA.  dims: each > 0 (else TVR_ERR_INVALID) and the product at most 2^31 (else TVR_ERR_UNSUPPORTED).  No atomics: the same bytes on every run. */
+int tvr_ngp_density_grid(const tvr_ngp_grid_cfg *grid_cfg, const void *grid, const void *net_packed, const void *bitfield, const float aabb_lo[3],
+                         const float aabb_hi[3], const int32_t dims[3], const float origin[3], const float spacing[3], float empty_value, void *volume_out,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -314,6 +314,10 @@ SYMBOLS = {
     "tvr_ngp_composite_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tvr_ngp_composite_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tvr_ngp_hash_encode_backward": (C.c_int, [C.POINTER(NgpGridCfg), C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvr_ngp_density_gradient": (C.c_int, [C.POINTER(NgpGridCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "tvr_ngp_density_grid": (C.c_int, [C.POINTER(NgpGridCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3),
+                                       C.POINTER(C.c_int32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 ARITH_MIN_PROBE_SAMPLES = 2048          # include/tvr.h TVR_ARITH_MIN_PROBE_SAMPLES

@@ -33,32 +33,12 @@ __device__ __forceinline__ float calc_dt(const MarchCfg &c, float t)
     const float v = t * c.cone_angle;
     return v < min_cone_step() ? min_cone_step() : (max_cone_step() < v ? max_cone_step() : v);
 }
-__device__ __forceinline__ int frexp_exponent(float v)
-{
-    int e;
-    (void)frexpf(v, &e);
-    return e;
-}
-__device__ __forceinline__ int mip_from_pos(float x, float y, float z)
-{
-    const float m = fmaxf(fmaxf(fabsf(x - 0.5f), fabsf(y - 0.5f)), fabsf(z - 0.5f));
-    return min(TVR_NGP_CASCADES - 1, max(0, frexp_exponent(m) + 1));
-}
 __device__ __forceinline__ int mip_from_dt(float dt, float x, float y, float z)
 {
     const int mip = mip_from_pos(x, y, z);
     dt *= (float)(2 * NGP_G);
     if (dt < 1.f) return mip;
     return min(TVR_NGP_CASCADES - 1, max(frexp_exponent(dt), mip));
-}
-__device__ __forceinline__ bool occupied_at(float x, float y, float z, const uint8_t *__restrict__ bits, uint32_t mip)
-{
-    const float s = ldexpf(1.0f, -(int)mip);
-    const int ix = (int)(((x - 0.5f) * s + 0.5f) * (float)NGP_G);
-    const int iy = (int)(((y - 0.5f) * s + 0.5f) * (float)NGP_G);
-    const int iz = (int)(((z - 0.5f) * s + 0.5f) * (float)NGP_G);
-    const uint32_t idx = morton3d((uint32_t)min(max(ix, 0), NGP_G - 1), (uint32_t)min(max(iy, 0), NGP_G - 1), (uint32_t)min(max(iz, 0), NGP_G - 1));
-    return bits[idx / 8 + (uint32_t)NGP_CELLS / 8 * mip] & (1u << (idx % 8));
 }
 __device__ __forceinline__ float dist_axis(float pos, float dir, float idir, float res)
 {

@@ -242,6 +242,28 @@ class NGPNetworks(torch.nn.Module):
                                             out.data_ptr(), _stream(grid.device)), "tvr_ngp_density")
         return out
 
+    def density_gradient(self, pos_input: torch.Tensor, n_dev: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """[n,3] -> (raw [n], grad [n,3]): the raw density (bit-equal to `density_raw`) and its analytic gradient with respect to the unit-cube position the
+        kernels take (`tvr_ngp_density_gradient`, include/tvr_ngp.h: per hash cell a constant times a bilinear function — no smoothing, no finite difference).
+        Row-strided views are read in place.  `n_dev` (uint32 [1] on the device) cuts the rows; rows behind it are left as allocated."""
+        grid = self.pos_encoder.m_grid
+        _need_gpu(grid, "NGPNetworks")
+        p = self._rows(pos_input, grid.device)
+        _need_gpu(p, "NGPNetworks.density_gradient")
+        n = p.shape[0]
+        raw, grad = torch.empty(n, device=grid.device), torch.empty(n, 3, device=grid.device)
+        if n:
+            L.check(L.lib().tvr_ngp_density_gradient(C.byref(self.pos_encoder.cfg), grid.data_ptr(), self.packed().data_ptr(), p.data_ptr(), p.stride(0), n,
+                                                     None if n_dev is None else n_dev.data_ptr(), raw.data_ptr(), grad.data_ptr(), _stream(grid.device)),
+                    "tvr_ngp_density_gradient")
+        return raw, grad
+
+    def surface_normals(self, pos_input: torch.Tensor) -> torch.Tensor:
+        """[n,3] -> [n,3]: -grad raw / |grad raw| (out of the dense side), in the axes of the positions; exactly zero where the gradient is zero."""
+        _, g = self.density_gradient(pos_input)
+        norm = torch.sqrt((g * g).sum(-1, keepdim=True))
+        return torch.where(norm > 0, -g / norm.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(g))
+
     def set_fp16(self):
         pass                                                            # fp16 = False in the shipped scene configs
 
@@ -608,6 +630,53 @@ def render_img(sampler: DensityGridSampler, model: NGPNetworks, rays_o: torch.Te
         out = model(pos, dirs)
         imgs[pixel:pixel + B] = sampler.rays2rgb(out, inference=True)
     return imgs[:R]
+
+
+# ------------------------------------------------------------------------------------------------------------------ the density on a lattice
+DENSITY_FLOOR = -1.0e4              # what `empty_value = -inf` becomes: exp() of it is 0 in fp32 (empty space), and marching cubes can still interpolate against it
+
+
+def unit_spacing(n: int) -> float:
+    """The largest fp32 spacing s <= 1 / (n - 1) whose last lattice point fma(n - 1, s, 0) still lies inside [0, 1] (1 for n == 1)."""
+    if n <= 1:
+        return 1.0
+    s = np.float32(1.0 / (n - 1))
+    while float(np.float32(float(n - 1) * float(s))) > 1.0:             # the product is exact in fp64: one rounding, like the kernel's fma
+        s = np.nextafter(s, np.float32(0))
+    return float(s)
+
+
+def density_volume(model: NGPNetworks, sampler: Optional["DensityGridSampler"] = None, resolution: Optional[int] = None, dims: Optional[Sequence[int]] = None,
+                   origin: Sequence[float] = (0.0, 0.0, 0.0), spacing: Optional[Sequence[float]] = None, empty_value: float = -math.inf) -> torch.Tensor:
+    """The RAW density on a lattice -> volume [nx, ny, nz] fp32 on the device, laid out as `mesh.marching_cubes` reads it (`tvr_ngp_density_grid`).  Lattice point
+    (i, j, k) is the unit-cube position fma((i, j, k), spacing, origin), formed in the kernel; no point tensor exists.  `resolution` = R is short for dims (R, R, R);
+    without `spacing` the lattice spans the unit cube from `origin` = 0 (`unit_spacing`).  With a `sampler`, a point whose occupancy cell (the march's lookup:
+    the cascade of the position, that cascade's cell) is not set in `density_grid_bitfield` receives `empty_value` without being evaluated, and so does every point
+    outside [0,1]^3; evaluated points are bit-equal to `NGPNetworks.density_raw`.  `empty_value` = -inf (the default) is stored as DENSITY_FLOOR.  The level set
+    sigma = s of the density is `raw = log(s)`."""
+    grid = model.pos_encoder.m_grid
+    _need_gpu(grid, "density_volume")
+    if (resolution is None) == (dims is None):
+        raise ValueError("density_volume: give either resolution or dims")
+    dims = [int(resolution)] * 3 if dims is None else [int(d) for d in dims]
+    if len(dims) != 3 or not all(0 < d < (1 << 31) for d in dims):
+        raise ValueError(f"density_volume: dims {dims} must be three positive int32 values")
+    if spacing is None:
+        spacing = [unit_spacing(d) for d in dims]
+    empty = float(empty_value)
+    if math.isnan(empty):
+        raise ValueError("density_volume: empty_value is NaN")
+    empty = DENSITY_FLOOR if empty == -math.inf else empty
+    bits = None
+    if sampler is not None:
+        bits = sampler.density_grid_bitfield
+        _need_gpu(bits, "density_volume")
+    lo, hi = _box(sampler.aabb_range) if sampler is not None else (None, None)
+    vol = L.dev_empty(tuple(max(d, 0) for d in dims), torch.float32, grid.device, what="density volume")
+    L.check(L.lib().tvr_ngp_density_grid(C.byref(model.pos_encoder.cfg), grid.data_ptr(), model.packed().data_ptr(), None if bits is None else bits.data_ptr(),
+                                         lo, hi, (C.c_int32 * 3)(*dims), _f3(origin), _f3(spacing), empty, vol.data_ptr() if vol.numel() else None,
+                                         _stream(grid.device)), "tvr_ngp_density_grid")
+    return vol
 
 
 # ------------------------------------------------------------------------------------------------------------------ rays
