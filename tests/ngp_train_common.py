@@ -8,14 +8,19 @@
                                     held fixed: differentiable with respect to the network outputs.
   * composite_loop                  the compositor's loop as the kernel runs it — T multiplied up step by step, colour added in sample order — in a chosen
                                     numpy dtype, serial over the steps and vectorised over the rays (every ray sees exactly its own loop's operations in
-                                    order), plus the analytic gradient of include/tvr_ngp.h.
+                                    order), plus the analytic gradient of include/tvr_ngp.h; `mutation=` restates six defects a kernel could have.
+  * designed_case / scene_inputs    the compositor tests' inputs: the designed ladder (constant dt, or a random dt per row) and the shared scene (constant dt, or
+                                    cone-stepped), with the rays that are compared; COMPOSITOR_POWER lists the (case, mutation) pairs the host test proves.
   * step_t                          one whole step's loss sum from (parameters, rows, background, target).
 fp64 on the CPU is the reference; the same code in fp32 is the yardstick the GPU tests derive their bars from.
 """
+import functools
 import os
 
 import numpy as np
 import torch
+
+import ngp_frame_common as F
 
 M32 = 0xFFFFFFFF
 THR = 1e-4
@@ -177,11 +182,24 @@ def composite_t(net_out, dt, numsteps, n_rows, bg, stop=None):
     return rgb + torch.where(full, t_end, torch.zeros_like(t_end))[:, None] * bg.to(dtype), stop
 
 
-def composite_loop(net_out, coords, numsteps, n_rows, bg, dtype=np.float64, grad_rgb=None):
+COMPOSITOR_MUTATIONS = ("dt_first_row", "dt_next_row", "dt_backward_stale", "suffix_without_background", "background_when_cut", "stop_one_late")
+
+
+def composite_loop(net_out, coords, numsteps, n_rows, bg, dtype=np.float64, grad_rgb=None, mutation=None):
     """The kernel's loop in numpy `dtype`: per ray T = 1; for j < nc: stop if T < 1e-4; rgb += alpha T c; T *= 1 - alpha; background if all n steps were
-    walked.  Serial over j, vectorised over rays.  Returns dict(rgb [R,3], stop [R] samples composited, n, nc, T_end [R], and with grad_rgb: grad [n_rows,4],
-    sigma_dt [n_rows] (0 on rows not composited), ray [n_rows] = owning ray of each composited row, -1 elsewhere)."""
+    walked.  Serial over j, vectorised over rays.  Returns dict(rgb [R,3], stop [R] samples composited, n, nc, T_end [R], T_seen [R,M] = T in front of sample j
+    (frozen behind the stop), and with grad_rgb: grad [n_rows,4], sigma_dt [n_rows] (0 on rows not composited), ray [n_rows] = owning ray of each composited
+    row, -1 elsewhere).
+    `mutation` (one of COMPOSITOR_MUTATIONS) restates a defect a kernel could have; tests/test_ngp_train_host.py proves that the GPU tests' bars see each:
+      dt_first_row               every row of a ray uses the dt of the ray's first row;
+      dt_next_row                row j uses the dt of row j + 1, the ray's last row keeps its own;
+      dt_backward_stale          T, w and rgb use the true dt; the sigma dt factor and the alpha of the gradient use the first row's (the backward's second walk
+                                 disagreeing with its first);
+      suffix_without_background  the gradient's suffix leaves out T_end * bg;
+      background_when_cut        the background is added when stop == nc instead of stop == n;
+      stop_one_late              the T < 1e-4 test comes after the sample is added: the sample in front of which T fell below the threshold is composited too."""
     from oracle import ngp_oracle as N
+    assert mutation is None or mutation in COMPOSITOR_MUTATIONS
     ns = np.asarray(numsteps, np.int64).reshape(-1, 2)
     n, base = ns[:, 0], ns[:, 1]
     R = n.shape[0]
@@ -193,6 +211,11 @@ def composite_loop(net_out, coords, numsteps, n_rows, bg, dtype=np.float64, grad
     one = dtype(1)
     o = np.asarray(net_out, np.float32)[idx].astype(dtype) if M else np.zeros((R, 0, 4), dtype)
     dt = np.asarray(N.unwarp_dt(np.asarray(coords, np.float32)[idx, 3]), np.float32).astype(dtype) if M else np.zeros((R, 0), dtype)
+    dt_true = dt
+    if M and mutation == "dt_first_row":
+        dt = np.broadcast_to(dt[:, :1], dt.shape).copy()
+    elif M and mutation == "dt_next_row":
+        dt = np.where(j + 1 < nc[:, None], np.concatenate([dt[:, 1:], dt[:, -1:]], 1), dt)
     sigma_dt = np.exp(o[..., 3]) * dt
     alpha = one - np.exp(-sigma_dt)
     c = one / (one + np.exp(-o[..., :3]))
@@ -201,22 +224,32 @@ def composite_loop(net_out, coords, numsteps, n_rows, bg, dtype=np.float64, grad
     live = np.zeros((R, M), bool)
     alive = np.ones(R, bool)
     for k in range(M):
+        late = alive & valid[:, k] & (T < dtype(THR)) if mutation == "stop_one_late" else None
         alive = alive & valid[:, k] & ~(T < dtype(THR))
         live[:, k] = alive
         Tj[:, k] = T
         T = np.where(alive, T * (one - alpha[:, k]), T)
+        if late is not None:
+            live[:, k] |= late                                                 # added, and only then tested: T stays what the test saw
     stop = live.sum(1)
     w = np.where(live, alpha * Tj, dtype(0))
     prefix = np.cumsum(w[..., None] * c, axis=1, dtype=dtype)                  # sequential: the loop's own order of additions
     bgv = np.asarray(bg, np.float32).astype(dtype).reshape(-1, 3)
-    rgb = (prefix[:, -1] if M else np.zeros((R, 3), dtype)) + np.where(stop == n, T, dtype(0))[:, None] * bgv
-    res = dict(rgb=rgb, stop=stop, n=n, nc=nc, T_end=T)
+    broke_late = (live & (Tj < dtype(THR))).any(1)                             # stop_one_late only: that loop left through its break, so no background
+    walked = (stop == nc) if mutation == "background_when_cut" else (stop == n) & ~broke_late
+    back = np.where(walked, T, dtype(0))[:, None] * bgv
+    rgb = (prefix[:, -1] if M else np.zeros((R, 3), dtype)) + back
+    res = dict(rgb=rgb, stop=stop, n=n, nc=nc, T_end=T, T_seen=Tj)
     if grad_rgb is not None:
         g = np.asarray(grad_rgb, np.float32).astype(dtype)[:, None, :]
-        suffix = rgb[:, None, :] - prefix
-        Tn = Tj * (one - alpha)
+        suffix = (rgb - back if mutation == "suffix_without_background" else rgb)[:, None, :] - prefix
+        sigma_dt_g, alpha_g = sigma_dt, alpha
+        if M and mutation == "dt_backward_stale":
+            sigma_dt_g = np.exp(o[..., 3]) * dt_true[:, :1]
+            alpha_g = one - np.exp(-sigma_dt_g)
+        Tn = Tj * (one - alpha_g)
         d_c = g * w[..., None] * (c * (one - c))
-        d_s = sigma_dt * (g * (Tn[..., None] * c - suffix)).sum(-1)
+        d_s = sigma_dt_g * (g * (Tn[..., None] * c - suffix)).sum(-1)
         grad = np.zeros((n_rows, 4), dtype)
         sd = np.zeros(n_rows, dtype)
         ray = np.full(n_rows, -1, np.int64)
@@ -236,6 +269,160 @@ def backward_row_error(got, ref, grad_rgb):
     gmax = np.abs(np.asarray(grad_rgb, np.float64)).max(1)[ref["ray"][own]]
     scale = np.maximum(gmax, 1e-30) * np.maximum(1.0, ref["sigma_dt"][own])
     return float((np.abs(np.asarray(got, np.float64)[own] - ref["grad"][own]).max(1) / scale).max())
+
+
+# --------------------------------------------------------------------------------------------------------------- compositor cases
+# Inputs of the compositor tests, built from the CPU oracle only: the host test checks their conditions and the bars' power on them, the GPU test runs the
+# kernels on them.  Two of them give every row its own step size, which no constant-dt input can (column 3 is one value there: a kernel that took dt from
+# another row, or whose backward walks disagreed about it, would compute the same bits):
+#   * the designed ladder with column 3 redrawn per row (`random_dt_rows`): the network's outputs are an input there, so only the compositor's own rounding
+#     moves ln T and a ray is compared when its smallest break margin |ln(T / 1e-4)| is at least RANDOM_DT_MARGIN;
+#   * the shared scene sampled with const_dt=False (cone stepping), rays kept by the network bar's shift of ln T as on the constant-dt scene.
+SCENES = (1, 2, 33, 97, F.NO_BREAK)
+CAP_KINDS = ("total", "inside", "ray_end", "slack")
+SLACK = 37                                                    # rows behind the total in the "slack" capacity: owned by no ray
+RANDOM_DT_SEED = 300                                          # chosen on the fp64 reference alone: at most 2 % of the ladder's rays fall below the margin
+RANDOM_DT_MARGIN = 1e-3
+RANDOM_DT_MAX = 0.1                                           # warped; unwarped dt then runs from 0.00085 (the constant step) to 0.0042
+LEFT_OUT_SHARE = 0.02
+FORWARD_BAR = 2e-5                                            # tvr_ngp_composite's bar
+
+
+def const_warped_dt():
+    """Column 3 of a const_dt row: dt = MIN_CONE_STEPSIZE / 2 warped as the sampler warps it (-1/30 in fp32)."""
+    from oracle import ngp_oracle as N
+    f32 = np.float32
+    mn = N.MIN_CONE_STEPSIZE
+    return f32(f32(f32(np.float64(mn) * 0.5) - mn) / f32(mn * f32(16) - mn))
+
+
+def random_dt_rows(coords, seed):
+    """A copy of `coords` with column 3 redrawn per row, uniform in [the constant warped dt, RANDOM_DT_MAX], as fp32."""
+    c = np.array(coords, np.float32, copy=True)
+    c[:, 3] = np.random.default_rng(seed).uniform(float(const_warped_dt()), RANDOM_DT_MAX, c.shape[0]).astype(np.float32)
+    return c
+
+
+def backward_bar(e32):
+    """The compositor backward's bar from the fp32 loop's own scaled error."""
+    return max(4 * e32, 1e-6)
+
+
+def row_owner(numsteps, n_rows):
+    """[n_rows] the ray whose capacity-clamped steps hold each row, -1 for rows no ray owns."""
+    idx, valid, _, _ = ray_rows(torch.as_tensor(np.asarray(numsteps, np.int64)), n_rows)
+    owner = np.full(n_rows, -1, np.int64)
+    idx, valid = idx.numpy(), valid.numpy()
+    owner[idx[valid]] = np.broadcast_to(np.arange(idx.shape[0])[:, None], idx.shape)[valid]
+    return owner
+
+
+@functools.lru_cache(maxsize=None)
+def designed_inputs(k, dt_kind="const"):
+    """The 421-ray ladder in designed_scene(k): rows (dt_kind "random": column 3 redrawn per row), network outputs (the C oracle's; the network does not read
+    column 3), a random background and gradient per ray, the capacities, and the rays that are compared (all of them for "const")."""
+    from oracle import ngp_oracle as N
+    assert dt_kind in ("const", "random")
+    _, _, coords, ns = F.designed_rows()
+    levels, arrs = F.designed_scene(k)
+    out = N.network_c(levels, arrs, coords)
+    rng = np.random.default_rng(100 + k)
+    R, total = ns.shape[0], coords.shape[0]
+    bg = rng.random((R, 3), dtype=np.float32)
+    g = rng.normal(0, 1, (R, 3)).astype(np.float32)
+    n, base = ns[:, 0].astype(np.int64), ns[:, 1].astype(np.int64)
+    inside = next(r for r in range(R // 2, R) if n[r] >= 3 and base[r] + n[r] < total)
+    at_end = next(r for r in range(R // 3, R) if n[r] >= 1 and base[r] + n[r] < total)
+    caps = {"total": total, "inside": int(base[inside] + n[inside] // 2), "ray_end": int(base[at_end] + n[at_end]), "slack": total + SLACK}
+    keep = np.ones(R, bool)
+    if dt_kind == "random":
+        coords = random_dt_rows(coords, RANDOM_DT_SEED)
+        keep = F.composite_f64(out, coords, ns, F.BG)[2] >= RANDOM_DT_MARGIN       # every decision of the uncut ray: a superset of any capacity's
+    return coords, ns, out, bg, g, caps, keep
+
+
+@functools.lru_cache(maxsize=None)
+def designed_case(k, cap_kind, dt_kind="const"):
+    """Inputs cut / padded to the capacity, and the loop reference in fp64 and fp32 (computed once, shared by the tests that need it)."""
+    coords, ns, out, bg, g, caps, keep = designed_inputs(k, dt_kind)
+    n_rows, total = caps[cap_kind], coords.shape[0]
+    if n_rows > total:                                          # rows no ray owns hold NaN: nothing may read them, their gradient is exactly 0
+        out_c = np.concatenate([out, np.full((n_rows - total, 4), np.nan, np.float32)])
+        coords_c = np.concatenate([coords, np.full((n_rows - total, 7), np.nan, np.float32)])
+    else:
+        out_c, coords_c = out[:n_rows], coords[:n_rows]
+    ref = composite_loop(out_c, coords_c, ns, n_rows, bg, np.float64, grad_rgb=g)
+    r32 = composite_loop(out_c, coords_c, ns, n_rows, bg, np.float32, grad_rgb=g)
+    return out_c, coords_c, ns, bg, g, n_rows, ref, r32, keep
+
+
+@functools.lru_cache(maxsize=None)
+def scene_rows(const_dt=True):
+    """The shared aabb_scale-4 scene under ngp_camera_rays(32, 32), marched by the oracle from Pcg32(1337): (levels, arrays, rays_o, rays_d, coords, numsteps,
+    the C oracle's network outputs).  const_dt=False: cone stepping, every row its own dt."""
+    from conftest import NGP_AABB_SCALE, ngp_camera_rays
+    from jittor_myc_nerfs_amd import synthetic
+    from oracle import ngp_oracle as N
+    levels = N.grid_levels(NGP_AABB_SCALE)
+    arrs = synthetic.make_ngp_scene_arrays(levels["offsets"])
+    arrs["density_grid_bitfield"], _ = N.update_bitfield(arrs["density_grid"])
+    o, d = ngp_camera_rays(32, 32)
+    coords, _, ns, _, _ = N.sample(o, d, arrs["density_grid_bitfield"], NGP_AABB_SCALE, N.Pcg32(1337).state, const_dt=const_dt)
+    out = N.network_c(levels, arrs, coords)
+    return levels, arrs, o, d, coords, ns, out
+
+
+def scene_capacities(total, const_dt):
+    """The row counts the shared-scene compositor tests run: all rows, and a cut (100 000 on the constant-dt rows, two thirds of the cone rows)."""
+    return {"total": total, "cut": 100000 if const_dt else total * 2 // 3}
+
+
+@functools.lru_cache(maxsize=None)
+def scene_inputs(const_dt=True):
+    """(coords, numsteps, out, bg, g, keep) of the shared scene: a random background and gradient per ray; rays are compared when the network bar cannot move
+    ln T across any of their break decisions."""
+    _, _, _, _, coords, ns, out = scene_rows(const_dt)
+    rng = np.random.default_rng(7 if const_dt else 8)
+    R = ns.shape[0]
+    bg, g = rng.random((R, 3), dtype=np.float32), rng.normal(0, 1, (R, 3)).astype(np.float32)
+    keep = F.composite_f64(out, coords, ns, F.BG)[2] >= F.network_shift(out)
+    return coords, ns, out, bg, g, keep
+
+
+def compositor_case(name):
+    """(out, coords, numsteps, bg, g, n_rows, keep) of a named case: 'ladder-{const|random}-k{K}-{capacity}' or '{shared|cone}-{total|cut}'."""
+    parts = name.split("-")
+    if parts[0] == "ladder":
+        out, coords, ns, bg, g, n_rows, _, _, keep = designed_case(int(parts[2][1:]), parts[3], parts[1])
+        return out, coords, ns, bg, g, n_rows, keep
+    const_dt = {"shared": True, "cone": False}[parts[0]]
+    coords, ns, out, bg, g, keep = scene_inputs(const_dt)
+    n_rows = scene_capacities(coords.shape[0], const_dt)[parts[1]]
+    return out[:n_rows], coords[:n_rows], ns, bg, g, n_rows, keep
+
+
+def compositor_measures(case, got_rgb, got_grad, ref, r32=None):
+    """The GPU tests' own measures of a compositor result against the fp64 loop `ref` on `case` (compositor_case's tuple): rgb L-inf on the kept rays, the
+    scaled backward error on the kept rays' composited rows, and the number of rows that must be exactly 0 (behind a kept ray's break, behind the cut, owned
+    by no ray) but are not.  With `r32` (the fp32 loop) also its scaled backward error, from which the backward bar derives."""
+    _, _, ns, _, g, n_rows, keep = case
+    fwd = float(np.abs(np.asarray(got_rgb, np.float64) - ref["rgb"])[keep].max())
+    rows_kept = (ref["ray"] >= 0) & keep[np.maximum(ref["ray"], 0)]
+    sub = dict(ref, ray=np.where(rows_kept, ref["ray"], -1))
+    owner = row_owner(ns, n_rows)
+    dead = (ref["ray"] < 0) & ((owner < 0) | keep[np.maximum(owner, 0)])
+    res = dict(forward=fwd, backward=backward_row_error(got_grad, sub, g), dead_rows=int(dead.sum()), dead_nonzero=int(np.asarray(got_grad)[dead].any(1).sum()))
+    if r32 is not None:
+        res["e32"] = backward_row_error(r32["grad"], sub, g)
+    return res
+
+
+# (case, mutation) pairs the host test proves the bars' power on; every mutation appears
+COMPOSITOR_POWER = ([("cone-total", m) for m in ("dt_first_row", "dt_next_row", "dt_backward_stale", "suffix_without_background", "stop_one_late")]
+                    + [("cone-cut", m) for m in ("dt_first_row", "dt_next_row", "dt_backward_stale", "background_when_cut")]
+                    + [("ladder-random-k33-total", m) for m in ("dt_first_row", "dt_next_row", "dt_backward_stale", "stop_one_late")]
+                    + [("ladder-random-k97-inside", m) for m in ("dt_first_row", "dt_next_row", "dt_backward_stale", "background_when_cut")]
+                    + [(f"ladder-random-k{F.NO_BREAK}-total", m) for m in ("dt_first_row", "dt_next_row", "dt_backward_stale", "suffix_without_background")])
 
 
 # --------------------------------------------------------------------------------------------------------------- one step

@@ -1,7 +1,6 @@
 """GPU checks of Instant-NGP training: csrc/tvr_ngp_train.hip through the C-ABI (include/tvr_ngp.h, "training") and the host surface of
 jittor_myc_nerfs_amd.ngp / ngp_train, against the fp64 references of tests/ngp_train_common.py.  Bars that are not fixed numbers are derived from the same
 reference run in fp32 on the CPU (printed before they are asserted)."""
-import functools
 import os
 import sys
 
@@ -12,12 +11,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ngp_frame_common as F  # noqa: E402
 import ngp_train_common as K  # noqa: E402
-from conftest import NGP_AABB_SCALE, ngp_camera_rays  # noqa: E402
+from conftest import NGP_AABB_SCALE  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SCENES = (1, 2, 33, 97, F.NO_BREAK)
-SLACK = 37                                                    # rows behind the total in the "slack" capacity: owned by no ray
+SCENES = K.SCENES                                             # (1, 2, 33, 97, F.NO_BREAK)
 
 
 def _t(a, dtype=None):
@@ -25,39 +23,7 @@ def _t(a, dtype=None):
 
 
 # --------------------------------------------------------------------------------------------------------------- designed inputs
-@functools.lru_cache(maxsize=None)
-def _designed_inputs(k):
-    """The 421-ray ladder in designed_scene(k): rows, network outputs (the C oracle's), a random background and gradient per ray, and the capacities."""
-    from oracle import ngp_oracle as N
-    _, _, coords, ns = F.designed_rows()
-    levels, arrs = F.designed_scene(k)
-    out = N.network_c(levels, arrs, coords)
-    rng = np.random.default_rng(100 + k)
-    R, total = ns.shape[0], coords.shape[0]
-    bg = rng.random((R, 3), dtype=np.float32)
-    g = rng.normal(0, 1, (R, 3)).astype(np.float32)
-    n, base = ns[:, 0].astype(np.int64), ns[:, 1].astype(np.int64)
-    inside = next(r for r in range(R // 2, R) if n[r] >= 3 and base[r] + n[r] < total)
-    at_end = next(r for r in range(R // 3, R) if n[r] >= 1 and base[r] + n[r] < total)
-    caps = {"total": total, "inside": int(base[inside] + n[inside] // 2), "ray_end": int(base[at_end] + n[at_end]), "slack": total + SLACK}
-    return coords, ns, out, bg, g, caps
-
-
-@functools.lru_cache(maxsize=None)
-def _designed_case(k, cap_kind):
-    """Inputs cut / padded to the capacity, and the loop reference in fp64 and fp32 (computed once, shared by the forward and the backward test)."""
-    coords, ns, out, bg, g, caps = _designed_inputs(k)
-    n_rows, total = caps[cap_kind], coords.shape[0]
-    if n_rows > total:                                          # rows no ray owns hold NaN: nothing may read them, their gradient is exactly 0
-        out_c = np.concatenate([out, np.full((n_rows - total, 4), np.nan, np.float32)])
-        coords_c = np.concatenate([coords, np.full((n_rows - total, 7), np.nan, np.float32)])
-    else:
-        out_c, coords_c = out[:n_rows], coords[:n_rows]
-    ref = K.composite_loop(out_c, coords_c, ns, n_rows, bg, np.float64, grad_rgb=g)
-    r32 = K.composite_loop(out_c, coords_c, ns, n_rows, bg, np.float32, grad_rgb=g)
-    return out_c, coords_c, ns, bg, g, n_rows, ref, r32
-
-
+# the inputs and their fp64 / fp32 loop references are built in ngp_train_common ("compositor cases"), where the host test checks them too
 def _run_compositor(out, coords, ns, bg, g, n_rows):
     from jittor_myc_nerfs_amd import ngp_train
     x = _t(out).requires_grad_(True)
@@ -66,95 +32,157 @@ def _run_compositor(out, coords, ns, bg, g, n_rows):
     return rgb.detach().cpu().numpy(), x.grad.cpu().numpy()
 
 
-def test_compositor_forward_designed():
-    from jittor_myc_nerfs_amd import ngp
+def _forward_designed(dt_kind):
+    """The forward on the ladder under every scene and capacity; returns which situations came up.  For "random" only the kept rays are held to the fp64
+    loop (at most 2 % are left out: their smallest break margin is below 1e-3); the exact statements hold for every ray."""
+    from jittor_myc_nerfs_amd import ngp, ngp_train
     seen = dict(cut_to_zero=False, no_steps=False, breaks=False, ends_dark=False)
     sampler = ngp.DensityGridSampler(ngp.NGPNetworks(1), 1, rng=ngp.Pcg32(1))
+    worst = 0.0
     for k in SCENES:
-        for cap_kind in ("total", "inside", "ray_end", "slack"):
-            out, coords, ns, bg, g, n_rows, ref, _ = _designed_case(k, cap_kind)
+        for cap_kind in K.CAP_KINDS:
+            out, coords, ns, bg, g, n_rows, ref, _, keep = K.designed_case(k, cap_kind, dt_kind)
+            assert (~keep).mean() <= K.LEFT_OUT_SHARE
             rgb, _ = _run_compositor(out, coords, ns, bg, g, n_rows)
-            err = float(np.abs(rgb - ref["rgb"]).max())
-            print(f"forward k={k} {cap_kind}: n_rows {n_rows} L-inf {err:.3e}")
-            assert err < 2e-5                                    # tvr_ngp_composite's bar
+            err = float(np.abs(rgb - ref["rgb"])[keep].max())
+            worst = max(worst, err)
+            print(f"forward {dt_kind} dt k={k} {cap_kind}: n_rows {n_rows} L-inf {err:.3e}, {(~keep).sum()} rays left out")
+            assert err < K.FORWARD_BAR                           # tvr_ngp_composite's bar
             n, nc, stop = ref["n"], ref["nc"], ref["stop"]
             zero = (nc == 0) & (n > 0)
             assert np.all(rgb[zero] == 0) and np.array_equal(rgb[n == 0], bg[n == 0])
             dark = (stop == n) & (n > 0) & (ref["T_end"] < 1e-4)   # T falls below the threshold only behind the last sample: background times that T
             seen["cut_to_zero"] |= bool(zero.any())
             seen["no_steps"] |= bool((n == 0).any())
-            seen["breaks"] |= bool((stop < nc).any())
-            seen["ends_dark"] |= bool(dark.any())
+            seen["breaks"] |= bool(((stop < nc) & keep).any())
+            seen["ends_dark"] |= bool((dark & keep).any())
         # one background, no cut: the inference compositor's bits
-        out, coords, ns, _, _, n_rows, _, _ = _designed_case(k, "total")
-        from jittor_myc_nerfs_amd import ngp_train
+        out, coords, ns, _, _, n_rows, _, _, _ = K.designed_case(k, "total", dt_kind)
         const = np.tile(np.asarray(F.BG, np.float32), (ns.shape[0], 1))
         a = ngp_train.composite_train(_t(out), _t(coords), _t(ns), _t(const))
         b = sampler._composite(_t(out), _t(coords), _t(ns), F.BG)
         assert torch.equal(a, b)
+    print(f"forward designed, {dt_kind} dt: worst L-inf {worst:.3e}")
+    return seen
+
+
+def _backward_designed(dt_kind):
+    worst, worst_err = 0.0, 0.0
+    for k in SCENES:
+        for cap_kind in K.CAP_KINDS:
+            case = K.designed_case(k, cap_kind, dt_kind)
+            out, coords, ns, bg, g, n_rows, ref, r32, keep = case
+            rgb, grad = _run_compositor(out, coords, ns, bg, g, n_rows)
+            _, grad2 = _run_compositor(out, coords, ns, bg, g, n_rows)
+            assert grad.shape == (n_rows, 4) and grad.tobytes() == grad2.tobytes()          # one owner per row: the same bytes on every run
+            m = K.compositor_measures((out, coords, ns, bg, g, n_rows, keep), rgb, grad, ref, r32)
+            e32, err = m["e32"], m["backward"]
+            bar = K.backward_bar(e32)
+            worst, worst_err = max(worst, err / bar), max(worst_err, err)
+            print(f"backward {dt_kind} dt k={k} {cap_kind}: scaled error {err:.3e}, fp32 loop {e32:.3e}, bar {bar:.3e}")
+            assert np.array_equal(r32["stop"][keep], ref["stop"][keep])
+            assert err <= bar
+            # behind a (compared ray's) break, behind the cut, in [total, n_rows): exactly 0
+            assert m["dead_rows"] > 0 and m["dead_nonzero"] == 0 and np.isfinite(grad).all()
+    print(f"backward designed, {dt_kind} dt: worst scaled error {worst_err:.3e}, worst error / bar = {worst:.3f}")
+
+
+def test_compositor_forward_designed():
+    seen = _forward_designed("const")
     assert all(seen.values()), seen
 
 
 def test_compositor_backward_designed():
-    worst = 0.0
-    for k in SCENES:
-        for cap_kind in ("total", "inside", "ray_end", "slack"):
-            out, coords, ns, bg, g, n_rows, ref, r32 = _designed_case(k, cap_kind)
-            _, grad = _run_compositor(out, coords, ns, bg, g, n_rows)
-            _, grad2 = _run_compositor(out, coords, ns, bg, g, n_rows)
-            assert grad.shape == (n_rows, 4) and grad.tobytes() == grad2.tobytes()          # one owner per row: the same bytes on every run
-            e32 = K.backward_row_error(r32["grad"], ref, g)
-            bar = max(4 * e32, 1e-6)
-            err = K.backward_row_error(grad, ref, g)
-            worst = max(worst, err / bar)
-            print(f"backward k={k} {cap_kind}: scaled error {err:.3e}, fp32 loop {e32:.3e}, bar {bar:.3e}")
-            assert np.array_equal(r32["stop"], ref["stop"])
-            assert err <= bar
-            dead = ref["ray"] < 0                                # behind a break, behind the cut, in [total, n_rows)
-            assert dead.any() and not grad[dead].any() and np.isfinite(grad).all()
-    print(f"backward designed: worst error / bar = {worst:.3f}")
+    _backward_designed("const")
+
+
+def test_compositor_forward_random_dt():
+    """The same ladder, scenes, capacities and bar with column 3 redrawn per row (uniform in [-1/30, 0.1] warped, seed 300): no two rows of a ray share a dt, so
+    a kernel that read another row's — the ray's first, row j +- 1, another column — misses the bar by orders of magnitude (test_ngp_train_host.py: forward
+    error / bar 492 to 7.7e3 for the wrong-row defects on the uncut ladder under k = 33 and the scene that never breaks).  Rays whose smallest break margin is below 1e-3 are left out (1 of 421 under k = 97, none
+    elsewhere); every situation the constant-dt ladder shows comes up here too, `ends_dark` included; bit-equal to tvr_ngp_composite with one background.
+    MI355X: L-inf 3.7e-7 at worst over the twenty cases (bar 2e-5; the constant-dt ladder: 3.9e-7)."""
+    seen = _forward_designed("random")
+    assert all(seen.values()), seen
+
+
+def test_compositor_backward_random_dt():
+    """The backward on the random-dt ladder: the walk that parks T_j and the walk from the back must read the same row's dt (a stale dt in the second walk:
+    error / bar 1.6e4 at the least on the host).  Same bar as the constant-dt test, on the kept rays' rows; rows behind a kept ray's break, behind the cut and
+    rows no ray owns are exactly 0; two runs give the same bytes.
+    MI355X: scaled error 5.2e-8 at worst, 0.052 of its bar (the constant-dt ladder: 2.5e-8, 0.025)."""
+    _backward_designed("random")
+
+
+def test_compositor_empty_capacity():
+    """n_rows == 0 with rays (a batch whose capacity holds nothing): rays without steps receive their background, every other ray exactly 0, and the backward
+    returns a [0, 4] gradient; no rays at all: empty results, and the rows' gradient is exactly 0."""
+    from jittor_myc_nerfs_amd import ngp_train
+    rng = np.random.default_rng(3)
+    ns = np.array([[0, 0], [3, 0], [0, 3], [5, 3], [0, 8]], np.int32)
+    bg, g = rng.random((5, 3), dtype=np.float32), rng.normal(0, 1, (5, 3)).astype(np.float32)
+    x = torch.zeros(0, 4, device=DEV, requires_grad=True)
+    rgb = ngp_train.composite_train(x, torch.zeros(0, 7, device=DEV), _t(ns), _t(bg))
+    want = np.where((ns[:, 0] == 0)[:, None], bg, np.float32(0))
+    assert rgb.shape == (5, 3) and rgb.detach().cpu().numpy().tobytes() == want.tobytes()
+    rgb.backward(_t(g))
+    assert x.grad is not None and tuple(x.grad.shape) == (0, 4)
+    for rows in (0, 5):
+        x = torch.randn(rows, 4, device=DEV).requires_grad_(True)
+        rgb = ngp_train.composite_train(x, torch.rand(rows, 7, device=DEV), torch.zeros(0, 2, dtype=torch.int32, device=DEV), torch.zeros(0, 3, device=DEV))
+        assert tuple(rgb.shape) == (0, 3)
+        rgb.backward(torch.zeros(0, 3, device=DEV))
+        assert tuple(x.grad.shape) == (rows, 4) and not x.grad.any()
+    torch.cuda.synchronize()
 
 
 # --------------------------------------------------------------------------------------------------------------- the shared scene
-@functools.lru_cache(maxsize=None)
-def _scene_rows():
-    from jittor_myc_nerfs_amd import synthetic
-    from oracle import ngp_oracle as N
-    levels = N.grid_levels(NGP_AABB_SCALE)
-    arrs = synthetic.make_ngp_scene_arrays(levels["offsets"])
-    arrs["density_grid_bitfield"], _ = N.update_bitfield(arrs["density_grid"])
-    o, d = ngp_camera_rays(32, 32)
-    coords, _, ns, _, _ = N.sample(o, d, arrs["density_grid_bitfield"], NGP_AABB_SCALE, N.Pcg32(1337).state)
-    out = N.network_c(levels, arrs, coords)
-    return levels, arrs, o, d, coords, ns, out
+_scene_rows = K.scene_rows
 
 
-def test_compositor_shared_scene():
-    levels, arrs, _, _, coords, ns, out = _scene_rows()
+def _shared_scene(const_dt):
+    """The compositor on the shared scene's rows at the full row count and at a cut, kept rays against the fp64 loop.  Returns (coords, ns, out, measures)."""
+    coords, ns, out, bg, g, keep = K.scene_inputs(const_dt)
     total, R = coords.shape[0], ns.shape[0]
-    assert R == 1024 and total > 100000
-    rng = np.random.default_rng(7)
-    bg, g = rng.random((R, 3), dtype=np.float32), rng.normal(0, 1, (R, 3)).astype(np.float32)
-    _, brk, margin, _ = F.composite_f64(out, coords, ns, F.BG)
-    keep = margin >= F.network_shift(out)
-    print(f"shared scene: {total} rows, {(ns[:, 0] > 0).sum()} live rays, {(brk >= 0).sum()} break, {(~keep).sum()} left out, raw density max {out[:, 3].max():.1f}")
-    assert (~keep).mean() <= 0.02
+    what = "shared scene" if const_dt else "cone rows"
+    brk = F.composite_f64(out, coords, ns, F.BG)[1]
+    print(f"{what}: {total} rows, {(ns[:, 0] > 0).sum()} live rays, {(brk >= 0).sum()} break, {(~keep).sum()} left out, raw density max {out[:, 3].max():.1f}")
+    assert (~keep).mean() <= K.LEFT_OUT_SHARE
     assert (brk >= 0).sum() > 100
-    for n_rows in (total, 100000):
+    measures = []
+    for n_rows in K.scene_capacities(total, const_dt).values():
+        case = (out[:n_rows], coords[:n_rows], ns, bg, g, n_rows, keep)
         ref = K.composite_loop(out[:n_rows], coords[:n_rows], ns, n_rows, bg, np.float64, grad_rgb=g)
         r32 = K.composite_loop(out[:n_rows], coords[:n_rows], ns, n_rows, bg, np.float32, grad_rgb=g)
         rgb, grad = _run_compositor(out[:n_rows], coords[:n_rows], ns, bg, g, n_rows)
-        err = float(np.abs(rgb - ref["rgb"])[keep].max())
-        rows_kept = (ref["ray"] >= 0) & keep[np.maximum(ref["ray"], 0)]
-        sub = dict(ref, ray=np.where(rows_kept, ref["ray"], -1))
-        e32, eg = K.backward_row_error(r32["grad"], sub, g), K.backward_row_error(grad, sub, g)
-        bar = max(4 * e32, 1e-6)
-        print(f"shared scene n_rows={n_rows}: rgb L-inf {err:.3e}; backward scaled error {eg:.3e}, fp32 loop {e32:.3e}, bar {bar:.3e}")
-        assert err < 2e-5 and eg <= bar
-        owner = np.repeat(np.arange(R), ref["nc"])                         # bases are the prefix sum: the rows lie in ray order
-        assert owner.shape[0] == n_rows
-        dead = (ref["ray"] < 0) & keep[owner]                             # behind a compared ray's break: exactly 0
-        assert dead.any() and not grad[dead].any()
+        m = K.compositor_measures(case, rgb, grad, ref, r32)
+        err, e32, eg = m["forward"], m["e32"], m["backward"]
+        bar = K.backward_bar(e32)
+        print(f"{what} n_rows={n_rows}: rgb L-inf {err:.3e}; backward scaled error {eg:.3e}, fp32 loop {e32:.3e}, bar {bar:.3e}")
+        assert err < K.FORWARD_BAR and eg <= bar
+        assert np.repeat(np.arange(R), ref["nc"]).shape[0] == n_rows       # bases are the prefix sum: every row has an owner
+        assert m["dead_rows"] > 0 and m["dead_nonzero"] == 0               # behind a compared ray's break: exactly 0
+        measures.append(m)
+    return coords, ns, out, measures
+
+
+def test_compositor_shared_scene():
+    coords, ns, _, _ = _shared_scene(True)
+    assert ns.shape[0] == 1024 and coords.shape[0] > 100000
+
+
+def test_compositor_shared_scene_cone():
+    """The shared scene marched with const_dt=False: 35 923 rows whose warped dt runs from 0.069 to 0.205 (within a ray max / min reaches 2.96), at the full
+    row count and at two thirds of it; 5 of 1024 rays left out by the network bar's shift of ln T, 302 rays break.  Same bars as the constant-dt scene; with
+    one background and no cut bit-equal to tvr_ngp_composite, which test_gpu_ngp_frame.py::test_cone_stepping holds to fp64 on cone rows.
+    MI355X: rgb L-inf 5.3e-7 at both row counts; backward scaled error 1.7e-7 / 1.4e-7 (fp32 loop 5.1e-7 / 4.5e-7, bars 2.0e-6 / 1.8e-6)."""
+    from jittor_myc_nerfs_amd import ngp, ngp_train
+    coords, ns, out, _ = _shared_scene(False)
+    assert ns.shape[0] == 1024 and coords[:, 3].max() > 2 * coords[:, 3].min() > 0
+    sampler = ngp.DensityGridSampler(ngp.NGPNetworks(NGP_AABB_SCALE), NGP_AABB_SCALE, rng=ngp.Pcg32(1))
+    const = np.tile(np.asarray(F.BG, np.float32), (ns.shape[0], 1))
+    a = ngp_train.composite_train(_t(out), _t(coords), _t(ns), _t(const))
+    assert torch.equal(a, sampler._composite(_t(out), _t(coords), _t(ns), F.BG))
 
 
 # --------------------------------------------------------------------------------------------------------------- hash grid backward
@@ -239,9 +267,10 @@ def test_forward_train_matches_fp64_and_leaves_forward_alone(setup):
     assert not after.requires_grad and torch.equal(after, before)
 
 
-def test_one_step_gradients(setup):
+def _one_step(model, sampler, what):
+    """One whole step through `sampler` on the shared scene's 1024 rays: every parameter's gradient of the Huber sum over the compared rays against the fp64
+    restatement on the sampler's own rows, held to 4 x the fp32 restatement's error (both normalised by the tensor's largest gradient)."""
     from jittor_myc_nerfs_amd.losses import huber_loss
-    model, sampler = setup
     levels, arrs, o, d, _, _, _ = _scene_rows()
     cap = sampler.target_batch_size
     rng = np.random.default_rng(21)
@@ -263,8 +292,8 @@ def test_one_step_gradients(setup):
             out64 = K.network_t(K.params_t(arrs, torch.float64, requires_grad=False), ent, frac, K.sh_t(c[:, 4:7].double())).numpy()
         margin = F.composite_f64(out64.astype(np.float32), coords, sampler._rays_numsteps_compacted.cpu().numpy(), F.BG)[2]     # the decisions on the kept rows
         keep = margin >= F.network_shift(out64)
-        print(f"one step: {n_rows} rows, {(~keep).sum()} of {R} rays left out")
-        assert (~keep).mean() <= 0.02
+        print(f"{what}: {n_rows} rows, {(~keep).sum()} of {R} rays left out")
+        assert (~keep).mean() <= K.LEFT_OUT_SHARE
         ref, stop = K.grads_of_step(arrs, levels, coords, ns, n_rows, bg, target, torch.float64, keep_rays=keep)
         g32, _ = K.grads_of_step(arrs, levels, coords, ns, n_rows, bg, target, torch.float32, keep_rays=keep)
         model.zero_grad(set_to_none=True)
@@ -279,10 +308,60 @@ def test_one_step_gradients(setup):
         scale = np.abs(r).max()
         e = float(np.abs(got[name].double().cpu().numpy().reshape(r.shape) - r).max() / scale)
         e32 = float(np.abs(g32[name] - r).max() / scale)
-        print(f"one step {name}: max|grad| {scale:.3e}, HIP error {e:.3e}, fp32 restatement {e32:.3e}, bar {4 * e32:.3e}")
+        print(f"{what} {name}: max|grad| {scale:.3e}, HIP error {e:.3e}, fp32 restatement {e32:.3e}, bar {4 * e32:.3e}")
         if not e <= 4 * e32:
             bad.append(name)
     assert not bad, bad
+
+
+def test_one_step_gradients(setup):
+    _one_step(*setup, "one step")
+
+
+def _cone_sampler(model, cap):
+    """A const_dt=False sampler on the shared scene with the oracle's bitfield, so that its rows are the oracle's cone rows."""
+    from jittor_myc_nerfs_amd import ngp
+    arrs = K.scene_rows(False)[1]
+    s = ngp.DensityGridSampler(model, NGP_AABB_SCALE, const_dt=False, rng=ngp.Pcg32(1337), target_batch_size=cap).to(DEV)
+    ngp.load_scene_arrays(model, s, arrs)
+    return s
+
+
+def test_one_step_gradients_cone(setup):
+    """test_one_step_gradients' procedure through a const_dt=False sampler: every row brings its own dt through sample -> forward_train -> rays2rgb ->
+    backward.  Row capacity 2^14 of the 35 923 cone rows, so the capacity binds; rays kept by the reference's margin.
+    MI355X: 16 384 rows, 1 of 1024 rays left out; HIP error (fp32 restatement's) grid 2.3e-6 (6.1e-5), density_mlp.0 1.1e-6 (2.4e-5), density_mlp.2 7.9e-7
+    (1.9e-5), rgb_mlp.0 / .2 / .4 2.7e-7 / 3.7e-7 / 2.7e-7 (2.9e-6 / 2.4e-6 / 6.5e-6).  The restatement forms T from a prefix sum of optical depths, which loses
+    more under the cone's larger steps than the kernels' running product does, so the bar is looser here than on the constant-dt step."""
+    model, _ = setup
+    sampler = _cone_sampler(model, 1 << 14)
+    _one_step(model, sampler, "one step, cone")
+    assert sampler._coords.shape[0] == 1 << 14 and float(sampler._coords[:, 3].max()) > 2 * float(sampler._coords[:, 3].min()) > 0
+
+
+def test_sampler_training_bookkeeping_cone(setup):
+    """sample(is_training=True) under cone stepping with a capacity below the total: the rows are the first `cap` rows the oracle marches with
+    const_dt=False, bit for bit (column 3, each row's own warped dt, included), the step counts are the oracle's, the compacted counts obey the clamp."""
+    model, _ = setup
+    _, _, o, d, coords, ns, _ = K.scene_rows(False)
+    total, cap = coords.shape[0], 20000
+    assert cap < total
+    s = _cone_sampler(model, cap)
+    model.hip_training = True
+    try:
+        s.training_step = 5
+        pos, dirs = s.sample(None, _t(o), _t(d), is_training=True)
+    finally:
+        model.hip_training = False
+    assert int(s._counter[1]) == total and s.measured_batch_size == total and pos.shape == (cap, 3) and dirs.shape == (cap, 3)
+    got = s._coords.cpu().numpy()
+    assert got.shape == (cap, 7) and got.tobytes() == np.ascontiguousarray(coords[:cap]).tobytes()
+    assert np.unique(got[:, 3]).size > 100
+    assert np.array_equal(s._rays_numsteps.cpu().numpy(), ns)
+    n, base = ns[:, 0].astype(np.int64), ns[:, 1].astype(np.int64)
+    want = np.minimum(cap - np.minimum(cap, base), n)
+    assert np.array_equal(s._rays_numsteps_compacted.cpu().numpy(), np.stack([want, base], 1))
+    assert (want < n).any() and int(want.sum()) == cap
 
 
 def test_sampler_training_bookkeeping(setup):

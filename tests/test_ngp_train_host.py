@@ -1,5 +1,8 @@
 """Host-side checks of Instant-NGP training (no GPU): the references of tests/ngp_train_common.py against the project's CPU oracle and against finite
-differences, and the plain-torch pieces of jittor_myc_nerfs_amd.ngp_train (Huber, ExpDecay, EMA, the ray-count update, the data's rays, the checkpoint)."""
+differences, and the plain-torch pieces of jittor_myc_nerfs_amd.ngp_train (Huber, ExpDecay, EMA, the ray-count update, the data's rays, the checkpoint).
+Also the compositor tests' inputs with a step size per row: that they meet the conditions the GPU tests lean on, that the constant-dt inputs cannot see a
+kernel reading the wrong row's dt, and that on the new inputs each of six restated defects exceeds a GPU bar at least tenfold."""
+import functools
 import os
 import sys
 
@@ -149,6 +152,136 @@ def test_designed_inputs_keep_break_decisions_off_the_threshold():
         assert margin[np.isfinite(margin)].min() >= min(F.MARGIN, 0.495 * F.designed_tau(k))      # tau / 2 either side of the break by design
         loop = K.composite_loop(full, coords, ns, total, np.tile(np.float32(F.BG), (ns.shape[0], 1)), np.float64)
         assert np.array_equal(loop["stop"], np.where(brk >= 0, brk, ns[:, 0]))
+
+
+# --------------------------------------------------------------------------------------------------------------- per-row step sizes
+def _decisions(ref, r32, keep):
+    """(T fp64, T fp32 as fp64) in front of every `T < 1e-4` test the loop makes on a compared ray: samples 0 .. stop (the breaking test included)."""
+    j = np.arange(ref["T_seen"].shape[1])[None, :]
+    dec = (j <= ref["stop"][:, None]) & (j < ref["nc"][:, None]) & keep[:, None]
+    return ref["T_seen"][dec], r32["T_seen"][dec].astype(np.float64)
+
+
+def _dt_spread(coords, ns, n_rows):
+    """(distinct values of column 3, share of the rays with more than one step whose max dt / min dt exceeds 1.2) over the rows the capacity keeps."""
+    idx, valid, _, nc = K.ray_rows(torch.as_tensor(np.asarray(ns, np.int64)), n_rows)
+    idx, valid, nc = idx.numpy(), valid.numpy(), nc.numpy()
+    dt = np.asarray(K.unwarp_dt_t(torch.as_tensor(np.ascontiguousarray(coords[:n_rows, 3]))).numpy(), np.float64)[idx]
+    many = nc > 1
+    ratio = np.where(valid, dt, -np.inf).max(1)[many] / np.where(valid, dt, np.inf).min(1)[many]
+    return np.unique(coords[:n_rows, 3]).size, float((ratio > 1.2).mean())
+
+
+def test_per_row_dt_inputs_meet_their_conditions():
+    """The two inputs that give every row its own dt (ngp_train_common: "compositor cases") meet what the GPU tests lean on.  Measured (fp64 and fp32 loops on
+    the CPU), random-dt ladder, seed 300: 29 508 distinct dt, every multi-step ray with max / min dt > 1.2; left out 0, 0, 0, 1, 0 of 421 rays for k = 1, 2, 33,
+    97, 1000; breaks at 9 distinct samples (8..16) for k = 33 and at 12 (27..38) for k = 97; the fp32 loop's T differs from the fp64 loop's by 9.9e-7 / 1.4e-6 /
+    1.5e-6 (k = 33 / 97 / 1000) at the decisions, 1/1000 of the margin 1e-3 or less.  For k = 1 and 2 ONE step takes T from 1 to about the threshold, so 1 - alpha
+    cancels: its fp32 rounding (3e-8) is 3e-4 of the threshold (measured 7.3e-5 and 3.0e-4) and `1e-3 >= 20 x` cannot hold there at any seed; what holds, and what
+    keeps a decision from flipping, is asserted for every scene: each decision lies at least 20 x farther from the threshold than the two loops lie apart at
+    that decision (measured: 431 x at the least, k = 2).  Cone rows of the shared scene: 35 923 rows, 35 727 distinct dt (warped 0.069..0.205), 5 of 1024 rays
+    left out, 302 rays break; the 40 x 40 CONE_POSE frame: 55 985 rows, 10 rays left out."""
+    thr = K.THR
+    for k in K.SCENES:
+        for cap_kind in K.CAP_KINDS:
+            out, coords, ns, bg, g, n_rows, ref, r32, keep = K.designed_case(k, cap_kind, "random")
+            total = K.designed_inputs(k, "random")[5]["total"]
+            distinct, spread = _dt_spread(coords, ns, min(n_rows, total))
+            assert distinct > 100 and spread >= 0.5
+            assert (~keep).mean() <= K.LEFT_OUT_SHARE
+            assert np.array_equal(ref["stop"][keep], r32["stop"][keep])
+            t64, t32 = _decisions(ref, r32, keep)
+            # the two loops' distance at a decision: |d ln T| where T >= 1e-4, in units of the threshold below it (an fp32 T of exactly 0 has no logarithm)
+            err = np.abs(t32 - t64) / np.maximum(t64, thr)
+            margin = np.abs(np.log(np.maximum(t64, 1e-300) / thr))
+            headroom = float((margin / np.maximum(err, 1e-300)).min())
+            broke = ref["stop"] < ref["nc"]
+            at = np.unique(ref["stop"][broke])
+            print(f"random-dt ladder k={k} {cap_kind}: {distinct} distinct dt, spread share {spread:.2f}, {(~keep).sum()} of {keep.size} rays left out, breaks at "
+                  f"{at.size} samples ({at.min(initial=1 << 30)}..{at.max(initial=-1)}), max |ln T_fp32 - ln T_fp64| at the decisions {err.max():.2e}, "
+                  f"smallest margin / error {headroom:.0f}")
+            assert margin.min() >= K.RANDOM_DT_MARGIN and headroom >= 20
+            if k >= 33:                                              # no single step cancels 1 - alpha (docstring): the margin is 20 x the loops' distance outright
+                assert K.RANDOM_DT_MARGIN >= 20 * err.max()
+            if k in (33, 97):
+                assert at.size >= 3
+    for const_dt, what in ((False, "cone rows, shared scene"),):
+        coords, ns, out, bg, g, keep = K.scene_inputs(const_dt)
+        total = coords.shape[0]
+        for n_rows in K.scene_capacities(total, const_dt).values():
+            distinct, spread = _dt_spread(coords, ns, n_rows)
+            ref = K.composite_loop(out[:n_rows], coords[:n_rows], ns, n_rows, bg, np.float64)
+            r32 = K.composite_loop(out[:n_rows], coords[:n_rows], ns, n_rows, bg, np.float32)
+            t64, t32 = _decisions(ref, r32, keep)
+            err = np.abs(t32 - t64) / np.maximum(t64, thr)
+            print(f"{what} n_rows={n_rows}: {distinct} distinct dt (warped {coords[:, 3].min():.3f}..{coords[:, 3].max():.3f}), spread share {spread:.2f}, "
+                  f"{(~keep).sum()} of {keep.size} rays left out, {(ref['stop'] < ref['nc']).sum()} break, raw density max {out[:, 3].max():.1f}, "
+                  f"max |ln T_fp32 - ln T_fp64| at the decisions {err.max():.2e} (network shift {F.network_shift(out):.2e})")
+            assert distinct > 100 and spread >= 0.5
+            assert (~keep).mean() <= K.LEFT_OUT_SHARE
+            assert np.array_equal(ref["stop"][keep], r32["stop"][keep])
+            assert F.network_shift(out) >= 20 * err.max()
+        assert coords[:, 3].max() > 2 * coords[:, 3].min() > 0
+    # the cone-stepping frame of test_gpu_ngp_frame.py, for the record: the same rule leaves out as few
+    from oracle import ngp_oracle as N
+    levels, arrs = K.scene_rows(False)[:2]
+    o, d = ngp_camera_rays(F.CONE_WH, F.CONE_WH, pose_index=F.CONE_POSE)
+    coords, ns = F.oracle_rows(o, d, arrs["density_grid_bitfield"], NGP_AABB_SCALE, const_dt=False)
+    out = N.network_c(levels, arrs, coords)
+    _, brk, margin, _ = F.composite_f64(out, coords, ns, F.BG)
+    left = margin < F.network_shift(out)
+    print(f"cone frame {F.CONE_WH} x {F.CONE_WH}: {coords.shape[0]} rows, {(brk >= 0).sum()} break, {left.sum()} of {left.size} rays left out")
+    assert left.mean() <= K.LEFT_OUT_SHARE
+
+
+def test_constant_dt_inputs_cannot_see_dt_defects():
+    """Why the per-row-dt inputs exist: on the constant-dt ladder and the constant-dt shared scene every row holds one dt, so a loop that takes dt from the
+    ray's first row, from the next row, or whose gradient uses a stale dt gives the unmutated loop's bytes.  The suite was blind to all three."""
+    cases = [f"ladder-const-k{k}-total" for k in K.SCENES] + ["ladder-const-k33-inside", "ladder-const-k97-slack", "shared-total", "shared-cut"]
+    for name in cases:
+        out, coords, ns, bg, g, n_rows, _ = K.compositor_case(name)
+        assert np.unique(coords[:min(n_rows, int(ns[:, 0].sum())), 3]).size == 1
+        ref = K.composite_loop(out, coords, ns, n_rows, bg, np.float64, grad_rgb=g)
+        for mutation in ("dt_first_row", "dt_next_row", "dt_backward_stale"):
+            m = K.composite_loop(out, coords, ns, n_rows, bg, np.float64, grad_rgb=g, mutation=mutation)
+            assert all(m[key].tobytes() == ref[key].tobytes() for key in ("rgb", "stop", "grad", "T_end")), (name, mutation)
+
+
+@functools.lru_cache(maxsize=None)
+def _power_reference(name):
+    case = K.compositor_case(name)
+    out, coords, ns, bg, g, n_rows, _ = case
+    return case, K.composite_loop(out, coords, ns, n_rows, bg, np.float64, grad_rgb=g), K.composite_loop(out, coords, ns, n_rows, bg, np.float32, grad_rgb=g)
+
+
+@pytest.mark.parametrize("name,mutation", K.COMPOSITOR_POWER)
+def test_compositor_bars_have_power(name, mutation):
+    """Each defect, restated in the fp64 loop, against the true fp64 loop by the GPU tests' own measures: the forward L-inf on the compared rays (bar 2e-5), the
+    scaled backward error on their composited rows (bar max(4 e32, 1e-6), e32 from the unmutated fp32 loop on the same case) and the rows that must be exactly
+    0 (bar: none; ten such rows count as 10 x).  One of them is exceeded at least tenfold.  Measured, error / bar:
+      dt_first_row               cone-total forward 5.1e3, backward 1.9e4; ladder-random-k33-total 4.3e3, 7.0e4
+      dt_next_row                cone-total forward 1.6e3, backward 1.3e4; ladder-random-k33-total 1.2e3, 1.2e5
+      dt_backward_stale          forward 0 everywhere (the forward is untouched); backward 5.3e4 (cone-total), 1.8e5 (ladder-random-k33-total)
+      suffix_without_background  backward 2.5e5 (cone-total), 6.2e4 (ladder-random-k1000-total)
+      background_when_cut        forward 5.0e4 (cone-cut, ladder-random-k97-inside)
+      stop_one_late              215 (cone-total) and 380 (ladder-random-k33-total) rows behind a break written; backward 14 and 67; forward 2.6 and 1.9 only."""
+    case, ref, r32 = _power_reference(name)
+    out, coords, ns, bg, g, n_rows, keep = case
+    assert (~keep).mean() <= K.LEFT_OUT_SHARE
+    m = K.composite_loop(out, coords, ns, n_rows, bg, np.float64, grad_rgb=g, mutation=mutation)
+    clean = K.compositor_measures(case, ref["rgb"], ref["grad"], ref, r32)
+    moved = K.compositor_measures(case, m["rgb"], m["grad"], ref, r32)
+    assert clean["forward"] == 0 and clean["backward"] == 0 and clean["dead_nonzero"] == 0
+    ratios = dict(forward=moved["forward"] / K.FORWARD_BAR, backward=moved["backward"] / K.backward_bar(moved["e32"]), dead_rows=float(moved["dead_nonzero"]))
+    print(f"power {mutation} on {name}: error / bar forward {ratios['forward']:.3g}, backward {ratios['backward']:.3g} (e32 {moved['e32']:.2e}), "
+          f"{moved['dead_nonzero']} of {moved['dead_rows']} dead rows written")
+    assert max(ratios.values()) >= 10, (name, mutation, ratios)
+
+
+def test_every_compositor_mutation_is_proven_on_some_case():
+    assert {m for _, m in K.COMPOSITOR_POWER} == set(K.COMPOSITOR_MUTATIONS)
+    for name, _ in K.COMPOSITOR_POWER:                                  # on the inputs with a dt per row, which the GPU tests run
+        assert name.split("-")[0] == "cone" or name.startswith("ladder-random-")
 
 
 def test_huber_expdecay_ema_and_batch_rays():
