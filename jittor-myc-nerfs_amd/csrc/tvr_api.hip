@@ -1,8 +1,8 @@
-// tvr_api.hip — the C-ABI of libtvr.so (include/tvr.h) for scenes, rendering, training, the dense linear algebra, profiling and tvr_mesh_project (the one mesh call
-// that reads a scene); every other tvr_mesh_* entry point is in tvr_mesh_api.hip, the NGP and background-network ones beside their kernels.  Host code only:
+// tvr_api.hip — the C-ABI of libtvr.so (include/tvr.h) for scenes, rendering, the training marches' forward (tvr_march_forward(_z)), ray filtering, field queries,
+// profiling and tvr_mesh_project (the one mesh call that reads a scene); the training entry points and the dense linear algebra are in tvr_train_api.hip, every
+// other tvr_mesh_* entry point in tvr_mesh_api.hip, the NGP and background-network ones beside their kernels.  Host code only (but maxdiff_kernel):
 // argument checks, packed-scene layout, scratch carving and kernel launches on the caller's stream.  No device allocation, no synchronisation.
-#include "tvr_device.h"
-#include "tvr_host.h"
+#include "tvr_scene.h"
 
 #include <cstdarg>
 #include <cstdlib>
@@ -20,16 +20,6 @@ int tvr_set_error(int code, const char *fmt, ...)
     va_end(ap);
     return code;
 }
-
-static const int kMatH[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-static const int kVecH[3] = {2, 1, 0};
-
-struct PackedLayout {
-    size_t dplane[3], dline[3], aplane[3], aline[3];
-    size_t aplane16[3], aline16[3];            // fp16 copies of the appearance factors (TVR_ARITH_F16's gather), floats / 2
-    size_t mlp_image, basis_frag, b3, w1gen, img16, basg16, refg16, total;
-    size_t cp_basis;                           // CP scenes: basis_mat as [ra / 4][27] float4 (CpDev::basis)
-};
 
 static PackedLayout packed_layout(const tvr_scene_desc &d)
 {
@@ -89,36 +79,6 @@ static PackedLayout cp_packed_layout(const tvr_scene_desc &d)
     L.total = off;
     return L;
 }
-
-struct tvr_scene {
-    bool cp;                   // a CP scene (tvr_cp_scene_create): dev.dline / dev.aline hold the CP lines, `cpd` the rest; default arithmetic only; trains through tvr_cp_* only
-    CpDev cpd;
-    tvr_scene_desc desc;
-    PackedLayout lay;
-    char *packed;
-    SceneDev dev;
-    bool params_set;
-    bool h16_stale;            // the fp16 copies of the appearance factors are older than the fp32 images
-    int arith_req;             // what tvr_scene_set_arith asked for; dev.arith is what the kernels RUN: arith_req once tvr_scene_validate_arith has measured it inside
-    int arith_valid;           // its tolerance for the parameters as packed (0 = nothing validated), TVR_ARITH_F32 until then
-    // piecewise rendering (round 6, tvr_scene_set_render_pieces): a tvr_render(_z) call of at least 2 x piece_rays rays goes out as pieces of ~piece_rays consecutive rays,
-    // alternately on two library-owned streams that fork from and join the caller's stream by events
-    int piece_rays;
-    hipStream_t side[2];
-    hipEvent_t ev_fork, ev_join[2];
-    bool side_ready;
-    // the baked density volume (tvr_scene_set_density_volume): the caller's memory; `dvol_stale`: the packed density factors are newer than the volume — the next call
-    // that launches the render march bakes first, on ITS stream, and records ev_dvol; a later call on another stream waits on that event (ensure_dvol)
-    float *dvol;
-    bool dvol_stale, dvol_recorded;
-    hipStream_t dvol_stream;
-    hipEvent_t ev_dvol;
-    // the baked appearance volume (tvr_scene_set_appearance_volume): the same rules for the render shade (ensure_fvol)
-    float4 *fvol;
-    bool fvol_stale, fvol_recorded;
-    hipStream_t fvol_stream;
-    hipEvent_t ev_fvol;
-};
 
 struct tvr_profile {
     std::vector<hipEvent_t> ev;   // 4 per recorded launch set (one per call; one per PIECE of a call rendered piecewise)
@@ -202,25 +162,11 @@ size_t tvr_scene_packed_bytes(const tvr_scene_desc *desc)
 
 }  // extern "C"
 
-// entry points a CP scene does not have (training, explicit depths, REFTensoRF's calls, the reduced arithmetics): refused before anything is launched
-static int cp_refused(const tvr_scene *s, const char *fn)
-{
-    if (s && s->cp) return fail(TVR_ERR_UNSUPPORTED, "%s: the scene is a CP scene (tvr_cp_scene_create) — CP scenes render and answer field queries in the default arithmetic; "
-                                                     "training, explicit depths, the _ref calls and the reduced arithmetics are not built for CP", fn);
-    return TVR_OK;
-}
-#define NOT_CP(s)                                        \
-    do {                                                 \
-        int rcp_ = cp_refused((s), __func__);            \
-        if (rcp_ != TVR_OK) return rcp_;                 \
-    } while (0)
-
 static int scene_create_impl(const tvr_scene_desc *desc, void *packed_dev, size_t packed_bytes, tvr_scene **out, bool cp)
 {
     if (!out) return fail(TVR_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    int rc = check_desc(desc, cp);
-    if (rc != TVR_OK) return rc;
+    TRY(check_desc(desc, cp));
     PackedLayout L = cp ? cp_packed_layout(*desc) : packed_layout(*desc);
     if (!packed_dev || packed_bytes < L.total) return fail(TVR_ERR_SCRATCH, "packed buffer %zu B < required %zu B", packed_bytes, L.total);
     if ((uintptr_t)packed_dev % 256) return fail(TVR_ERR_SCRATCH, "packed buffer must be 256-byte aligned");
@@ -233,24 +179,7 @@ static int scene_create_impl(const tvr_scene_desc *desc, void *packed_dev, size_
     s->desc = *desc;
     s->lay = L;
     s->packed = (char *)packed_dev;
-    s->params_set = false;
-    s->h16_stale = true;
-    s->arith_req = TVR_ARITH_F32;
-    s->arith_valid = 0;
     s->piece_rays = default_piece_rays();
-    s->side[0] = s->side[1] = nullptr;
-    s->ev_fork = s->ev_join[0] = s->ev_join[1] = nullptr;
-    s->side_ready = false;
-    s->dvol = nullptr;
-    s->dvol_stale = true;
-    s->dvol_recorded = false;
-    s->dvol_stream = nullptr;
-    s->ev_dvol = nullptr;
-    s->fvol = nullptr;
-    s->fvol_stale = true;
-    s->fvol_recorded = false;
-    s->fvol_stream = nullptr;
-    s->ev_fvol = nullptr;
     SceneDev &v = s->dev;
     memset(&v, 0, sizeof(v));
     for (int k = 0; k < 3; ++k) {
@@ -598,32 +527,6 @@ int tvr_scene_set_appearance_volume(tvr_scene *s, void *buf, size_t bytes, void 
     return TVR_OK;
 }
 
-// scratch carving shared by the size query and tvr_render
-#define TVR_RAY_ORDER_MAX_RAYS 65536      // march_forward_impl: batches up to this many rays get a ray-ordered queue
-struct ScratchLayout { size_t counter, ray_off, ray_cnt, acc, q_pos, q_out, q_ray, q_j, ray_new, cp_feat, cp_dir, cp_rgb, total; };
-static ScratchLayout scratch_layout(int64_t n_rays, int32_t S, bool cp = false)
-{
-    ScratchLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t cap = (size_t)n_rays * (size_t)S;
-    L.counter = take(256);
-    L.ray_off = take(n_rays * 4);
-    L.ray_cnt = take(n_rays * 4);
-    L.acc = take(n_rays * 4);
-    L.q_pos = take(cap * 16);
-    L.q_out = take(cap * 16);
-    L.q_ray = take(cap * 4);
-    L.q_j = take(cap * 4);
-    L.ray_new = take(n_rays * 4);          // the training queue's ray-ordered offsets (launch_queue_ray_order); behind everything the public layout names
-    // a CP scene's render stages per queue entry what its feature kernel hands the network: features [cap,27], view direction [cap,3], colour [cap,3] (132 B more per entry)
-    L.cp_feat = cp ? take(cap * TVR_APPDIM * 4) : 0;
-    L.cp_dir = cp ? take(cap * 12) : 0;
-    L.cp_rgb = cp ? take(cap * 12) : 0;
-    L.total = off;
-    return L;
-}
-
 // Piecewise rendering: a call of n rays goes out as K = round(n / piece_rays) pieces of ceil(n / K) rays rounded up to 512 (the last one shorter), if that makes at least
 // TVR_MIN_PIECES.  Measured on one box (bench.py --emulate-world N --pieces P, profiles/r06_split_frame.txt): the 640 000-ray frame -3.6 % .. -4.6 %, a 320 000-ray share
 // -4.6 %, a 160 000-ray share +-0.5 %, an 80 000-ray share +0.9 % (two or three pieces do not settle into the overlap that pays): small calls stay one launch set.
@@ -669,15 +572,7 @@ size_t tvr_render_scratch_bytes_min(const tvr_scene *s, int64_t n_rays, int32_t 
 static int render_one(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, int32_t white_bg, const MarchSampling &sm, float eps_T, float *rgb_out, float *depth_out,
                       float *lam6_out, char *b, const ScratchLayout &L, const tvr_dense_out *dense, uint64_t *stats, hipEvent_t *ev, hipStream_t stream)
 {
-    MarchOut mo;
-    mo.counter = (unsigned *)(b + L.counter);
-    mo.ray_off = (unsigned *)(b + L.ray_off);
-    mo.ray_cnt = (unsigned *)(b + L.ray_cnt);
-    mo.acc = (float *)(b + L.acc);
-    mo.depth = depth_out;
-    mo.q_pos = (float4 *)(b + L.q_pos);
-    mo.q_out = (float4 *)(b + L.q_out);
-    mo.q_ray = (unsigned *)(b + L.q_ray);
+    MarchOut mo = carve_scratch(b, L, depth_out);
     mo.q_j = (dense && dense->rgb) ? (unsigned *)(b + L.q_j) : nullptr;
     mo.stats = (unsigned long long *)stats;
     mo.lam6 = lam6_out;
@@ -760,15 +655,10 @@ static int render_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     if ((uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "scratch must be 256-byte aligned");
     if (prof && prof->n_calls >= prof->max_calls) return fail(TVR_ERR_INVALID, "profile is full (%d calls)", prof->max_calls);
     hipStream_t stream = (hipStream_t)stream_;
-    if (s->dev.arith == TVR_ARITH_F16 && !s->dev.gen && s->h16_stale) {        // the mode was set after the last tvr_scene_update
-        int rc16 = refresh_h16(s, stream);
-        if (rc16 != TVR_OK) return rc16;
-    }
+    if (s->dev.arith == TVR_ARITH_F16 && !s->dev.gen && s->h16_stale) TRY(refresh_h16(s, stream));        // the mode was set after the last tvr_scene_update
     if (!s->cp) {                          // the density volume, if one is attached: current, and this stream behind its bake, before anything forks
-        int rcv = ensure_dvol(s, stream);
-        if (rcv != TVR_OK) return rcv;
-        if (s->dev.arith == TVR_ARITH_F32) rcv = ensure_fvol(s, stream);          // (the reduced arithmetics shade on the factored kernels: nothing to bake for them)
-        if (rcv != TVR_OK) return rcv;
+        TRY(ensure_dvol(s, stream));
+        if (s->dev.arith == TVR_ARITH_F32) TRY(ensure_fvol(s, stream));          // (the reduced arithmetics shade on the factored kernels: nothing to bake for them)
     }
     // the per-sample outputs of `dense` are a debugging / parity surface ([n,S,*] arrays): such calls stay one launch set
     const PiecePlan P = dense ? PiecePlan{1, n_rays} : piece_plan(s, n_rays);
@@ -833,33 +723,6 @@ int tvr_render_z(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, int
     return render_impl(s, rays, n_rays, S, white_bg, sm, eps_T, rgb_out, depth_out, t_last_tiny_out, scratch, scratch_bytes, dense, stats, nullptr, stream);
 }
 
-}  // extern "C"
-
-static int scene_ready(const tvr_scene *s)
-{
-    if (!s || !s->params_set) return fail(TVR_ERR_INVALID, "scene is NULL or tvr_scene_update has not run");
-    return TVR_OK;
-}
-
-static MarchOut carve_scratch(char *b, const ScratchLayout &L, float *depth_out)
-{
-    MarchOut mo;
-    mo.counter = (unsigned *)(b + L.counter);
-    mo.ray_off = (unsigned *)(b + L.ray_off);
-    mo.ray_cnt = (unsigned *)(b + L.ray_cnt);
-    mo.acc = (float *)(b + L.acc);
-    mo.depth = depth_out;
-    mo.q_pos = (float4 *)(b + L.q_pos);
-    mo.q_out = (float4 *)(b + L.q_out);
-    mo.q_ray = (unsigned *)(b + L.q_ray);
-    mo.q_j = nullptr;
-    mo.stats = nullptr;
-    mo.lam6 = nullptr;
-    return mo;
-}
-
-extern "C" {
-
 int tvr_scratch_describe(int64_t n_rays, int32_t n_samples, tvr_scratch_layout *out)
 {
     if (!out || n_rays <= 0 || n_samples <= 0) return fail(TVR_ERR_INVALID, "bad arguments");
@@ -871,18 +734,15 @@ int tvr_scratch_describe(int64_t n_rays, int32_t n_samples, tvr_scratch_layout *
 
 }  // extern "C"
 
-static int march_forward_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const MarchSampling &sm, float eps_T, float *depth_out,
-                              float *lam6_out, void *scratch, size_t scratch_bytes, void *stream_)
+// (declared in tvr_scene.h: tvr_train_api.hip's tvr_train_forward begins with this march)
+int march_forward_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const MarchSampling &sm, float eps_T, float *depth_out,
+                       float *lam6_out, void *scratch, size_t scratch_bytes, void *stream_)
 {
     NOT_CP(s);
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
+    TRY(scene_ready(s));
     if (!rays || !depth_out || n_rays <= 0) return fail(TVR_ERR_INVALID, "rays/depth_out NULL or n_rays <= 0");
-    if (S <= 0 || S > 4096) return fail(TVR_ERR_INVALID, "n_samples=%d out of [1,4096]", S);
-    if ((size_t)n_rays * (size_t)S >= (1ull << 32)) return fail(TVR_ERR_INVALID, "n_rays*n_samples must be < 2^32 per call");
-    if (!(eps_T >= 0.0f) || eps_T > s->desc.weight_thres) return fail(TVR_ERR_INVALID, "eps_T=%g must be in [0, weight_thres]", eps_T);
+    TRY(march_args_ok(s, n_rays, S, eps_T, scratch, scratch_bytes, "scratch too small (%zu < %zu) or misaligned"));
     ScratchLayout L = scratch_layout(n_rays, S);
-    if (!scratch || scratch_bytes < L.total || (uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "scratch too small (%zu < %zu) or misaligned", scratch_bytes, L.total);
     hipStream_t stream = (hipStream_t)stream_;
     MarchOut mo = carve_scratch((char *)scratch, L, depth_out);
     mo.lam6 = lam6_out;
@@ -994,724 +854,6 @@ int tvr_filter_rays(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, 
     if (mask_bytes < (size_t)n_rays) return fail(TVR_ERR_SCRATCH, "mask holds fewer than n_rays bytes");
     if (!bbox_only && !s->dev.avol) return fail(TVR_ERR_INVALID, "the scene has no alpha mask (tvr_scene_set_alpha): only bbox_only filtering is defined");
     HIP_TRY(launch_filter_rays(s->dev, rays, n_rays, S, bbox_only ? 1 : 0, mask, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-size_t tvr_grad_scratch_bytes(const tvr_scene *s)
-{
-    if (!s) return 0;
-    if (cp_refused(s, __func__) != TVR_OK) return 0;
-    return s->lay.mlp_image;      // the VM blocks come first in the packed layout; the gradient images mirror them
-}
-
-static TrainGrads carve_grads(const tvr_scene *s, char *g)
-{
-    TrainGrads tg;
-    for (int i = 0; i < 3; ++i) {
-        tg.dplane[i] = (float *)(g + s->lay.dplane[i]);
-        tg.dline[i] = (float *)(g + s->lay.dline[i]);
-        tg.aplane[i] = (float *)(g + s->lay.aplane[i]);
-        tg.aline[i] = (float *)(g + s->lay.aline[i]);
-    }
-    return tg;
-}
-
-}  // extern "C"
-
-static int march_backward_impl(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const MarchSampling &sm, float eps_T, const void *fwd_scratch,
-                               size_t fwd_scratch_bytes, const float *grad_w, const float *grad_acc, const float *lam6, const float *grad_lam6,
-                               void *grad_scratch, size_t grad_scratch_bytes, const tvr_vm_grads *out, void *stream_, long long gw_cap = -1)
-{
-    NOT_CP(s);
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    if (!rays || !fwd_scratch || !grad_w || !grad_acc || !grad_scratch || !out || n_rays <= 0) return fail(TVR_ERR_INVALID, "NULL argument");
-    ScratchLayout L = scratch_layout(n_rays, S);
-    if (fwd_scratch_bytes < L.total) return fail(TVR_ERR_SCRATCH, "forward scratch %zu B < %zu B", fwd_scratch_bytes, L.total);
-    if (grad_scratch_bytes < s->lay.mlp_image || (uintptr_t)grad_scratch % 256) return fail(TVR_ERR_SCRATCH, "gradient scratch too small or misaligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    const tvr_scene_desc &d = s->desc;
-    char *g = (char *)grad_scratch;
-    TrainGrads tg = carve_grads(s, g);
-    for (int i = 0; i < 3; ++i) {
-        const size_t W = d.grid[kMatH[i][0]], H = d.grid[kMatH[i][1]], Ln = d.grid[kVecH[i]];
-        HIP_TRY(launch_zero_f32(tg.dplane[i], (long long)((H + 1) * (W + 1) * TVR_CD), stream));       // (channel counts are multiples of 4, blocks 256-B aligned)
-        HIP_TRY(launch_zero_f32(tg.dline[i], (long long)((Ln + 1) * TVR_CD), stream));
-    }
-    MarchOut mo = carve_scratch((char *)fwd_scratch, L, nullptr);
-    HIP_TRY(launch_march_backward(s->dev, rays, (int)n_rays, S, sm, eps_T, mo, grad_w, grad_acc, lam6, grad_lam6, tg, stream, gw_cap));
-    for (int i = 0; i < 3; ++i) {
-        if (!out->density_plane[i] || !out->density_line[i]) return fail(TVR_ERR_INVALID, "density gradient pointer %d is NULL", i);
-        const int W = d.grid[kMatH[i][0]], H = d.grid[kMatH[i][1]], Ln = d.grid[kVecH[i]];
-        HIP_TRY(launch_unpack_grad(tg.dplane[i], out->density_plane[i], s->desc.density_n_comp[i], TVR_CD, H, W, stream));
-        HIP_TRY(launch_unpack_grad(tg.dline[i], out->density_line[i], s->desc.density_n_comp[i], TVR_CD, Ln, 1, stream));
-    }
-    return TVR_OK;
-}
-
-extern "C" {
-
-int tvr_march_backward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, const void *fwd_scratch,
-                       size_t fwd_scratch_bytes, const float *grad_w, const float *grad_acc, void *grad_scratch, size_t grad_scratch_bytes,
-                       const tvr_vm_grads *out, void *stream)
-{
-    const MarchSampling sm = {jitter, nullptr};
-    return march_backward_impl(s, rays, n_rays, S, sm, eps_T, fwd_scratch, fwd_scratch_bytes, grad_w, grad_acc, nullptr, nullptr, grad_scratch,
-                               grad_scratch_bytes, out, stream);
-}
-
-int tvr_march_backward_z(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *z_vals, float eps_T, const void *fwd_scratch,
-                         size_t fwd_scratch_bytes, const float *grad_w, const float *grad_acc, const float *t_last_tiny,
-                         const float *grad_t_last_tiny, void *grad_scratch, size_t grad_scratch_bytes, const tvr_vm_grads *out, void *stream)
-{
-    if (!z_vals) return fail(TVR_ERR_INVALID, "z_vals is NULL");
-    if ((t_last_tiny == nullptr) != (grad_t_last_tiny == nullptr)) return fail(TVR_ERR_INVALID, "t_last_tiny and its gradient go together");
-    const MarchSampling sm = {nullptr, z_vals};
-    return march_backward_impl(s, rays, n_rays, S, sm, eps_T, fwd_scratch, fwd_scratch_bytes, grad_w, grad_acc, t_last_tiny, grad_t_last_tiny,
-                               grad_scratch, grad_scratch_bytes, out, stream);
-}
-
-int tvr_app_h_forward(tvr_scene *s, const float *xyz, int64_t m, float *h_out, size_t h_bytes, void *stream)
-{
-    NOT_CP(s);
-    if (m > 0) NEED("h_out [m,144]", h_bytes, m, TVR_KAPP);
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    if (m == 0) return TVR_OK;
-    if (!xyz || !h_out || m < 0) return fail(TVR_ERR_INVALID, "xyz/h_out NULL or m < 0");
-    HIP_TRY(launch_app_h_forward(s->dev, xyz, m, h_out, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-size_t tvr_mlp_train_image_bytes(void) { return mlp_train_image_bytes(); }
-
-static int mlp_train_forward_impl(tvr_scene *s, int variant, const float *h, const float *viewdirs, int64_t m, float *rgb, size_t rgb_bytes, float *feats32,
-                                  size_t feats32_bytes, float *h1, size_t h1_bytes, float *h2, size_t h2_bytes, float *g8, size_t g8_bytes, float *rgb_s, size_t rgb_s_bytes,
-                                  void *stream)
-{
-    const char *fn = variant ? "tvr_mlp_train_forward_ref" : "tvr_mlp_train_forward";
-    { int rcp = cp_refused(s, fn); if (rcp != TVR_OK) return rcp; }
-    if (m > 0) {
-        int rc_;
-        if ((rc_ = need_bytes(fn, "rgb [m,3]", rgb_bytes, m, 3)) != TVR_OK) return rc_;
-        if ((rc_ = need_bytes(fn, "feats32 [m,32]", feats32_bytes, m, 32)) != TVR_OK) return rc_;
-        if ((rc_ = need_bytes(fn, "h1 [m,128]", h1_bytes, m, TVR_FEATC)) != TVR_OK) return rc_;
-        if ((rc_ = need_bytes(fn, "h2 [m,128]", h2_bytes, m, TVR_FEATC)) != TVR_OK) return rc_;
-        if (variant) {
-            if ((rc_ = need_bytes(fn, "g8 [m,8]", g8_bytes, m, 8)) != TVR_OK) return rc_;
-            if ((rc_ = need_bytes(fn, "rgb_s [m,3]", rgb_s_bytes, m, 3)) != TVR_OK) return rc_;
-        }
-        if ((uint64_t)m * 576u >= (1ull << 32)) return fail(TVR_ERR_INVALID, "m = %lld: 32-bit row offsets inside the kernels allow 7.4 M entries per call", (long long)m);
-    }
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    if (s->desc.variant != variant)
-        return fail(TVR_ERR_UNSUPPORTED, "%s: the scene is %s", fn, s->desc.variant ? "a REFTensoRF scene (tvr_mlp_train_forward_ref)" : "a TensorVMSplit scene (tvr_mlp_train_forward)");
-    {
-        const tvr_scene_desc &d = s->desc;
-        bool std_shape = d.featureC == TVR_FEATC && d.view_pe == 2 && d.fea_pe == 2;
-        for (int i = 0; i < 3; ++i) std_shape = std_shape && d.app_n_comp[i] == TVR_CA;
-        if (!std_shape) return fail(TVR_ERR_UNSUPPORTED, "%s: the fused training kernels take 48 appearance components, featureC 128, view_pe = fea_pe = 2 "
-                                                         "(zero-padded shapes train through the library-GEMM path)", fn);
-    }
-    if (m == 0) return TVR_OK;
-    if (!h || !viewdirs || !rgb || !feats32 || !h1 || !h2 || m < 0 || (variant && (!g8 || !rgb_s))) return fail(TVR_ERR_INVALID, "NULL argument or m < 0");
-    if (((uintptr_t)h | (uintptr_t)feats32 | (uintptr_t)h1 | (uintptr_t)h2 | (uintptr_t)g8) % 16) return fail(TVR_ERR_INVALID, "h / feats32 / h1 / h2 / g8 must be 16-byte aligned");
-    ShadeArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.n = m; sa.h_in = h; sa.viewdirs = viewdirs; sa.out = rgb; sa.t_feats = feats32; sa.t_h1 = h1; sa.t_h2 = h2; sa.t_g8 = g8; sa.t_rgbs = rgb_s;
-    HIP_TRY(launch_shade(s->dev, SH_SRC_H, SH_DST_TRAIN, sa, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_mlp_train_forward(tvr_scene *s, const float *h, const float *viewdirs, int64_t m, float *rgb, size_t rgb_bytes, float *feats32, size_t feats32_bytes,
-                          float *h1, size_t h1_bytes, float *h2, size_t h2_bytes, void *stream)
-{
-    return mlp_train_forward_impl(s, 0, h, viewdirs, m, rgb, rgb_bytes, feats32, feats32_bytes, h1, h1_bytes, h2, h2_bytes, nullptr, 0, nullptr, 0, stream);
-}
-
-int tvr_mlp_train_forward_ref(tvr_scene *s, const float *h, const float *viewdirs, int64_t m, float *rgb, size_t rgb_bytes, float *feats32, size_t feats32_bytes,
-                              float *h1, size_t h1_bytes, float *h2, size_t h2_bytes, float *g8, size_t g8_bytes, float *rgb_s, size_t rgb_s_bytes, void *stream)
-{
-    return mlp_train_forward_impl(s, 1, h, viewdirs, m, rgb, rgb_bytes, feats32, feats32_bytes, h1, h1_bytes, h2, h2_bytes, g8, g8_bytes, rgb_s, rgb_s_bytes, stream);
-}
-
-int tvr_mlp_train_backward(const float *W1, const float *W2, const float *W3, const float *basis, const float *grad_rgb, const float *rgb, const float *feats32,
-                           const float *h1, const float *h2, int64_t m, const float *gscale_dev, float *d_out4, size_t d_out4_bytes, float *dh2, size_t dh2_bytes,
-                           float *dh1, size_t dh1_bytes, float *dfeats32, size_t dfeats32_bytes, float *dh, size_t dh_bytes, uint32_t *sat_flag_dev,
-                           void *image, size_t image_bytes, void *stream)
-{
-    if (m == 0) return TVR_OK;
-    if (m > 0) {
-        NEED("d_out4 [m,4]", d_out4_bytes, m, 4);
-        NEED("dh2 [m,128]", dh2_bytes, m, TVR_FEATC);
-        NEED("dh1 [m,128]", dh1_bytes, m, TVR_FEATC);
-        NEED("dfeats32 [m,32]", dfeats32_bytes, m, 32);
-        NEED("dh [m,144]", dh_bytes, m, TVR_KAPP);
-    }
-    if (!W1 || !W2 || !W3 || !basis || !grad_rgb || !rgb || !feats32 || !h1 || !h2 || !gscale_dev || !d_out4 || !dh2 || !dh1 || !dfeats32 || !dh || !image || m < 0)
-        return fail(TVR_ERR_INVALID, "NULL argument or m < 0");
-    if (image_bytes < mlp_train_image_bytes() || (uintptr_t)image % 256) return fail(TVR_ERR_SCRATCH, "training image buffer too small or misaligned");
-    if ((uint64_t)m * 576u >= (1ull << 32)) return fail(TVR_ERR_INVALID, "m = %lld: 32-bit row offsets inside the kernels allow 7.4 M entries per call", (long long)m);
-    if (((uintptr_t)feats32 | (uintptr_t)h1 | (uintptr_t)h2 | (uintptr_t)d_out4 | (uintptr_t)dh2 | (uintptr_t)dh1 | (uintptr_t)dfeats32 | (uintptr_t)dh) % 16)
-        return fail(TVR_ERR_INVALID, "activation / gradient matrices must be 16-byte aligned");
-    HIP_TRY(launch_pack_train_image(W1, W2, W3, basis, nullptr, image, (hipStream_t)stream));
-    HIP_TRY(launch_mlp_train_backward(grad_rgb, rgb, feats32, h1, h2, m, gscale_dev, d_out4, dh2, dh1, dfeats32, dh, sat_flag_dev, image, nullptr, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_mlp_train_backward_ref(const float *W1, const float *W2, const float *W3, const float *basis, const float *const heads_W[4], const float *grad_rgb,
-                               const float *grad_in0, const float *rgb_s, const float *feats32, const float *h1, const float *h2, const float *g8, const float *viewdirs,
-                               int64_t m, const float *gscale_dev, float *d_out4, size_t d_out4_bytes, float *dh2, size_t dh2_bytes, float *dh1, size_t dh1_bytes,
-                               float *dfeats32, size_t dfeats32_bytes, float *dg8, size_t dg8_bytes, float *dh, size_t dh_bytes, uint32_t *sat_flag_dev, void *image,
-                               size_t image_bytes, void *stream)
-{
-    if (m == 0) return TVR_OK;
-    if (m > 0) {
-        NEED("d_out4 [m,4]", d_out4_bytes, m, 4);
-        NEED("dh2 [m,128]", dh2_bytes, m, TVR_FEATC);
-        NEED("dh1 [m,128]", dh1_bytes, m, TVR_FEATC);
-        NEED("dfeats32 [m,32]", dfeats32_bytes, m, 32);
-        NEED("dg8 [m,8]", dg8_bytes, m, 8);
-        NEED("dh [m,144]", dh_bytes, m, TVR_KAPP);
-    }
-    if (!W1 || !W2 || !W3 || !basis || !heads_W || !heads_W[0] || !heads_W[1] || !heads_W[2] || !heads_W[3] || !grad_rgb || !rgb_s || !feats32 || !h1 || !h2 || !g8 ||
-        !viewdirs || !gscale_dev || !d_out4 || !dh2 || !dh1 || !dfeats32 || !dg8 || !dh || !image || m < 0)
-        return fail(TVR_ERR_INVALID, "NULL argument or m < 0");
-    if (image_bytes < mlp_train_image_bytes() || (uintptr_t)image % 256) return fail(TVR_ERR_SCRATCH, "training image buffer too small or misaligned");
-    if ((uint64_t)m * 576u >= (1ull << 32)) return fail(TVR_ERR_INVALID, "m = %lld: 32-bit row offsets inside the kernels allow 7.4 M entries per call", (long long)m);
-    if (((uintptr_t)feats32 | (uintptr_t)h1 | (uintptr_t)h2 | (uintptr_t)g8 | (uintptr_t)d_out4 | (uintptr_t)dh2 | (uintptr_t)dh1 | (uintptr_t)dfeats32 | (uintptr_t)dg8 | (uintptr_t)dh) % 16)
-        return fail(TVR_ERR_INVALID, "activation / gradient matrices must be 16-byte aligned");
-    HIP_TRY(launch_pack_train_image(W1, W2, W3, basis, heads_W, image, (hipStream_t)stream));
-    MlpRefBwd rb;
-    rb.g8 = g8; rb.viewdirs = viewdirs; rb.grad_in0 = grad_in0; rb.dg8 = dg8; rb.rays = nullptr; rb.q_ray = nullptr;
-    HIP_TRY(launch_mlp_train_backward(grad_rgb, rgb_s, feats32, h1, h2, m, gscale_dev, d_out4, dh2, dh1, dfeats32, dh, sat_flag_dev, image, &rb, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-}  // extern "C"
-
-static int app_h_backward_impl(tvr_scene *s, const float *xyz, int xyz_stride, int64_t m, const unsigned *m_dev, const float *dh, void *grad_scratch,
-                               size_t grad_scratch_bytes, const tvr_vm_grads *out, void *stream_)
-{
-    NOT_CP(s);
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    if (!grad_scratch || !out || m < 0 || (m > 0 && (!xyz || !dh))) return fail(TVR_ERR_INVALID, "NULL argument");
-    if (grad_scratch_bytes < s->lay.mlp_image || (uintptr_t)grad_scratch % 256) return fail(TVR_ERR_SCRATCH, "gradient scratch too small or misaligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    const tvr_scene_desc &d = s->desc;
-    TrainGrads tg = carve_grads(s, (char *)grad_scratch);
-    for (int i = 0; i < 3; ++i) {
-        const size_t W = d.grid[kMatH[i][0]], H = d.grid[kMatH[i][1]], Ln = d.grid[kVecH[i]];
-        HIP_TRY(launch_zero_f32(tg.aplane[i], (long long)((H + 1) * (W + 1) * TVR_CA), stream));
-        HIP_TRY(launch_zero_f32(tg.aline[i], (long long)((Ln + 1) * TVR_CA), stream));
-    }
-    if (m > 0) HIP_TRY(launch_app_h_backward(s->dev, xyz, m, dh, tg, stream, xyz_stride, m_dev));
-    for (int i = 0; i < 3; ++i) {
-        if (!out->app_plane[i] || !out->app_line[i]) return fail(TVR_ERR_INVALID, "appearance gradient pointer %d is NULL", i);
-        const int W = d.grid[kMatH[i][0]], H = d.grid[kMatH[i][1]], Ln = d.grid[kVecH[i]];
-        HIP_TRY(launch_unpack_grad(tg.aplane[i], out->app_plane[i], s->desc.app_n_comp[i], TVR_CA, H, W, stream));
-        HIP_TRY(launch_unpack_grad(tg.aline[i], out->app_line[i], s->desc.app_n_comp[i], TVR_CA, Ln, 1, stream));
-    }
-    return TVR_OK;
-}
-
-// ---- CP training (include/tvr.h, CP TRAINING; csrc/tvr_cp_train.hip): entry points of their own beside the refusals above ----
-static int cp_required(const tvr_scene *s, const char *fn)
-{
-    if (!s) return fail(TVR_ERR_INVALID, "%s: scene is NULL", fn);
-    if (!s->cp) return fail(TVR_ERR_UNSUPPORTED, "%s: the scene is not a CP scene (tvr_cp_scene_create); TensorVMSplit / REFTensoRF scenes train through tvr_march_forward / "
-                                                 "_backward, tvr_app_h_* and tvr_train_*", fn);
-    return TVR_OK;
-}
-
-// the gradient images mirror the packed CP layout: dline[i] / aline[i] blocks, then the basis block ([27][ra] here), which ends where the network images begin
-struct CpGradImages { float *dline[3], *aline[3], *basis; };
-static CpGradImages cp_carve_grads(const tvr_scene *s, char *g)
-{
-    CpGradImages G;
-    for (int i = 0; i < 3; ++i) {
-        G.dline[i] = (float *)(g + s->lay.dline[i]);
-        G.aline[i] = (float *)(g + s->lay.aline[i]);
-    }
-    G.basis = (float *)(g + s->lay.cp_basis);
-    return G;
-}
-
-extern "C" {
-
-size_t tvr_cp_grad_scratch_bytes(const tvr_scene *s)
-{
-    if (cp_required(s, __func__) != TVR_OK) return 0;
-    return s->lay.mlp_image;
-}
-
-int tvr_cp_march_forward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, float *depth_out, void *scratch,
-                         size_t scratch_bytes, void *stream_)
-{
-    int rc = cp_required(s, __func__);
-    if (rc != TVR_OK) return rc;
-    rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    if (!rays || !depth_out || n_rays <= 0) return fail(TVR_ERR_INVALID, "rays/depth_out NULL or n_rays <= 0");
-    if (S <= 0 || S > 4096) return fail(TVR_ERR_INVALID, "n_samples=%d out of [1,4096]", S);
-    if ((size_t)n_rays * (size_t)S >= (1ull << 32)) return fail(TVR_ERR_INVALID, "n_rays*n_samples must be < 2^32 per call");
-    if (!(eps_T >= 0.0f) || eps_T > s->desc.weight_thres) return fail(TVR_ERR_INVALID, "eps_T=%g must be in [0, weight_thres]", eps_T);
-    ScratchLayout L = scratch_layout(n_rays, S);
-    if (!scratch || scratch_bytes < L.total || (uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "scratch too small (%zu < %zu) or misaligned", scratch_bytes, L.total);
-    hipStream_t stream = (hipStream_t)stream_;
-    MarchOut mo = carve_scratch((char *)scratch, L, depth_out);
-    const MarchSampling sm = {jitter, nullptr};
-    HIP_TRY(launch_zero_header(mo.counter, stream));                   // [0] queue length, [1] the march's tile counter, [2] its fault flag
-    HIP_TRY(launch_cp_march(s->dev, s->cpd, rays, (int)n_rays, S, sm, eps_T, mo, nullptr, stream));
-    if (n_rays <= TVR_RAY_ORDER_MAX_RAYS)                              // a training queue in ray order, as march_forward_impl leaves it
-        HIP_TRY(launch_queue_ray_order(mo, (unsigned *)((char *)scratch + L.ray_new), mo.q_out, (unsigned *)((char *)scratch + L.q_j), (int)n_rays, stream));
-    return TVR_OK;
-}
-
-int tvr_cp_march_backward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, const void *fwd_scratch, size_t fwd_scratch_bytes,
-                          const float *grad_w, const float *grad_acc, void *grad_scratch, size_t grad_scratch_bytes, const tvr_cp_grads *out, void *stream_)
-{
-    int rc = cp_required(s, __func__);
-    if (rc != TVR_OK) return rc;
-    rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    if (!rays || !fwd_scratch || !grad_w || !grad_acc || !grad_scratch || !out || n_rays <= 0) return fail(TVR_ERR_INVALID, "NULL argument or n_rays <= 0");
-    for (int i = 0; i < 3; ++i)
-        if (!out->density_line[i]) return fail(TVR_ERR_INVALID, "density gradient pointer %d is NULL", i);
-    if (S <= 0 || S > 4096) return fail(TVR_ERR_INVALID, "n_samples=%d out of [1,4096]", S);
-    if ((size_t)n_rays * (size_t)S >= (1ull << 32)) return fail(TVR_ERR_INVALID, "n_rays*n_samples must be < 2^32 per call");
-    if (!(eps_T >= 0.0f) || eps_T > s->desc.weight_thres) return fail(TVR_ERR_INVALID, "eps_T=%g must be in [0, weight_thres]", eps_T);
-    ScratchLayout L = scratch_layout(n_rays, S);
-    if (fwd_scratch_bytes < L.total || (uintptr_t)fwd_scratch % 256) return fail(TVR_ERR_SCRATCH, "forward scratch %zu B < %zu B or misaligned", fwd_scratch_bytes, L.total);
-    if (grad_scratch_bytes < s->lay.mlp_image || (uintptr_t)grad_scratch % 256) return fail(TVR_ERR_SCRATCH, "gradient scratch too small or misaligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    const tvr_scene_desc &d = s->desc;
-    CpGradImages G = cp_carve_grads(s, (char *)grad_scratch);
-    for (int i = 0; i < 3; ++i) HIP_TRY(launch_zero_f32(G.dline[i], (long long)(d.grid[kVecH[i]] + 1) * s->cpd.rd, stream));       // (rd is a multiple of 16, blocks 256-B aligned)
-    MarchOut mo = carve_scratch((char *)fwd_scratch, L, nullptr);
-    HIP_TRY(launch_cp_march_backward(s->dev, s->cpd, rays, (int)n_rays, S, jitter, eps_T, mo, grad_w, grad_acc, G.dline, stream));
-    for (int i = 0; i < 3; ++i) HIP_TRY(launch_unpack_grad(G.dline[i], out->density_line[i], d.density_n_comp[0], s->cpd.rd, d.grid[kVecH[i]], 1, stream));
-    return TVR_OK;
-}
-
-int tvr_cp_app_backward(tvr_scene *s, const float *xyz, int64_t m, const float *grad_features, size_t grad_features_bytes, void *grad_scratch, size_t grad_scratch_bytes,
-                        const tvr_cp_grads *out, void *stream_)
-{
-    int rc = cp_required(s, __func__);
-    if (rc != TVR_OK) return rc;
-    rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    if (!grad_scratch || !out || m < 0 || (m > 0 && (!xyz || !grad_features))) return fail(TVR_ERR_INVALID, "NULL argument or m < 0");
-    for (int i = 0; i < 3; ++i)
-        if (!out->app_line[i]) return fail(TVR_ERR_INVALID, "appearance gradient pointer %d is NULL", i);
-    if (!out->basis_mat) return fail(TVR_ERR_INVALID, "basis_mat gradient pointer is NULL");
-    if (m > 0) NEED("grad_features [m,27]", grad_features_bytes, m, TVR_APPDIM);
-    if ((uint64_t)m >= (1ull << 32)) return fail(TVR_ERR_INVALID, "m = %lld: at most 2^32 - 1 entries per call", (long long)m);
-    if (grad_scratch_bytes < s->lay.mlp_image || (uintptr_t)grad_scratch % 256) return fail(TVR_ERR_SCRATCH, "gradient scratch too small or misaligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    const tvr_scene_desc &d = s->desc;
-    CpGradImages G = cp_carve_grads(s, (char *)grad_scratch);
-    for (int i = 0; i < 3; ++i) HIP_TRY(launch_zero_f32(G.aline[i], (long long)(d.grid[kVecH[i]] + 1) * s->cpd.ra, stream));       // (ra is a multiple of 4)
-    HIP_TRY(launch_zero_f32(G.basis, (long long)TVR_APPDIM * s->cpd.ra, stream));
-    if (m > 0) HIP_TRY(launch_cp_app_backward(s->dev, s->cpd, xyz, m, grad_features, G.aline, G.basis, stream));
-    for (int i = 0; i < 3; ++i) HIP_TRY(launch_unpack_grad(G.aline[i], out->app_line[i], d.app_n_comp[0], s->cpd.ra, d.grid[kVecH[i]], 1, stream));
-    HIP_TRY(launch_copy_cols(out->basis_mat, d.app_n_comp[0], 0, G.basis, s->cpd.ra, d.app_n_comp[0], TVR_APPDIM, stream));
-    return TVR_OK;
-}
-
-}  // extern "C"
-
-// ---- the training step without a host read (include/tvr.h: tvr_train_forward / tvr_train_backward) ----
-struct WorkLayout {
-    size_t h, feats32, h1, h2, rgb, g8, rgb_s, pre, grgb, gin0, grad_w, grad_acc, d_out4, dh2, dh1, dfeats32, dg8, dh, X, tmp, gemm, colsum, image, scalars, total;
-};
-static WorkLayout work_layout(int64_t n_rays, int32_t S, int64_t cap, bool gen = false)
-{
-    WorkLayout L;
-    size_t off = 0;
-    auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * sizeof(float), 256); return o; };
-    const size_t c = (size_t)cap, n = (size_t)n_rays;
-    L.h = take(c * TVR_KAPP); L.feats32 = take(c * 32); L.h1 = take(c * TVR_FEATC); L.h2 = take(c * TVR_FEATC); L.rgb = take(c * 3);
-    L.g8 = take(c * 8); L.rgb_s = take(c * 3); L.pre = take(n * 3);
-    L.grgb = take(c * 3); L.gin0 = take(c); L.grad_w = take(n * (size_t)S); L.grad_acc = take(n);
-    L.d_out4 = take(c * 4); L.dh2 = take(c * TVR_FEATC); L.dh1 = take(c * TVR_FEATC); L.dfeats32 = take(c * 32); L.dg8 = take(c * 8); L.dh = take(c * TVR_KAPP);
-    L.X = take(c * (gen ? (size_t)TVR_GENX_FLOATS : (size_t)TVR_GENX_W));    // (more than two encoding frequencies: three column blocks of 152, tvr_train.hip pe_concat_gen_kernel; otherwise one block or [cap,150 / 151])
-    L.tmp = take((size_t)TVR_FEATC * TVR_GENX_W + 256);       // gemm_tn results that are wider than the gradient they feed ([4,128], [32,144], [8,144]; a [128,152] block of dW1, dW2 of a narrow network) and bias sums
-    size_t g = gemm_tn_scratch_bytes(TVR_FEATC, TVR_GENX_W + 1, cap);        // (+ 1: the ones column that carries the bias gradient)
-    L.gemm = take(g / sizeof(float) + 64);
-    L.colsum = take(colsum_scratch_bytes() / sizeof(float));
-    L.image = take(mlp_train_image_bytes() / sizeof(float) + 64);
-    L.scalars = take(64);                                     // [0] max |gradient| bits, [1] gscale
-    L.total = off;
-    return L;
-}
-
-static int train_args_ok(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const void *fwd_scratch, size_t fwd_bytes, const void *work, size_t work_bytes,
-                         int64_t app_cap)
-{
-    NOT_CP(s);
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
-    const tvr_scene_desc &d = s->desc;
-    // round 6: view_pe / fea_pe up to 6 (TensorVMSplit scenes: the lockstep layer 1 forward, the streamed W1^T backward); REFTensoRF keeps 2 / 2
-    // and (TensorVMSplit) any component counts the kernels hold, <= 16 / 48 per plane — TensorBase's own defaults are 8 / 24: the packed scene carries zero channels, basis_mat's
-    // columns are mapped in pack_train_image_kernel and its gradient is copied back plane by plane
-    // — and any hidden width up to 128 and any frequencies 0 .. 6: every TensorVMSplit shape the scene itself accepts (check_desc) trains through the fused step
-    bool std_shape = d.variant == 0 ? (d.featureC >= 1 && d.featureC <= TVR_FEATC && d.view_pe >= 0 && d.view_pe <= TVR_GEN_PE && d.fea_pe >= 0 && d.fea_pe <= TVR_GEN_PE)
-                                    : (d.featureC == TVR_FEATC && d.view_pe == 2 && d.fea_pe == 2);
-    for (int i = 0; i < 3; ++i) std_shape = std_shape && (d.app_n_comp[i] == TVR_CA || (d.variant == 0 && d.app_n_comp[i] >= 1 && d.app_n_comp[i] <= TVR_CA));
-    if (!std_shape) return fail(TVR_ERR_UNSUPPORTED, "the fused training step takes REFTensoRF scenes at featureC 128, view_pe = fea_pe = 2, 48 appearance components per plane (TensorVMSplit: any shape the scene accepts)");
-    if (!rays || n_rays <= 0 || S <= 0 || S > 4096 || app_cap <= 0) return fail(TVR_ERR_INVALID, "rays NULL, or n_rays / n_samples / app_cap out of range");
-    if ((size_t)n_rays * (size_t)S >= (1ull << 32) || (uint64_t)app_cap * 576u >= (1ull << 32)) return fail(TVR_ERR_INVALID, "n_rays * n_samples and app_cap * 576 must be < 2^32");
-    if (!fwd_scratch || fwd_bytes < scratch_layout(n_rays, S).total || (uintptr_t)fwd_scratch % 256) return fail(TVR_ERR_SCRATCH, "forward scratch too small or misaligned");
-    if (!work || work_bytes < work_layout(n_rays, S, app_cap, s->dev.gen != 0).total || (uintptr_t)work % 256) return fail(TVR_ERR_SCRATCH, "training workspace too small (tvr_train_work_bytes) or misaligned");
-    return TVR_OK;
-}
-
-extern "C" {
-
-size_t tvr_train_work_bytes(const tvr_scene *s, int64_t n_rays, int32_t n_samples, int64_t app_cap)
-{
-    if (n_rays <= 0 || n_samples <= 0 || app_cap <= 0) return 0;
-    if (cp_refused(s, __func__) != TVR_OK) return 0;
-    return work_layout(n_rays, n_samples, app_cap, s && s->dev.gen).total;           // (a scene with more than two encoding frequencies has the wider X)
-}
-
-int tvr_train_work_describe(const tvr_scene *s, int64_t n_rays, int32_t n_samples, int64_t app_cap, tvr_train_work_layout *out)
-{
-    NOT_CP(s);
-    if (!s || !out || n_rays <= 0 || n_samples <= 0 || app_cap <= 0) return fail(TVR_ERR_INVALID, "tvr_train_work_describe: NULL argument or a count <= 0");
-    const bool gen = s->dev.gen != 0;
-    const WorkLayout W = work_layout(n_rays, n_samples, app_cap, gen);
-    out->h = W.h; out->feats32 = W.feats32; out->h1 = W.h1; out->h2 = W.h2; out->rgb = W.rgb; out->grgb = W.grgb; out->d_out4 = W.d_out4; out->dh2 = W.dh2; out->dh1 = W.dh1;
-    out->dfeats32 = W.dfeats32; out->dh = W.dh; out->X = W.X; out->total = W.total;
-    const int n_in = TVR_APPDIM + 3 + 2 * TVR_APPDIM * s->desc.fea_pe + 6 * s->desc.view_pe;
-    const bool blocks = s->desc.variant == 0 && (gen || s->desc.fea_pe != 2 || s->desc.view_pe != 2 || s->desc.featureC < TVR_FEATC);
-    out->x_blocks = blocks ? (n_in + TVR_GENX_W - 1) / TVR_GENX_W : 1;
-    out->x_block_cols = blocks ? TVR_GENX_W : (s->desc.variant == 1 ? TVR_NIN_REF : TVR_NIN);
-    return TVR_OK;
-}
-
-int tvr_train_forward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, int32_t white_bg, void *fwd_scratch,
-                      size_t fwd_bytes, void *work, size_t work_bytes, int64_t app_cap, float *rgb_map, float *depth, float *pen_ray, void *stream_)
-{
-    int rc = train_args_ok(s, rays, n_rays, S, fwd_scratch, fwd_bytes, work, work_bytes, app_cap);
-    if (rc != TVR_OK) return rc;
-    const bool ref = s->desc.variant == 1;
-    if (!rgb_map || !depth || (ref && !pen_ray)) return fail(TVR_ERR_INVALID, "rgb_map / depth (/ pen_ray for a REFTensoRF scene) is NULL");
-    hipStream_t stream = (hipStream_t)stream_;
-    const MarchSampling sm = {jitter, nullptr};
-    rc = march_forward_impl(s, rays, n_rays, S, sm, eps_T, depth, nullptr, fwd_scratch, fwd_bytes, stream_);
-    if (rc != TVR_OK) return rc;
-    const ScratchLayout SL = scratch_layout(n_rays, S);
-    const MarchOut mo = carve_scratch((char *)fwd_scratch, SL, depth);
-    const WorkLayout W = work_layout(n_rays, S, app_cap, s->dev.gen != 0);
-    char *w = (char *)work;
-    HIP_TRY(launch_app_h_forward(s->dev, (const float *)mo.q_pos, app_cap, (float *)(w + W.h), stream, 4, mo.counter));
-    ShadeArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.n = app_cap; sa.counter = mo.counter; sa.h_in = (const float *)(w + W.h); sa.q_ray = mo.q_ray; sa.rays = rays;
-    sa.out = (float *)(w + W.rgb); sa.t_feats = (float *)(w + W.feats32); sa.t_h1 = (float *)(w + W.h1); sa.t_h2 = (float *)(w + W.h2);
-    sa.t_g8 = (float *)(w + W.g8); sa.t_rgbs = (float *)(w + W.rgb_s);
-    HIP_TRY(launch_shade(s->dev, SH_SRC_H, SH_DST_TRAIN, sa, stream));
-    HIP_TRY(launch_composite_train_forward(mo, (int)n_rays, app_cap, white_bg, (const float *)(w + W.rgb), (const float *)(w + W.feats32), ref ? 1 : 0, rgb_map,
-                                           (float *)(w + W.pre), pen_ray, stream));
-    return TVR_OK;
-}
-
-int tvr_train_backward(tvr_scene *s, const float *rays, int64_t n_rays, int32_t S, const float *jitter, float eps_T, int32_t white_bg, const void *fwd_scratch,
-                       size_t fwd_bytes, void *work, size_t work_bytes, int64_t app_cap, const tvr_train_weights *wt, const float *grad_rgb_map,
-                       const float *grad_pen_ray, float grad_scale_target, void *grad_scratch, size_t grad_scratch_bytes, const tvr_vm_grads *vm_out,
-                       const tvr_train_mlp_grads *mo_, uint32_t *sat_flag_dev, void *stream_)
-{
-    int rc = train_args_ok(s, rays, n_rays, S, fwd_scratch, fwd_bytes, work, work_bytes, app_cap);
-    if (rc != TVR_OK) return rc;
-    const bool ref = s->desc.variant == 1;
-    if (!wt || !wt->W1 || !wt->W2 || !wt->W3 || !wt->basis || !grad_rgb_map || !vm_out || !mo_ || !(grad_scale_target > 0.0f)) return fail(TVR_ERR_INVALID, "NULL argument or grad_scale_target <= 0");
-    if (!mo_->W1 || !mo_->b1 || !mo_->W2 || !mo_->b2 || !mo_->W3 || !mo_->b3 || !mo_->basis) return fail(TVR_ERR_INVALID, "a network gradient pointer is NULL");
-    if (ref)
-        for (int i = 0; i < 4; ++i)
-            if (!wt->heads_W[i] || !mo_->heads_W[i] || !mo_->heads_b[i]) return fail(TVR_ERR_INVALID, "REFTensoRF head %d (normal, diffuse, specular, rho): weight or gradient pointer is NULL", i);
-    hipStream_t stream = (hipStream_t)stream_;
-    const ScratchLayout SL = scratch_layout(n_rays, S);
-    const MarchOut mo = carve_scratch((char *)fwd_scratch, SL, nullptr);
-    const bool gen = s->dev.gen != 0;
-    const WorkLayout W = work_layout(n_rays, S, app_cap, gen);
-    char *w = (char *)work;
-    auto F = [&](size_t off) { return (float *)(w + off); };
-    unsigned *amax = (unsigned *)(w + W.scalars);
-    float *gscale = (float *)(w + W.scalars) + 1;
-    const unsigned *mdev = mo.counter;
-    const int nin = ref ? TVR_NIN_REF : TVR_NIN;
-    // 1. compositing backward: gradients of the per-sample colours, of the weights and of acc; the scale of the fused backward
-    HIP_TRY(launch_composite_train_backward(mo, (int)n_rays, app_cap, white_bg, F(W.rgb), F(W.feats32), ref ? F(W.g8) : nullptr, F(W.pre), grad_rgb_map, ref ? grad_pen_ray : nullptr,
-                                            F(W.grgb), F(W.gin0), F(W.grad_w), F(W.grad_acc), amax, grad_scale_target, gscale, stream));
-    // 2. the network backward (register-resident MFMA chains), dh through basis_mat (and the heads)
-    const int fc = s->desc.featureC;
-    // dW1 in column blocks (tvr_train.hip pe_concat_gen_kernel) for every shape but the kernels' own 2 / 2 at width 128: more than two frequencies (three blocks), fewer (one block
-    // of 30 .. 144 columns), a narrower network (its gradients are cropped out of the 128-wide products)
-    const bool blocks = !ref && (gen || s->desc.fea_pe != 2 || s->desc.view_pe != 2 || fc < TVR_FEATC);
-    HIP_TRY(launch_pack_train_image(wt->W1, wt->W2, wt->W3, wt->basis, ref ? wt->heads_W : nullptr, w + W.image, stream, s->desc.fea_pe, s->desc.view_pe, s->desc.app_n_comp, fc));
-    MlpRefBwd rb;
-    rb.g8 = F(W.g8); rb.viewdirs = nullptr; rb.grad_in0 = F(W.gin0); rb.dg8 = F(W.dg8); rb.rays = rays; rb.q_ray = mo.q_ray;
-    HIP_TRY(launch_mlp_train_backward(F(W.grgb), ref ? F(W.rgb_s) : F(W.rgb), F(W.feats32), F(W.h1), F(W.h2), app_cap, gscale, F(W.d_out4), F(W.dh2), F(W.dh1), F(W.dfeats32),
-                                      F(W.dh), sat_flag_dev, w + W.image, ref ? &rb : nullptr, stream, mdev, gen ? 1 : 0));
-    // 3. weight gradients: dW = dY^T X over the step's appearance samples (tall-skinny reductions, fixed order), bias gradients = column sums
-    if (blocks) HIP_TRY(launch_pe_concat_gen(F(W.feats32), 32, rays, mo.q_ray, s->desc.fea_pe, s->desc.view_pe, app_cap, mdev, F(W.X), stream));
-    else if (ref) HIP_TRY(launch_pe_concat_strided(F(W.feats32), 32, F(W.feats32) + 27, 32, nullptr, nullptr, F(W.feats32) + 30, 32, app_cap, mdev, F(W.X), stream));
-    else HIP_TRY(launch_pe_concat_strided(F(W.feats32), 32, nullptr, 0, rays, mo.q_ray, nullptr, 0, app_cap, mdev, F(W.X), stream));
-    float *tmp = F(W.tmp), *gsc = F(W.gemm), *csc = F(W.colsum);
-    // (the bias gradients ride along as a virtual ones column of the second operand: no second pass over d_out / dh2 / dh1)
-    float *bs3 = tmp + 32 * TVR_KAPP + 16, *btmp = tmp + TVR_FEATC * TVR_GENX_W + 64;          // (btmp: a 128-entry bias sum of a product whose rows are cropped afterwards)
-    // The products run on the fp16-split MFMAs at the backward's own gradient scale (the same values went through fp16 at that scale inside
-    // mlp_train_backward / basis_backward, which raise the saturation flag if they do not fit): the kernel then runs at its staging rate.
-    HIP_TRY(launch_gemm_tn(F(W.d_out4), 4, 4, F(W.h2), TVR_FEATC, TVR_FEATC, app_cap, tmp, gsc, stream, mdev, bs3, gscale));
-    if (fc == TVR_FEATC) HIP_TRY(launch_copy_f32(mo_->W3, tmp, 3 * TVR_FEATC, stream));
-    else HIP_TRY(launch_copy_cols(mo_->W3, fc, 0, tmp, TVR_FEATC, fc, 3, stream));             // W3's gradient is [3, fc]: the first fc columns of the [4,128] product
-    HIP_TRY(launch_copy_f32(mo_->b3, bs3, 3, stream));
-    if (fc == TVR_FEATC) HIP_TRY(launch_gemm_tn(F(W.dh2), TVR_FEATC, TVR_FEATC, F(W.h1), TVR_FEATC, TVR_FEATC, app_cap, mo_->W2, gsc, stream, mdev, mo_->b2, gscale));
-    else {                                                                                      // [fc, fc] and [fc] out of the 128-wide product (units that do not exist: exact zeros)
-        HIP_TRY(launch_gemm_tn(F(W.dh2), TVR_FEATC, TVR_FEATC, F(W.h1), TVR_FEATC, TVR_FEATC, app_cap, tmp, gsc, stream, mdev, btmp, gscale));
-        HIP_TRY(launch_copy_cols(mo_->W2, fc, 0, tmp, TVR_FEATC, fc, fc, stream));
-        HIP_TRY(launch_copy_f32(mo_->b2, btmp, fc, stream));
-    }
-    if (blocks) {
-        // dW1 [fc, n_in] block by block (tvr_train.hip pe_concat_gen_kernel): each block's product lands in `tmp` and is copied to its columns; the bias rides with block 0
-        const int n_in = TVR_APPDIM + 3 + 2 * TVR_APPDIM * s->desc.fea_pe + 6 * s->desc.view_pe, nb = (n_in + TVR_GENX_W - 1) / TVR_GENX_W;
-        for (int b = 0; b < nb; ++b) {
-            const int cols = b == nb - 1 ? n_in - b * TVR_GENX_W : TVR_GENX_W, wb = (cols + 3) & ~3;
-            HIP_TRY(launch_gemm_tn(F(W.dh1), TVR_FEATC, TVR_FEATC, F(W.X) + (size_t)b * (size_t)app_cap * TVR_GENX_W, wb, wb, app_cap, tmp, gsc, stream, mdev,
-                                   b == 0 ? (fc == TVR_FEATC ? mo_->b1 : btmp) : nullptr, gscale));
-            HIP_TRY(launch_copy_cols(mo_->W1, n_in, b * TVR_GENX_W, tmp, wb, cols, fc, stream));
-            if (b == 0 && fc < TVR_FEATC) HIP_TRY(launch_copy_f32(mo_->b1, btmp, fc, stream));
-        }
-    } else
-    HIP_TRY(launch_gemm_tn(F(W.dh1), TVR_FEATC, TVR_FEATC, F(W.X), nin, nin, app_cap, mo_->W1, gsc, stream, mdev, mo_->b1, gscale));
-    HIP_TRY(launch_gemm_tn(F(W.dfeats32), 32, 32, F(W.h), TVR_KAPP, TVR_KAPP, app_cap, tmp, gsc, stream, mdev, nullptr, gscale));
-    {
-        int k_app = 0;
-        for (int i = 0; i < 3; ++i) k_app += s->desc.app_n_comp[i];
-        if (k_app == TVR_KAPP) HIP_TRY(launch_copy_f32(mo_->basis, tmp, TVR_APPDIM * TVR_KAPP, stream));
-        else                                     // fewer components: the gradient's [27, k_app] takes plane p's columns 48 p .. 48 p + n_p of the [32,144] product
-            for (int i = 0, off = 0; i < 3; off += s->desc.app_n_comp[i], ++i)
-                HIP_TRY(launch_copy_cols(mo_->basis, k_app, off, tmp + i * TVR_CA, TVR_KAPP, s->desc.app_n_comp[i], TVR_APPDIM, stream));
-    }
-    if (ref) {
-        HIP_TRY(launch_gemm_tn(F(W.dg8), 8, 8, F(W.h), TVR_KAPP, TVR_KAPP, app_cap, tmp, gsc, stream, mdev));      // rows: normal 0..2, specular 3, diffuse 4..6, rho 7
-        HIP_TRY(launch_copy_f32(mo_->heads_W[0], tmp, 3 * TVR_KAPP, stream));
-        HIP_TRY(launch_copy_f32(mo_->heads_W[2], tmp + 3 * TVR_KAPP, TVR_KAPP, stream));
-        HIP_TRY(launch_copy_f32(mo_->heads_W[1], tmp + 4 * TVR_KAPP, 3 * TVR_KAPP, stream));
-        HIP_TRY(launch_copy_f32(mo_->heads_W[3], tmp + 7 * TVR_KAPP, TVR_KAPP, stream));
-        float *bs = tmp + 32 * TVR_KAPP;
-        HIP_TRY(launch_colsum(F(W.dg8), 8, 8, app_cap, mdev, bs, csc, stream));
-        HIP_TRY(launch_copy_f32(mo_->heads_b[0], bs, 3, stream));
-        HIP_TRY(launch_copy_f32(mo_->heads_b[2], bs + 3, 1, stream));
-        HIP_TRY(launch_copy_f32(mo_->heads_b[1], bs + 4, 3, stream));
-        HIP_TRY(launch_copy_f32(mo_->heads_b[3], bs + 7, 1, stream));
-    }
-    // 4. scatter dh into the appearance planes / lines, then the march backward for the density factors
-    rc = app_h_backward_impl(s, (const float *)mo.q_pos, 4, app_cap, mdev, F(W.dh), grad_scratch, grad_scratch_bytes, vm_out, stream_);
-    if (rc != TVR_OK) return rc;
-    const MarchSampling sm = {jitter, nullptr};
-    return march_backward_impl(s, rays, n_rays, S, sm, eps_T, fwd_scratch, fwd_bytes, F(W.grad_w), F(W.grad_acc), nullptr, nullptr, grad_scratch, grad_scratch_bytes, vm_out,
-                               stream_, app_cap);
-}
-
-int tvr_app_h_backward(tvr_scene *s, const float *xyz, int64_t m, const float *dh, size_t dh_bytes, void *grad_scratch, size_t grad_scratch_bytes,
-                       const tvr_vm_grads *out, void *stream_)
-{
-    NOT_CP(s);
-    if (m > 0) NEED("dh [m,144]", dh_bytes, m, TVR_KAPP);
-    return app_h_backward_impl(s, xyz, 3, m, nullptr, dh, grad_scratch, grad_scratch_bytes, out, stream_);
-}
-
-int tvr_pe_concat(const float *features, const float *viewdirs, const float *dot_product, int64_t m, float *X, size_t X_bytes, void *stream)
-{
-    if (m == 0) return TVR_OK;
-    if (m > 0) NEED(dot_product ? "X [m,151]" : "X [m,150]", X_bytes, m, dot_product ? TVR_NIN_REF : TVR_NIN);
-    if (!features || !viewdirs || !X || m < 0) return fail(TVR_ERR_INVALID, "features/viewdirs/X NULL or m < 0");
-    HIP_TRY(launch_pe_concat(features, viewdirs, dot_product, m, X, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_pe_concat_backward(const float *features, const float *viewdirs, const float *grad_X, int64_t m, int32_t with_dot, float *grad_features,
-                           size_t grad_features_bytes, float *grad_viewdirs, float *grad_dot, void *stream)
-{
-    if (m == 0) return TVR_OK;
-    if (m > 0) NEED("grad_features [m,27]", grad_features_bytes, m, TVR_APPDIM);
-    if (!features || !viewdirs || !grad_X || !grad_features || m < 0) return fail(TVR_ERR_INVALID, "NULL argument or m < 0");
-    HIP_TRY(launch_pe_concat_backward(features, viewdirs, grad_X, m, with_dot ? 1 : 0, grad_features, grad_viewdirs, grad_dot, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_tv_loss(const float *x, int32_t C, int32_t H, int32_t W, float weight, float *value, float *grad, void *scratch, size_t scratch_bytes,
-                void *stream)
-{
-    if (!x || !value || !grad || C < 1 || H < 1 || W < 1) return fail(TVR_ERR_INVALID, "x/value/grad NULL or bad shape");
-    if (!scratch || scratch_bytes < 2048) return fail(TVR_ERR_SCRATCH, "tvr_tv_loss needs 2048 bytes of scratch");
-    HIP_TRY(launch_tv_loss(x, C, H, W, weight, value, grad, (float *)scratch, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-static int reg_list(RegList &L, const float *const *xs, float *const *grads, const int64_t *counts, const int32_t *rows, int32_t n, bool need_grads)
-{
-    if (n < 1 || n > TVR_REG_MAX) return fail(TVR_ERR_INVALID, "1..%d tensors per call", TVR_REG_MAX);
-    if (!xs || !counts || (need_grads && !grads)) return fail(TVR_ERR_INVALID, "xs/counts/grads NULL");
-    L.n = n;
-    for (int t = 0; t < n; ++t) {
-        if (!xs[t] || counts[t] < 1 || (need_grads && !grads[t])) return fail(TVR_ERR_INVALID, "tensor %d: NULL pointer or empty", t);
-        L.x[t] = xs[t];
-        L.grad[t] = need_grads ? grads[t] : nullptr;
-        L.count[t] = counts[t];
-        L.rows[t] = rows ? rows[t] : 1;
-        L.blocks[t] = 0;
-    }
-    return TVR_OK;
-}
-
-size_t tvr_l1_mean_scratch_bytes(const int64_t *counts, int32_t n)
-{
-    RegList L;
-    if (!counts || n < 1 || n > TVR_REG_MAX) return 0;
-    L.n = n;
-    for (int t = 0; t < n; ++t) L.count[t] = counts[t] < 1 ? 1 : counts[t];
-    return reg_l1_scratch_bytes(L);
-}
-
-int tvr_l1_mean(const float *const *xs, const int64_t *counts, int32_t n, float *value, void *scratch, size_t scratch_bytes, void *stream)
-{
-    RegList L;
-    int rc = reg_list(L, xs, nullptr, counts, nullptr, n, false);
-    if (rc != TVR_OK) return rc;
-    if (!value) return fail(TVR_ERR_INVALID, "value NULL");
-    if (!scratch || scratch_bytes < reg_l1_scratch_bytes(L)) return fail(TVR_ERR_SCRATCH, "scratch too small (tvr_l1_mean_scratch_bytes)");
-    HIP_TRY(launch_l1_forward(L, value, (float *)scratch, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_l1_mean_backward(const float *const *xs, float *const *grads, const int64_t *counts, int32_t n, const float *grad_value, void *stream)
-{
-    RegList L;
-    int rc = reg_list(L, xs, grads, counts, nullptr, n, true);
-    if (rc != TVR_OK) return rc;
-    if (!grad_value) return fail(TVR_ERR_INVALID, "grad_value NULL");
-    HIP_TRY(launch_l1_backward(L, grad_value, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-static int ortho_list(RegList &L, const float *const *vs, float *const *grads, const int32_t *n_comp, const int32_t *n_size, int32_t n, bool need_grads)
-{
-    if (!n_comp || !n_size) return fail(TVR_ERR_INVALID, "n_comp/n_size NULL");
-    int64_t counts[TVR_REG_MAX];
-    if (n < 1 || n > TVR_REG_MAX) return fail(TVR_ERR_INVALID, "1..%d line factors per call", TVR_REG_MAX);
-    for (int t = 0; t < n; ++t) {
-        if (n_comp[t] < 2 || n_comp[t] > 48 || n_size[t] < 1) return fail(TVR_ERR_UNSUPPORTED, "line factor %d: %d components x %d (2..48 components)", t, n_comp[t], n_size[t]);
-        counts[t] = (int64_t)n_comp[t] * n_size[t];
-    }
-    return reg_list(L, vs, grads, counts, n_comp, n, need_grads);
-}
-
-int tvr_line_ortho(const float *const *vs, const int32_t *n_comp, const int32_t *n_size, int32_t n, float *value, void *scratch, size_t scratch_bytes, void *stream)
-{
-    RegList L;
-    int rc = ortho_list(L, vs, nullptr, n_comp, n_size, n, false);
-    if (rc != TVR_OK) return rc;
-    if (!value) return fail(TVR_ERR_INVALID, "value NULL");
-    if (!scratch || scratch_bytes < TVR_LINE_ORTHO_SCRATCH_BYTES) return fail(TVR_ERR_SCRATCH, "tvr_line_ortho needs %d bytes of scratch", (int)TVR_LINE_ORTHO_SCRATCH_BYTES);
-    HIP_TRY(launch_ortho(L, nullptr, value, (float *)scratch, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_line_ortho_backward(const float *const *vs, float *const *grads, const int32_t *n_comp, const int32_t *n_size, int32_t n, const float *grad_value, void *stream)
-{
-    RegList L;
-    int rc = ortho_list(L, vs, grads, n_comp, n_size, n, true);
-    if (rc != TVR_OK) return rc;
-    if (!grad_value) return fail(TVR_ERR_INVALID, "grad_value NULL");
-    HIP_TRY(launch_ortho(L, grad_value, nullptr, nullptr, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_linear_dx(const float *dY, int32_t ldy, int32_t N, const float *W, int32_t ldw, int32_t n_valid, int32_t K, const float *mask, int32_t ldm,
-                  const uint64_t *mask_bits, float *dX, int32_t ldx, size_t dX_bytes, int64_t M, const float *scale_dev, uint32_t *sat_flag_dev, void *stream)
-{
-    if (mask && mask_bits) return fail(TVR_ERR_INVALID, "mask and mask_bits are alternatives");
-    if ((uintptr_t)mask_bits & 7) return fail(TVR_ERR_INVALID, "mask_bits is not 8-B aligned");
-    if (scale_dev && (N & 15)) return fail(TVR_ERR_INVALID, "the fp16-split form (scale_dev) takes N in multiples of 16 (N = %d)", N);
-    if (M < 0) return fail(TVR_ERR_INVALID, "M < 0");
-    if (N < 8 || N > 128 || (N & 7) || n_valid < 1 || n_valid > N) return fail(TVR_ERR_UNSUPPORTED, "N = %d (a multiple of 8 in [8,128]) / n_valid = %d", N, n_valid);
-    if (K != 32 && K != 64 && K != 96 && K != 128) return fail(TVR_ERR_UNSUPPORTED, "K = %d (32, 64, 96 or 128)", K);
-    if (ldy < N || ldx < K || ldw < K || (mask && ldm < K) || (ldy & 3) || (ldx & 3) || (mask && (ldm & 3))) return fail(TVR_ERR_INVALID, "row strides: >= the row length and multiples of 4");
-    if (M == 0) return TVR_OK;
-    if (!dY || !W || !dX || ((uintptr_t)dY & 15) || ((uintptr_t)dX & 15) || ((uintptr_t)mask & 15)) return fail(TVR_ERR_INVALID, "dY / W / dX NULL or not 16-B aligned");
-    if (dX_bytes < ((size_t)(M - 1) * ldx + K) * sizeof(float)) return fail(TVR_ERR_SCRATCH, "dX holds fewer than M rows");
-    HIP_TRY(launch_linear_dx(dY, ldy, N, W, ldw, n_valid, K, mask, ldm, dX, ldx, M, (hipStream_t)stream, scale_dev, sat_flag_dev,
-                             (const unsigned long long *)mask_bits));
-    return TVR_OK;
-}
-
-size_t tvr_colsum_scratch_bytes(void) { return colsum_scratch_bytes(); }
-
-int tvr_colsum(const float *A, int32_t lda, int32_t K, int64_t M, float *out, void *scratch, size_t scratch_bytes, void *stream)
-{
-    if (M < 0 || K < 1 || K > 128 || lda < K) return fail(TVR_ERR_INVALID, "bad M / K / lda (K <= 128)");
-    if (!out || (M > 0 && !A)) return fail(TVR_ERR_INVALID, "A / out NULL");
-    if (!scratch || scratch_bytes < colsum_scratch_bytes()) return fail(TVR_ERR_SCRATCH, "scratch too small (tvr_colsum_scratch_bytes)");
-    HIP_TRY(launch_colsum(A, lda, K, M, nullptr, out, (float *)scratch, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-static int gemm_tn_check(int32_t Ka, int32_t Kb, int64_t M)
-{
-    if (M < 0 || Ka < 1 || Kb < 1) return fail(TVR_ERR_INVALID, "bad Ka/Kb/M");
-    if (((Ka + 31) / 32) * ((Kb + 31) / 32) > 20) return fail(TVR_ERR_UNSUPPORTED, "Ka x Kb = %d x %d exceeds the 20 32x32 tiles of a workgroup", Ka, Kb);
-    return TVR_OK;
-}
-
-size_t tvr_gemm_tn_scratch_bytes(int32_t Ka, int32_t Kb, int64_t M)
-{
-    if (gemm_tn_check(Ka, Kb, M) != TVR_OK) return 0;
-    return gemm_tn_scratch_bytes(Ka, Kb, M);
-}
-
-int tvr_gemm_tn(const float *A, int32_t lda, int32_t Ka, const float *B, int32_t ldb, int32_t Kb, int64_t M, float *C, void *scratch,
-                size_t scratch_bytes, void *stream)
-{
-    int rc = gemm_tn_check(Ka, Kb, M);
-    if (rc != TVR_OK) return rc;
-    if (!C || (M > 0 && (!A || !B))) return fail(TVR_ERR_INVALID, "A/B/C NULL");
-    if (lda < Ka || ldb < Kb) return fail(TVR_ERR_INVALID, "lda/ldb smaller than the row length");
-    if (M > 0 && (!scratch || scratch_bytes < gemm_tn_scratch_bytes(Ka, Kb, M))) return fail(TVR_ERR_SCRATCH, "scratch too small (tvr_gemm_tn_scratch_bytes)");
-    HIP_TRY(launch_gemm_tn(A, lda, Ka, B, ldb, Kb, M, C, (float *)scratch, (hipStream_t)stream));
-    return TVR_OK;
-}
-
-int tvr_gemm_tn_scaled(const float *A, int32_t lda, int32_t Ka, const float *B, int32_t ldb, int32_t Kb, int64_t M, float *C, float *colsum_A, const float *scale_dev,
-                       void *scratch, size_t scratch_bytes, void *stream)
-{
-    const int ones = colsum_A ? 1 : 0;
-    int rc = gemm_tn_check(Ka, Kb + ones, M);
-    if (rc != TVR_OK) return rc;
-    if (!C || !scale_dev || (M > 0 && (!A || !B))) return fail(TVR_ERR_INVALID, "A/B/C/scale_dev NULL");
-    if (lda < Ka || ldb < Kb) return fail(TVR_ERR_INVALID, "lda/ldb smaller than the row length");
-    if (Ka > 128 || 16 * (Ka + Kb) > 256 * 20) return fail(TVR_ERR_UNSUPPORTED, "the fp16-split form takes Ka <= 128 and Ka + Kb <= 320 (Ka = %d, Kb = %d)", Ka, Kb);
-    if (M > 0 && (!scratch || scratch_bytes < gemm_tn_scratch_bytes(Ka, Kb + ones, M))) return fail(TVR_ERR_SCRATCH, "scratch too small (tvr_gemm_tn_scratch_bytes(Ka, Kb + 1, M))");
-    HIP_TRY(launch_gemm_tn(A, lda, Ka, B, ldb, Kb, M, C, (float *)scratch, (hipStream_t)stream, nullptr, colsum_A, scale_dev));
-    return TVR_OK;
-}
-
-int tvr_gemm_tn_bias(const float *A, int32_t lda, int32_t Ka, const float *B, int32_t ldb, int32_t Kb, int64_t M, float *C, float *colsum_A, void *scratch,
-                     size_t scratch_bytes, void *stream)
-{
-    int rc = gemm_tn_check(Ka, Kb + 1, M);
-    if (rc != TVR_OK) return rc;
-    if (!C || !colsum_A || (M > 0 && (!A || !B))) return fail(TVR_ERR_INVALID, "A/B/C/colsum_A NULL");
-    if (lda < Ka || ldb < Kb) return fail(TVR_ERR_INVALID, "lda/ldb smaller than the row length");
-    if (16 * (Ka + Kb) > 256 * 20) return fail(TVR_ERR_UNSUPPORTED, "Ka + Kb = %d exceeds the 320 staged columns of the kernel that carries the ones column", Ka + Kb);
-    if (M > 0 && (!scratch || scratch_bytes < gemm_tn_scratch_bytes(Ka, Kb + 1, M))) return fail(TVR_ERR_SCRATCH, "scratch too small (tvr_gemm_tn_scratch_bytes(Ka, Kb + 1, M))");
-    HIP_TRY(launch_gemm_tn(A, lda, Ka, B, ldb, Kb, M, C, (float *)scratch, (hipStream_t)stream, nullptr, colsum_A));
     return TVR_OK;
 }
 
@@ -1833,10 +975,7 @@ int tvr_render_normals(tvr_scene *s, const float *rays, int64_t n_rays, int32_t 
     if (!scratch || scratch_bytes < L.total) return fail(TVR_ERR_SCRATCH, "tvr_render_normals: scratch %zu B < required %zu B", scratch_bytes, L.total);
     if ((uintptr_t)scratch % 256) return fail(TVR_ERR_SCRATCH, "tvr_render_normals: scratch must be 256-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
-    if (!s->cp) {                          // the same march as tvr_render's: the density volume, if one is attached
-        int rcv = ensure_dvol(s, stream);
-        if (rcv != TVR_OK) return rcv;
-    }
+    if (!s->cp) TRY(ensure_dvol(s, stream));       // the same march as tvr_render's: the density volume, if one is attached
     char *b = (char *)scratch;
     MarchOut mo;
     mo.counter = (unsigned *)(b + L.counter);
@@ -1884,8 +1023,7 @@ int tvr_app_feature_ref(tvr_scene *s, const float *xyz, int64_t m, float *featur
         NEED("features [m,27]", features_bytes, m, TVR_APPDIM);
         NEED("extra [m,8]", extra_bytes, m, 8);
     }
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
+    TRY(scene_ready(s));
     if (s->desc.variant != 1) return fail(TVR_ERR_INVALID, "tvr_app_feature_ref needs a REFTensoRF (variant 1) scene");
     if (m == 0) return TVR_OK;
     if (!xyz || !features || !extra || m < 0) return fail(TVR_ERR_INVALID, "xyz/features/extra NULL or m < 0");
@@ -1904,8 +1042,7 @@ int tvr_mlp_render_ref(tvr_scene *s, const float *viewdirs, const float *feature
 {
     NOT_CP(s);
     if (m > 0) NEED("rgb [m,3]", rgb_bytes, m, 3);
-    int rc = scene_ready(s);
-    if (rc != TVR_OK) return rc;
+    TRY(scene_ready(s));
     if (s->desc.variant != 1) return fail(TVR_ERR_INVALID, "tvr_mlp_render_ref needs a REFTensoRF (variant 1) scene");
     if (m == 0) return TVR_OK;
     if (!viewdirs || !features || !dot_product || !rgb || m < 0) return fail(TVR_ERR_INVALID, "viewdirs/features/dot_product/rgb NULL or m < 0");
